@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- mixtures/sec of the DPTN-AV forward (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,12 @@ A "step" = one forward of the whole hot path (libdptnav: head -> 12 TransformerD
 Mixtures are independent, so ranks shard by batch with no data-path collective (weak scaling); the only
 collectives are the timing barrier and a MAX over ranks of the elapsed time.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+--dump-outputs DIR writes what the last timed step computed (s1_pred / s2_pred; for the training configuration also
+the loss, the gradient norm and the updated parameters) as DIR/<name>.npy in float32, before any other leg runs.
+
+Rank 0 prints ONE JSON line.  A plain run (no --full) sets up, warms up, times the K steps and prints the contract
+fields only (metric, value, unit, ms_per_step, higher_is_better, dtype, ..., outputs_finite of the last timed step).
+With --full the line carries the contract fields plus
   "roofline"      -- the DOMINANT kernel class = the one with the largest device time per step in this very run
                      (since round 2 the fused attention block, not the recurrence): algorithmic FLOPs per launch / its mean
                      device time, measured live with HIP events recorded on the launch stream (dptnav_profile_*);
@@ -295,17 +300,41 @@ def bench_train(args, env, cfg, B, T, workload):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        stats = train_step(model, dict(batch0), crit, opt, 10.0, env=env)
+        last = dict(batch0)
+        stats = train_step(model, last, crit, opt, 10.0, env=env)
     torch.cuda.synchronize(dev)
     env.barrier()
     torch.cuda.synchronize(dev)
     mine = time.perf_counter() - t0
     elapsed = env.max_over_ranks(mine)
     per_rank_s = env.gather_over_ranks(mine)
+    if args.dump_outputs:
+        # the last step's model outputs, loss and gradient norm, and the parameters the optimizer left (identical on every rank)
+        arrays = {k: v for k, v in last.items() if k not in batch0 and torch.is_tensor(v)}
+        arrays.update(stats)
+        if env.rank == 0:
+            arrays["parameters"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        dump_outputs(args.dump_outputs, arrays, env.rank, env.world)
     if args.pmc_run:
         if env.rank == 0:
             print(json.dumps({"pmc_run": True, "config": args.config, "steps": args.steps, "ms_per_step": round(1e3 * elapsed / args.steps, 3)}),
                   flush=True)
+        env.close()
+        return
+    value = env.world * B * args.steps / elapsed
+    head = {"metric": "mixtures/sec DPTN-AV training step (fwd + PIT SI-SNR loss + bwd + clip + AdamW)",
+            "value": round(value, 3), "unit": "mixtures/sec", "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{workload}, batch={B} per GPU, T={T}, random-init weights (numpy seed 0)",
+                       "batch_per_gpu": B, "samples": T,
+                       "parallelism": f"dp{env.world} (one flat gradient all-reduce per step over RCCL)"}}
+    tail = {"rccl_ranks": env.backend_world() if env.backend == "nccl" else 0, "backend": env.backend,
+            "per_rank_mixtures_per_sec": [round(B * args.steps / t, 3) for t in per_rank_s],
+            "last_step": {k: round(float(v), 5) for k, v in stats.items()} if stats else None}
+    if not args.full:
+        if env.rank == 0:
+            print(json.dumps({**head, **tail}), flush=True)
         env.close()
         return
     eng = model._engine
@@ -317,17 +346,10 @@ def bench_train(args, env, cfg, B, T, workload):
     prof = eng.profile_read()
     eng.profile(False)
     if env.rank == 0:
-        value = env.world * B * args.steps / elapsed
         ttab = pmc_table(args.config, PMC_TABLE_TRAIN)
         flops = 3.0 * eng.flops_per_mixture(T)            # forward + backward (dgrad + wgrad), recomputes not counted
         print(json.dumps({
-            "metric": "mixtures/sec DPTN-AV training step (fwd + PIT SI-SNR loss + bwd + clip + AdamW)",
-            "value": round(value, 3), "unit": "mixtures/sec", "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{workload}, batch={B} per GPU, T={T}, random-init weights (numpy seed 0)",
-                       "batch_per_gpu": B, "samples": T,
-                       "parallelism": f"dp{env.world} (one flat gradient all-reduce per step over RCCL)"},
+            **head,
             "roofline": {"bound": "mfma", "kernel": "whole step", "achieved": round(value / env.world * flops / 1e12, 3),
                          "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(value / env.world * flops / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
@@ -337,9 +359,7 @@ def bench_train(args, env, cfg, B, T, workload):
                          if ttab else None,
                          "note": "algorithmic FLOPs = 3 x forward (612 GFLOP per mixture)"},
             "kernels_ms_per_step": {k: round(v[0] / psteps, 3) for k, v in prof.items()},
-            "rccl_ranks": env.backend_world() if env.backend == "nccl" else 0, "backend": env.backend,
-            "per_rank_mixtures_per_sec": [round(B * args.steps / t, 3) for t in per_rank_s],
-            "last_step": {k: round(float(v), 5) for k, v in stats.items()} if stats else None}), flush=True)
+            **tail}), flush=True)
     env.close()
 
 
@@ -675,6 +695,28 @@ def split_experiment(eng, mix, e1, e2, out, B, steps, warmup, dev):
             "agreement_db_vs_f32_run": round(min(agree(ref1, o2[0]), agree(ref2, o2[1])), 1), "budget_db": 51.0}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (rank r > 0: <name>.rank<r>.npy).  When the arrays of
+    this rank exceed their share of DUMP_BUDGET_BYTES, each is cut to a fixed, seeded sample of its flattened elements (the
+    same positions in every run of the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.size * 4 for a in host.values())
+    budget = DUMP_BUDGET_BYTES // max(1, world) - 4096 * len(host)     # (npy headers)
+    for k, a in host.items():
+        if total > budget and a.size > 1:
+            keep = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            log(f"dump-outputs: {k} cut to a seeded sample of {keep} of {a.size} elements")
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + (f".rank{rank}" if rank else "") + ".npy"), np.asarray(a, dtype=np.float32))
+    log(f"dump-outputs: {len(host)} arrays written to {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -697,7 +739,16 @@ def main():
                     "(dptnav_set_option; experiments / A-B runs): the line then carries them under config.options")
     ap.add_argument("--serialize", action="store_true", help="with --pmc-run: option serialize = 1 (the step's sub-batch launches one "
                     "after the other on one stream), the pass bench.py's roofline figures are taken from")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: per-kernel event passes and the "
+                    "roofline, the split-precision experiment, other configurations, bs = 1 latency, the training-step leg, the "
+                    "end-to-end inference leg and the CPU baseline (the --no-* options then drop single legs).  Without it a run "
+                    "sets up, warms up, times the steps and prints the contract fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed "
+                    "in its last step as DIR/<name>.npy (float32, at most 64 MB in all; inputs are seeded, so two builds can be "
+                    "compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
 
@@ -752,10 +803,31 @@ def main():
     elapsed = env.max_over_ranks(mine)
     per_rank_s = env.gather_over_ranks(mine)
     log(f"timed region: {args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"s1_pred": out[0], "s2_pred": out[1]}, env.rank, env.world)
     if args.pmc_run:
         if env.rank == 0:
             print(json.dumps({"pmc_run": True, "config": args.config, "steps": args.steps, "warmup": args.warmup,
                               "ms_per_step": round(1e3 * elapsed / args.steps, 4)}), flush=True)
+        env.close()
+        return 0
+    value = env.world * B * args.steps / elapsed
+    head = {
+        "metric": "mixtures/sec (2-spk, 4 s @ 8 kHz) DPTN-AV forward" if args.config == "dptn_av"
+                  else f"mixtures/sec {args.config} forward",
+        "value": round(value, 3), "unit": "mixtures/sec", "n_gpus": env.world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{workload}, batch={B} per GPU, T={T}, random-init weights (numpy seed 0)",
+                   "batch_per_gpu": B, "samples": T, "tokens_per_mixture": eng.chunks(T) * cfg.chunk_size,
+                   "options": args.opt or None, "parallelism": f"dp{env.world} (batch shards, no data-path collective)"}}
+    tail = {"backend": env.backend, "rccl_ranks": env.backend_world() if env.backend == "nccl" else 0,
+            "per_rank_mixtures_per_sec": [round(B * args.steps / t, 3) for t in per_rank_s]}
+    if not args.full:
+        # the headline figure alone: the outputs of the last timed step are checked, nothing else is run
+        finite = bool(torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all())
+        if env.rank == 0:
+            print(json.dumps({**head, "outputs_finite": finite, **tail}), flush=True)
         env.close()
         return 0
 
@@ -784,7 +856,6 @@ def main():
         n_cus = torch.cuda.get_device_properties(dev).multi_processor_count
         kernels = {k: round(v[0] / psteps, 4) for k, v in prof.items()}
         kernels_alone = {k: round(v[0] / psteps_alone, 4) for k, v in prof_alone.items()}
-        value = env.world * B * args.steps / elapsed
         whole = None
         tpath = os.path.relpath(PMC_TABLES.get(args.config, PMC_TABLE), ROOT)
         traffic_unit = (f"HBM bytes per launch, from {tpath} (PMC FETCH_SIZE x2 + WRITE_SIZE; {table_state(tab)})") if tab_ok \
@@ -797,14 +868,7 @@ def main():
                      "source": f"{tpath} (sum over kernels x launches per step; {table_state(tab)}; "
                                f"{tab.get('corrections', '')})"}
         line = {
-            "metric": "mixtures/sec (2-spk, 4 s @ 8 kHz) DPTN-AV forward" if args.config == "dptn_av"
-                      else f"mixtures/sec {args.config} forward",
-            "value": round(value, 3), "unit": "mixtures/sec", "n_gpus": env.world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{workload}, batch={B} per GPU, T={T}, random-init weights (numpy seed 0)",
-                       "batch_per_gpu": B, "samples": T, "tokens_per_mixture": S * K, "options": args.opt or None,
-                       "parallelism": f"dp{env.world} (batch shards, no data-path collective)"},
+            **head,
             "roofline": {"bound": "mfma", "kernel": dom["kernel"], "class": dom["class"], "achieved": dom["achieved"],
                          "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": dom["frac"],
                          "traffic": dom["traffic"], "traffic_unit": traffic_unit,
@@ -837,8 +901,7 @@ def main():
             "kernels_ms_per_step": kernels,
             "kernels_ms_per_step_serialised": kernels_alone,
             "outputs_finite": finite,
-            "backend": env.backend, "rccl_ranks": env.backend_world() if env.backend == "nccl" else 0,
-            "per_rank_mixtures_per_sec": [round(B * args.steps / t, 3) for t in per_rank_s],
+            **tail,
         }
     del eng, out, mix, e1, e2
     torch.cuda.empty_cache()

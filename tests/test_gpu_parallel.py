@@ -5,7 +5,7 @@ code runs one rank per GPU over RCCL).
     tensor is the mean of the two ranks' gradients, reduced IN PLACE by one collective (trainer.py:47 + the
     data-parallel all-reduce this repo adds, SURVEY.md 8e);
   * `python bench.py --gpus 2` with no launcher on the command line starts its own ranks and prints one JSON line with
-    n_gpus = 2 (forward and training-step configurations).
+    n_gpus = 2 (forward and training-step configurations), with --full and without it.
 """
 import json
 import os
@@ -81,11 +81,12 @@ def test_world2_training_step_allreduces_the_flat_gradient_in_place():
         assert err < 1e-6, (rank, err)                  # mean of two fp32 numbers: exact up to one rounding
 
 
-def _run_bench(extra, gpus=2):
+def _run_bench(extra, gpus=2, full=True):
     env = dict(os.environ, BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "2", "--no-cpu-baseline"] + (["--full"] if full else []) + extra, env=env,
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                 # rank 0 only
@@ -106,6 +107,28 @@ def test_bench_launches_its_own_ranks(config):
         assert "error" not in tr, tr
         assert tr["n_gpus"] == 2 and tr["parallelism"].startswith("dp2") and tr["value"] > 0 and np.isfinite(tr["last_loss"])
         assert abs(tr["value"] - 2 * 2 / (tr["ms_per_step"] / 1e3)) < 1e-2 * tr["value"]
+
+
+@pytest.mark.parametrize("config", ["dptn_av", "dptn_av_train"])
+def test_bench_plain_run_dumps_the_last_step(config, tmp_path):
+    """Without --full the line carries the contract fields and nothing that needs a pass of its own; --dump-outputs
+    writes the last timed step's results, each rank its own shard, and the same arguments give the same inputs."""
+    line = _run_bench(["--config", config, "--dump-outputs", str(tmp_path)], full=False)
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["ms_per_step"] > 0 and np.isfinite(line["value"])
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in line
+    assert "train_step" not in line and "roofline" not in line and "kernels_ms_per_step" not in line
+    for name in ("s1_pred", "s2_pred", "s1_pred.rank1", "s2_pred.rank1"):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape[0] == 2 and a.size == 2 * 32000 and np.isfinite(a).all()
+    assert not np.array_equal(np.load(tmp_path / "s1_pred.npy"), np.load(tmp_path / "s1_pred.rank1.npy"))
+    if config == "dptn_av_train":
+        assert np.isfinite(np.load(tmp_path / "loss.npy")) and np.load(tmp_path / "parameters.npy").size > 10 ** 6
+    else:
+        again = tmp_path / "again"
+        _run_bench(["--config", config, "--dump-outputs", str(again)], full=False)
+        for name in ("s1_pred", "s2_pred"):
+            np.testing.assert_array_equal(np.load(tmp_path / f"{name}.npy"), np.load(again / f"{name}.npy"))
 
 
 def test_bench_four_rank_rehearsal_reports_every_rank():

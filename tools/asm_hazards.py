@@ -14,6 +14,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "speech_separation_amd", "csrc")
@@ -22,13 +23,14 @@ NO_VGPR_FORM = {"dgrad_r.hip"}
 
 
 def asm_of(src):
-    out = os.path.join("/tmp", "asm_hazards_" + os.path.splitext(src)[0] + ".s")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC"] + ([] if src in NO_VGPR_FORM else ["-mllvm", "-amdgpu-mfma-vgpr-form"]) + [
-        "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise SystemExit(f"{src}: hipcc failed\n{r.stderr[-2000:]}")
-    return [ln.strip() for ln in open(out) if ln.strip() and not ln.strip().startswith(";") or ln.strip().startswith(";;#")]
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, os.path.splitext(src)[0] + ".s")
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC"] + ([] if src in NO_VGPR_FORM else ["-mllvm", "-amdgpu-mfma-vgpr-form"]) + [
+            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"{src}: hipcc failed\n{r.stderr[-2000:]}")
+        return [ln.strip() for ln in open(out) if ln.strip() and not ln.strip().startswith(";") or ln.strip().startswith(";;#")]
 
 
 def main():

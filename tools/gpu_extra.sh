@@ -7,7 +7,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 for cfg in dptn_audio dprnn_av; do
-  timeout -k 10 300 python bench.py --config $cfg --steps 10 --warmup 3 > $O/${TAG}_bench_$cfg.json 2> $O/${TAG}_bench_$cfg.err || { echo "bench $cfg failed"; tail -5 $O/${TAG}_bench_$cfg.err; }
+  timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --warmup 3 > $O/${TAG}_bench_$cfg.json 2> $O/${TAG}_bench_$cfg.err || { echo "bench $cfg failed"; tail -5 $O/${TAG}_bench_$cfg.err; }
   python - <<PY
 import json
 d=json.load(open("$O/${TAG}_bench_$cfg.json"))
@@ -15,7 +15,7 @@ s=d.get("split_bf16_experiment") or {}
 print("$cfg", d["value"], "ms", d["ms_per_step"], "whole frac", d["roofline"]["whole_path_frac"], "split", s.get("value"), s.get("agreement_db_vs_f32_run"))
 PY
 done
-timeout -k 10 600 python bench.py --config dptn_av_train --steps 10 --warmup 3 > $O/${TAG}_bench_train.json 2> $O/${TAG}_bench_train.err || { echo "bench train failed"; tail -5 $O/${TAG}_bench_train.err; }
+timeout -k 10 600 python bench.py --full --config dptn_av_train --steps 10 --warmup 3 > $O/${TAG}_bench_train.json 2> $O/${TAG}_bench_train.err || { echo "bench train failed"; tail -5 $O/${TAG}_bench_train.err; }
 python -c "
 import json; d=json.load(open('$O/${TAG}_bench_train.json')); print('train', d['value'], d['ms_per_step'], d['roofline']['frac'], d['last_step'])"
 export TMPDIR=/tmp

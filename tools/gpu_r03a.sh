@@ -6,5 +6,5 @@ timeout -k 10 800 python -m pytest tests/test_gpu_backward.py tests/test_gpu_par
    -k "reference_gradients or rccl or frozen" > $O/r03_a_tests.log 2>&1
 echo "tests exit $?"
 grep -n "dB (the\|passed\|failed\|Error" $O/r03_a_tests.log | tail -20
-timeout -k 10 600 python bench.py > $O/r03_a_bench.json 2> $O/r03_a_bench.err
+timeout -k 10 600 python bench.py --full > $O/r03_a_bench.json 2> $O/r03_a_bench.err
 echo "bench exit $?"; tail -5 $O/r03_a_bench.err; head -c 2500 $O/r03_a_bench.json

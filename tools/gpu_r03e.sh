@@ -2,7 +2,7 @@
 # headline bench (isolated rows) + kernel trace of config 2 (attn_block64) + MFMA-busy counters of both attention blocks
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $O/r03e_bench.json 2> $O/r03e_bench.err || { echo bench failed; tail -20 $O/r03e_bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $O/r03e_bench.json 2> $O/r03e_bench.err || { echo bench failed; tail -20 $O/r03e_bench.err; exit 1; }
 python - <<PY
 import json
 d=json.load(open("$O/r03e_bench.json"))

@@ -71,7 +71,7 @@ if has bench; then
 fi
 cd $R
 if has bench; then
-  timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo bench failed; tail -20 $O/${TAG}_bench.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo bench failed; tail -20 $O/${TAG}_bench.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$O/${TAG}_bench.json"))

@@ -11,7 +11,7 @@ if [ "$2" != "skiptests" ]; then
   echo "tests exit $?" | tee -a $O/${TAG}_tests.log
   tail -5 $O/${TAG}_tests.log
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo bench failed; tail -20 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo bench failed; tail -20 $O/${TAG}_bench.err; exit 1; }
 python - <<PY
 import json
 d=json.load(open("$O/${TAG}_bench.json"))
