@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define DPTNAV_ABI_VERSION 3
+#define DPTNAV_ABI_VERSION 4   /* 4: dptnav_config.mask_tail (the struct grew: a v3 caller is refused by the version check) */
 
 /* error codes */
 #define DPTNAV_OK 0
@@ -63,6 +63,12 @@ typedef struct dptnav_config {
   int32_t arch;            /* 0: DPTN blocks = TransformerDPRNN (dptn.py:9-52)
                               1: DPRNN blocks = IntraChunkRNN/InterChunkRNN (dprnn.py:7-89): LSTM -> fc -> LayerNorm -> +res,
                                  no attention; head and tail are identical (dprnn.py:200-227,260-274)           */
+  int32_t mask_tail;       /* 1 -> DPTNEncDec (dptn.py:82-208): per speaker m = ReLU(tanh(W_out u + b_out) *
+                                 sigmoid(W_gate u + b_gate)), decoder input m * encoded (dptn.py:141,189) instead of
+                                 postprocessing(u) + encoded.  Only with arch == 0 && audio_only == 1 (the only
+                                 combination the reference defines).  The weight table then holds
+                                 dprnn.output_gate.0.{weight,bias}, dprnn.output.0.{weight,bias} in place of
+                                 dprnn.postprocessing.0.*; option "fold_tail" does not apply (the tail is not linear). */
 } dptnav_config;
 
 typedef struct dptnav_ctx* dptnav_handle;
@@ -115,7 +121,8 @@ int dptnav_stage_head(dptnav_handle h, const float* mix, const float* e1, const 
 int dptnav_stage_path(dptnav_handle h, int block, int path, const float* x_in, float* x_out, int B, int S,
                       void* workspace, size_t workspace_bytes, void* stream);
 /* tail: PReLU + 1x1 conv + overlap-add + pad + postprocessing + skip + transposed conv + pad
- *   dptn_wav.py:47-61, 186-193 */
+ *   dptn_wav.py:47-61, 186-193; with mask_tail: ... + pad + ReLU(tanh(output) * sigmoid(output_gate)) * encoded
+ *   + transposed conv + pad (dptn.py:122-141, 185-193) */
 int dptnav_stage_tail(dptnav_handle h, const float* x, const float* encoded, int B, int64_t T, float* s1_pred,
                       float* s2_pred, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -133,7 +140,9 @@ int dptnav_sisnr_pairs(dptnav_handle h, const float* s1_pred, const float* s2_pr
 /* ---- introspection for tests / profiling ------------------------------------------------ */
 /* Offsets (in bytes, from the workspace base) of intermediates left behind by the LAST
  * dptnav_stage_path call: "qkv" (M,3N), "att" (M,N), "y1" (M,N) [post-LN1], "hc" (M,2H)
- * [ReLU(h_fwd|h_bwd)].  Returns non-zero for an unknown name. */
+ * [ReLU(h_fwd|h_bwd)]; after dptnav_stage_tail: "taps" (2,B,L,8) decoder tap products D[spk][b][l][j] =
+ * sum_c q[c][l] W_dec[c][j] of the decoder input q (columns j >= kernel_size_enc are 0).
+ * Returns non-zero for an unknown name. */
 int dptnav_workspace_tap(dptnav_handle h, int B, int64_t T, int Tv, const char* name, size_t* offset_bytes,
                          size_t* numel);
 /* ---- training step, path level (BASELINE config 4; DPTN architecture, num_features = 128, dropout 0) ------------
@@ -228,7 +237,9 @@ int dptnav_dropout_mask(dptnav_handle h, int block, int path, int B, int S, floa
  *                 fp32 kernel; the stage entry points always run whole paths.
  *   "fold_tail" (0/1, default 1): inference computes the decoder tap products as ONE contraction per frame,
  *                 [OLA(mask) | encoded] . [W_dec^T W_post | W_dec^T] + W_dec^T b_post (folded from the current weights on
- *                 every call), instead of the post-processing GEMM with a k-reduction epilogue.
+ *                 every call), instead of the post-processing GEMM with a k-reduction epilogue.  Ignored when
+ *                 mask_tail = 1: the masked tail (tanh / sigmoid / ReLU, then a product with encoded) does not fold; it
+ *                 always runs mask_tail.hip (one gather + 2N x N product + epilogue + tap contraction per frame tile).
  *   "wgrad2" (0/1, default 1): training computes the W_ih and W_hh gradients of an LSTM in one pass over dP, the four
  *                 (direction, gate-row half) problems of a path in one launch; 0 = eight single-gradient launches.
  *   "wgrad_ride" (0/1, default 1): training forms the out-projection and ffn.1 weight / bias gradients inside the

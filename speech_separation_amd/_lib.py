@@ -13,7 +13,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPTNAV_LIB: another build of the library (same-box A/B of two builds: tools/train_ab.py, tools/ab_option.py)
 LIB_PATH = os.environ.get("DPTNAV_LIB") or os.path.join(_HERE, "libdptnav.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class DptnavConfig(C.Structure):
@@ -21,7 +21,7 @@ class DptnavConfig(C.Structure):
 
     _fields_ = [(n, C.c_int32) for n in (
         "num_features", "video_emb_size", "hidden_video", "kernel_size_enc", "hidden_dim", "num_blocks",
-        "chunk_size", "step_size", "num_heads", "bidir", "audio_only", "arch")]
+        "chunk_size", "step_size", "num_heads", "bidir", "audio_only", "arch", "mask_tail")]
 
 
 _vp, _fp, _i, _i64, _sz = C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_size_t

@@ -30,7 +30,9 @@ SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "
            "attn_block64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            "lstm16s.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            "lstm4.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-           "lstm16x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "fcln.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+           "lstm16x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "fcln.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+           # mask_tail.hip: the masked tail of DPTNEncDec (plain VALU, no MFMA)
+           "mask_tail.hip": []}
 
 
 def _headers():

@@ -26,6 +26,7 @@
 #include "train_tail.h"
 #include "backward.h"
 #include "backward_ends.h"
+#include "mask_tail.h"
 
 namespace {
 
@@ -42,7 +43,7 @@ constexpr int QUEUE_SLOTS = 1024;
 
 struct Plan {  // workspace offsets in floats
   int64_t L, S, M;
-  size_t queue, vid, E, X0, X1, qkv, att, y1, pre, hc, stamps, wfold, wpack, wih, whh4, winp, total;
+  size_t queue, vid, E, X0, X1, qkv, att, y1, pre, hc, stamps, wfold, wpack, wih, whh4, winp, wmask, total;
   size_t qkv_n, att_n, y1_n, hc_n;
 };
 
@@ -306,8 +307,15 @@ void build_names(dptnav_ctx* c) {
   add("dprnn.speakers_separation.0.weight", 1);
   add("dprnn.speakers_separation.1.weight", 2 * N * N);
   add("dprnn.speakers_separation.1.bias", 2 * N);
-  add("dprnn.postprocessing.0.weight", N * N);
-  add("dprnn.postprocessing.0.bias", N);
+  if (g.mask_tail) {   // DPTN registers output_gate before output (dptn.py:103-111); its postprocessing is a bare ReLU
+    add("dprnn.output_gate.0.weight", N * N);
+    add("dprnn.output_gate.0.bias", N);
+    add("dprnn.output.0.weight", N * N);
+    add("dprnn.output.0.bias", N);
+  } else {
+    add("dprnn.postprocessing.0.weight", N * N);
+    add("dprnn.postprocessing.0.bias", N);
+  }
   add("decoder.weight", N * k);
   c->ptr.assign(c->names.size(), nullptr);
 }
@@ -399,6 +407,8 @@ int make_plan(dptnav_ctx* c, int B, int64_t T, int Tv, Plan* p) {
   p->whh4 = take((size_t)2 * g.num_blocks * 2 * 4 * H * H);
   // ... and of the attention in-projection weights of every path, for gemm_t.hip (training forward)
   p->winp = take(g.arch == 0 && N == 128 ? (size_t)2 * g.num_blocks * 3 * N * N : 0);
+  // masked tail: [W_out; W_gate] and the two biases packed from the current weights on every call (mask_tail.h)
+  p->wmask = take(g.mask_tail ? (size_t)2 * N * N + 2 * N : 0);
   p->total = o;
   return DPTNAV_OK;
 }
@@ -1083,7 +1093,18 @@ int run_tail(dptnav_ctx* c, Run& run, const float* x, const float* E, int B, int
   // T2: overlap-add gather -> post-processing conv -> + E -> decoder tap products
   const int ola = (int)((pl.S - 1) * g.step_size + g.chunk_size);
   const int left = (int)((pl.L - ola) / 2);
-  if (c->opt_fold_tail) {
+  if (g.mask_tail) {
+    // DPTNEncDec: ReLU(tanh(output(u)) * sigmoid(output_gate(u))) * E per speaker, then the decoder taps (mask_tail.hip).
+    // Not linear, so option fold_tail does not apply; the training forward runs it too (the backward recomputes it).
+    float* Wp = ws + pl.wmask;
+    ProfScope ps(c, CAT_POST, st);
+    int e = mask_tail_pack_launch(st, N, c->w("dprnn.output.0.weight"), c->w("dprnn.output.0.bias"),
+                                  c->w("dprnn.output_gate.0.weight"), c->w("dprnn.output_gate.0.bias"), Wp);
+    const MaskTailGeom mg{Z, E, B, (int)pl.L, (int)pl.S, g.chunk_size, g.step_size, left, ola, g.kernel_size_enc};
+    if (e == 0) e = mask_tail_fwd_launch(st, N, mg, Wp, c->w("decoder.weight"), D, c->num_cus);
+    if (e != 0) return c->fail(DPTNAV_ERR_HIP, "masked tail: %s", hipGetErrorString((hipError_t)e));
+    LAUNCH_CHECK(c, "masked tail");
+  } else if (c->opt_fold_tail) {
     // the three linear steps folded into one contraction of length 2N per frame (headtail.h); the training forward too:
     // its backward recomputes q from Z and E itself (run_tail_backward), nothing of the GEMM form is kept
     float* Wf = ws + pl.wfold;
@@ -1126,6 +1147,7 @@ struct PathTape {  // offsets in floats inside one path's tape
 struct BwdPlan {   // offsets in floats inside the backward workspace
   size_t queue, dz, dh, dg, dy1, datt, dqkv, slab, lnp, dxa, dxb, dq, du, de, dvi, dv, total;
   size_t wiht;                      // fragment-order copies of the weights dgrad_t.hip multiplies by (2 x W_ih, in_proj_weight), per path
+  size_t da, wm, gw;                // masked tail: d [a_out | a_gate] (rows x 2N), packed weights, weight-gradient scratch
   size_t dg2, dg3, slab2, queue2;   // more dP buffers / second slab region / ticket counters: the LSTM weight gradients on a side stream (option wgrad_side)
   int slab_wgs;
 };
@@ -1190,6 +1212,9 @@ int make_bwd_plan(dptnav_ctx* c, int B, int S, BwdPlan* p, int64_t L = 0, int Tv
   p->de = take((size_t)B * L * N);
   p->dvi = take((size_t)B * L * N);
   p->dv = take((size_t)B * (Tv > 0 ? Tv : 1) * N);
+  p->da = take(g.mask_tail ? (size_t)2 * B * L * 2 * N : 0);
+  p->wm = take(g.mask_tail ? (size_t)2 * N * N + 2 * N : 0);
+  p->gw = take(g.mask_tail ? (size_t)2 * N * N + 2 * N : 0);
   p->total = o;
   p->slab_wgs = BWD_SLAB_WGS;
   return DPTNAV_OK;
@@ -1872,6 +1897,42 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
         *slab = br.ws + br.pl.slab;
   auto G = [&](const char* name) { return br.gptr[c->slot(name)]; };
   int grid = 0;
+  if (g.mask_tail) {
+    // DPTNEncDec tail: recompute u, a, m per frame tile; DQ = d q * m (E's gradient through the product, summed over the
+    // speakers by head_bwd_frames_kernel), DA = d [a_out | a_gate], decoder weight-gradient partials (mask_tail.hip)
+    float *DA = br.ws + br.pl.da, *Wp = br.ws + br.pl.wm, *GW = br.ws + br.pl.gw;
+    const MaskTailGeom mg{Z, E, B, (int)L, S, K, P, left, ola, g.kernel_size_enc};
+    int e = mask_tail_pack_launch(st, N, c->w("dprnn.output.0.weight"), c->w("dprnn.output.0.bias"),
+                                  c->w("dprnn.output_gate.0.weight"), c->w("dprnn.output_gate.0.bias"), Wp);
+    if (e == 0)
+      e = mask_tail_bwd_launch(st, N, mg, Wp, c->w("decoder.weight"), d_s1, d_s2, T, c->stride, pad_left, DQ, DA, LNP,
+                               BWD_LNP_WGS, c->num_cus, &grid);
+    if (e != 0) return c->fail(DPTNAV_ERR_HIP, "masked tail backward: %s", hipGetErrorString((hipError_t)e));
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((N * 8 + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)N * 8, slab, 0);
+    hipLaunchKernelGGL(decoder_wgrad_finish_kernel, dim3((N * g.kernel_size_enc + 255) / 256), dim3(256), 0, st, slab,
+                       G("decoder.weight"), N, g.kernel_size_enc);
+    LAUNCH_CHECK(c, "masked tail backward + decoder weight grad");
+    br.slot = run.slot;
+    // [dW_out; dW_gate] = DA^T u and [db_out; db_gate] = column sums of DA in one pass, then into the four slots
+    {
+      ALoadCols yl{DA, rows, 2 * N, 0, 32};
+      ALoadOla xl{Z, N, B, (int)L, S, K, P, left, ola, 32};
+      if (int rc = launch_wgrad<2 * N, N>(c, br, "d mask weights", (rows + 31) / 32, yl, xl, GW, GW + 2 * N * N)) return rc;
+      e = mask_tail_grad_scatter_launch(st, N, GW, GW + 2 * N * N, G("dprnn.output.0.weight"), G("dprnn.output.0.bias"),
+                                        G("dprnn.output_gate.0.weight"), G("dprnn.output_gate.0.bias"));
+      if (e != 0) return c->fail(DPTNAV_ERR_HIP, "masked tail gradient scatter: %s", hipGetErrorString((hipError_t)e));
+    }
+    run.slot = br.slot;
+    // d u = DA [W_out; W_gate]
+    {
+      ALoadDense al{DA, rows, 2 * N, BMn};
+      EpiAddMaskStoreT<false, false> ep{DU, nullptr, nullptr, rows, N, BMn, N};
+      if (int rc = launch_gemm<2 * N, 1, WRn, WCn, true>(c, run, CAT_POST, "d u (masked tail)", Wp, (rows + BMn - 1) / BMn, 1,
+                                                        al, ep, nullptr, N))
+        return rc;
+    }
+    br.slot = run.slot;
+  } else {
   // T2 recompute: q = OLA(Z) W_post^T + b_post + E ; d q, d decoder.weight
   {
     ALoadOla al{Z, N, B, (int)L, S, K, P, left, ola, BMn};
@@ -1908,6 +1969,7 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
       return rc;
   }
   br.slot = run.slot;
+  }
   // overlap-add backward -> d Z ; separation conv gradients ; PReLU backward -> d x
   hipLaunchKernelGGL(ola_grad_gather_kernel, dim3((unsigned)M), dim3(64), 0, st, DU, DZs, N, B, (int)L, S, K, P, left);
   LAUNCH_CHECK(c, "ola backward");
@@ -2041,6 +2103,10 @@ int dptnav_create(const dptnav_config* cfg, dptnav_handle* out) {
   if (cfg->hidden_dim != 128) return bad("hidden_dim must be 128");
   if (cfg->arch != 0 && cfg->arch != 1) return bad("arch must be 0 (DPTN) or 1 (DPRNN)");
   if (cfg->arch == 0 && cfg->num_heads != 4) return bad("num_heads must be 4 (head dim 32 or 16)");
+  if (cfg->mask_tail != 0 && cfg->mask_tail != 1) return bad("mask_tail must be 0 or 1");
+  if (cfg->mask_tail && (cfg->arch != 0 || !cfg->audio_only))
+    return bad("mask_tail = 1 (DPTNEncDec) needs arch = 0 (DPTN blocks) and audio_only = 1: the reference defines no other "
+               "masked variant");
   if (cfg->kernel_size_enc < 2 || cfg->kernel_size_enc > 8) return bad("kernel_size_enc must be in [2,8]");
   if (cfg->num_blocks < 1) return bad("num_blocks must be >= 1");
   if (cfg->chunk_size < 1 || (cfg->arch == 0 && cfg->chunk_size > 256))
@@ -2354,6 +2420,7 @@ int dptnav_workspace_tap(dptnav_handle h, int B, int64_t T, int Tv, const char* 
   else if (n == "y1") { *off = pl.y1 * 4; *numel = pl.y1_n; }
   else if (n == "hc") { *off = pl.hc * 4; *numel = pl.hc_n; }
   else if (n == "encoded") { *off = pl.E * 4; *numel = (size_t)B * pl.L * h->cfg.num_features; }
+  else if (n == "taps") { *off = pl.att * 4; *numel = (size_t)2 * B * pl.L * 8; }
   else if (n == "lstm_stamps") { *off = pl.stamps * 4; *numel = (pl.total - pl.stamps); }
   else return h->fail(DPTNAV_ERR_INVALID, "unknown tap '%s'", name);
   return DPTNAV_OK;
@@ -2881,7 +2948,7 @@ double dptnav_flops_per_mixture(dptnav_handle h, int64_t T) {
   };
   double f = g.num_blocks * M * (path(K, 2) + path(S, g.bidir ? 2 : 1));
   f += 2 * N * 2 * N * M;                 // separation conv
-  f += 2 * 2 * N * N * L;                 // post-processing conv, both speakers
+  f += (g.mask_tail ? 2 : 1) * 2 * 2 * N * N * L;   // post-processing conv (masked tail: output + output_gate), both speakers
   f += 2 * N * g.kernel_size_enc * L;     // encoder
   f += 2 * 2 * N * g.kernel_size_enc * L; // decoder
   if (!g.audio_only) f += 2.0 * 2 * 50 * g.video_emb_size * (g.hidden_video / 2);
@@ -2895,7 +2962,8 @@ double dptnav_min_bytes_per_mixture(dptnav_handle h, int64_t T) {
   const double N = g.num_features, K = g.chunk_size;
   const double L = (double)dptnav_frames(h, T), S = (double)dptnav_chunks(h, T), M = S * K;
   const double A = M * N * 4, F = L * N * 4;
-  return g.num_blocks * 2 * 2 * A + (A + 2 * 2 * A) + 2 * 2 * F + 4 * F + F + 3.0 * T * 4;
+  // masked tail: the latent is read once more per speaker (the product m * encoded)
+  return g.num_blocks * 2 * 2 * A + (A + 2 * 2 * A) + 2 * 2 * F + 4 * F + F + 3.0 * T * 4 + (g.mask_tail ? 2 * F : 0);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@ Mirrors (does not import) the reference interface for this path:
   * ``DPTNAVWavEncDec(num_features, video_emb_size, hidden_video, kernel_size_enc, hidden_dim, num_blocks,
     chunk_size, step_size, num_heads, dropout, bidir)``            src/model/dptn_wav.py:137-150
   * ``DPTNWavEncDec(num_features, kernel_size_enc, ...)``           src/model/dptn_wav.py:72-83
+  * ``DPTNEncDec(num_features, kernel_size_enc, ...)``              src/model/dptn.py:154-165 (masked tail, dptn.py:103-115)
   * ``forward(mix, s1_embedding, s2_embedding, **batch) -> {"s1_pred","s2_pred"}``  dptn_wav.py:171,194
     -- called as ``self.model(**batch)`` by src/trainer/trainer.py:40 and inferencer.py:117, so unknown
     batch keys (mix_spectrogram, s1, s2, paths, ...) must be accepted and ignored.
@@ -170,7 +171,7 @@ class _DPTNBase(nn.Module):
         # model.train() under torch.no_grad(): the reference still applies attention dropout (nn.MultiheadAttention looks at
         # self.training only).  The dropout lives in the training kernels, so take that path and drop the tape; where it
         # is not built, say so instead of silently returning the eval-mode result.  DPRNN blocks have no dropout.
-        if self.training and self.cfg.arch == "dptn" and self.cfg.dropout > 0:
+        if self.training and self.cfg.blocks == "dptn" and self.cfg.dropout > 0:
             if not self._train_kernels_built():
                 raise NotImplementedError("train-mode forward (attention dropout) is built for num_features in {128, 64} "
                                           "only: call model.eval() for inference")
@@ -211,6 +212,22 @@ class DPTNWavEncDec(_DPTNBase):
                                     hidden_dim=hidden_dim, num_blocks=num_blocks, chunk_size=chunk_size,
                                     step_size=step_size, num_heads=num_heads, dropout=dropout, bidir=bool(bidir),
                                     audio_only=True))
+
+    def forward(self, mix, **batch):
+        return self._run(mix, None, None)
+
+
+class DPTNEncDec(_DPTNBase):
+    """Audio-only masked DPTN (src/configs/model/dptn.yaml) -- same constructor as the reference class of that name
+    (dptn.py:154-165).  Same blocks and separation conv as DPTNWavEncDec; per speaker the tail is
+    ReLU(tanh(output(u)) * sigmoid(output_gate(u))) * encoded instead of postprocessing(u) + encoded (dptn.py:141,189)."""
+
+    def __init__(self, num_features=64, kernel_size_enc=2, hidden_dim=32, num_blocks=6, chunk_size=10, step_size=5,
+                 num_heads=4, dropout=0.1, bidir=True):
+        super().__init__(DPTNConfig(num_features=num_features, kernel_size_enc=kernel_size_enc,
+                                    hidden_dim=hidden_dim, num_blocks=num_blocks, chunk_size=chunk_size,
+                                    step_size=step_size, num_heads=num_heads, dropout=dropout, bidir=bool(bidir),
+                                    audio_only=True, arch="dptn_mask"))
 
     def forward(self, mix, **batch):
         return self._run(mix, None, None)

@@ -39,7 +39,24 @@ class DPTNConfig:
     dropout: float = 0.1
     bidir: bool = True
     audio_only: bool = False  # True -> DPTNWavEncDec / DPRNNEncDec (no video branch)
-    arch: str = "dptn"        # "dptn": MHA + bi-LSTM blocks (dptn.py); "dprnn": bi-LSTM + fc blocks (dprnn.py:7-113)
+    arch: str = "dptn"        # "dptn": MHA + bi-LSTM blocks (dptn.py); "dprnn": bi-LSTM + fc blocks (dprnn.py:7-113);
+    #                           "dptn_mask": DPTN blocks with the masked tail of DPTNEncDec (dptn.py:82-208, audio only)
+
+    def __post_init__(self):
+        if self.arch not in ("dptn", "dprnn", "dptn_mask"):
+            raise ValueError(f"arch must be 'dptn', 'dprnn' or 'dptn_mask' (got {self.arch!r})")
+        if self.arch == "dptn_mask" and not self.audio_only:
+            raise ValueError("arch='dptn_mask' (DPTNEncDec) is audio-only: the reference defines no AV masked variant")
+
+    @property
+    def blocks(self) -> str:
+        """Block type of the separator: "dptn" (TransformerDPRNN, also for the masked variant) or "dprnn"."""
+        return "dprnn" if self.arch == "dprnn" else "dptn"
+
+    @property
+    def mask_tail(self) -> bool:
+        """True for DPTNEncDec: ReLU(tanh(W_out u + b_out) * sigmoid(W_gate u + b_gate)) * encoded (dptn.py:103-115,141,189)."""
+        return self.arch == "dptn_mask"
 
     # ---- derived sizes -------------------------------------------------
     @property
@@ -77,6 +94,9 @@ DPTN_AUDIO = DPTNConfig(num_features=64, audio_only=True)
 DPRNN_AUDIO = DPTNConfig(num_features=64, hidden_video=64, kernel_size_enc=2, hidden_dim=128, num_blocks=6,
                          chunk_size=250, step_size=125, audio_only=True, arch="dprnn")
 DPRNN_AV = DPTNConfig(**{**DPRNN_AUDIO.__dict__, "audio_only": False})
+#: src/configs/model/dptn.yaml (top-level config dptn.yaml): the masked DPTNEncDec (dptn.py:139-208)
+DPTN_MASK = DPTNConfig(num_features=64, kernel_size_enc=7, hidden_dim=128, num_blocks=6, chunk_size=150, step_size=75,
+                       num_heads=4, audio_only=True, arch="dptn_mask")
 #: small shape used by the golden fixtures (fast on every backend)
 DPTN_TINY = DPTNConfig(num_features=32, video_emb_size=24, hidden_video=32, kernel_size_enc=7,
                        hidden_dim=32, num_blocks=2, chunk_size=10, step_size=5, num_heads=4)
@@ -139,7 +159,7 @@ def state_dict_spec(cfg: DPTNConfig) -> List[Tuple[str, Tuple[int, ...]]]:
         for path in ("intra_chunk_block", "inter_chunk_block"):
             two_dirs = True if path == "intra_chunk_block" else cfg.bidir
             dims = {"N": N, "3N": 3 * N, "4H": 4 * H, "H": H, "DH": H * (2 if two_dirs else 1)}
-            for suffix, code in (_PATH_TENSORS if cfg.arch == "dptn" else _DPRNN_PATH_TENSORS):
+            for suffix, code in (_PATH_TENSORS if cfg.blocks == "dptn" else _DPRNN_PATH_TENSORS):
                 if suffix.endswith("_reverse") and not two_dirs:
                     continue
                 shape = tuple(dims[c] for c in code.split(","))
@@ -147,8 +167,14 @@ def state_dict_spec(cfg: DPTNConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     out.append(("dprnn.speakers_separation.0.weight", (1,)))
     out.append(("dprnn.speakers_separation.1.weight", (2 * N, N, 1, 1)))
     out.append(("dprnn.speakers_separation.1.bias", (2 * N,)))
-    out.append(("dprnn.postprocessing.0.weight", (N, N, 1)))
-    out.append(("dprnn.postprocessing.0.bias", (N,)))
+    if cfg.mask_tail:   # DPTN.__init__ registers output_gate before output (dptn.py:103-111); postprocessing is a bare ReLU
+        out.append(("dprnn.output_gate.0.weight", (N, N, 1)))
+        out.append(("dprnn.output_gate.0.bias", (N,)))
+        out.append(("dprnn.output.0.weight", (N, N, 1)))
+        out.append(("dprnn.output.0.bias", (N,)))
+    else:
+        out.append(("dprnn.postprocessing.0.weight", (N, N, 1)))
+        out.append(("dprnn.postprocessing.0.bias", (N,)))
     out.append(("decoder.weight", (N, 1, k)))
     return out
 
