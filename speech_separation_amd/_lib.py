@@ -73,6 +73,26 @@ SYMBOLS = {
     "dptnav_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
 }
 
+CTASNET_ABI_VERSION = 1
+
+#: name -> (restype, argtypes): every symbol include/ctasnet.h declares (Conv-TasNet forward, same shared object)
+CTASNET_SYMBOLS = {
+    "ctasnet_abi_version": (_i, []),
+    "ctasnet_create": (_i, [C.POINTER(_vp)]),
+    "ctasnet_destroy": (None, [_vp]),
+    "ctasnet_last_error": (C.c_char_p, [_vp]),
+    "ctasnet_num_weights": (_i, [_vp]),
+    "ctasnet_weight_name": (C.c_char_p, [_vp, _i]),
+    "ctasnet_weight_numel": (_i64, [_vp, _i]),
+    "ctasnet_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "ctasnet_frames": (_i64, [_i64]),
+    "ctasnet_out_len": (_i64, [_i64]),
+    "ctasnet_workspace_bytes": (_sz, [_vp, _i, _i64]),
+    "ctasnet_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+    "ctasnet_flops_per_mixture": (C.c_double, [_vp, _i64]),
+    "ctasnet_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -90,7 +110,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` at the repo root).  speech_separation_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -99,5 +119,7 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.dptnav_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libdptnav ABI {lib.dptnav_abi_version()} != binding {ABI_VERSION}: rebuild")
+    if lib.ctasnet_abi_version() != CTASNET_ABI_VERSION:
+        raise RuntimeError(f"ctasnet ABI {lib.ctasnet_abi_version()} != binding {CTASNET_ABI_VERSION}: rebuild")
     _lib = lib
     return lib

@@ -32,11 +32,13 @@ SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "
            "lstm4.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            "lstm16x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "fcln.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # mask_tail.hip: the masked tail of DPTNEncDec (plain VALU, no MFMA)
-           "mask_tail.hip": []}
+           "mask_tail.hip": [],
+           # ctasnet.hip: Conv-TasNet forward; instantiates the GEMM engine (same atomic-optimizer reason as dptnav.hip)
+           "ctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "dptnav.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h")]
 
 
 def source_digest() -> str:

@@ -464,3 +464,120 @@ def params_to_device(sd: Mapping[str, "object"], device) -> Dict[str, torch.Tens
         t = v if isinstance(v, torch.Tensor) else torch.from_numpy(v)
         out[k] = t.to(device=device, dtype=torch.float32).contiguous()
     return out
+
+
+class ConvTasNetEngine:
+    """Conv-TasNet forward (include/ctasnet.h): one handle <-> one device <-> the caller's current stream.  Same conventions
+    as DptnEngine: borrowed weights (bind / bound_to), a cached workspace taken through the optional `alloc` hook."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import convtasnet_state_dict_spec
+        self.device = torch.device(device)
+        self._alloc_hook = alloc
+        if self.device.type != "cuda":
+            raise RuntimeError("ConvTasNetEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _DeviceBoundLib(_lib.load(), self.device)
+        h = C.c_void_p()
+        rc = self.lib.ctasnet_create(C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"ctasnet_create failed ({rc}): {self.lib.ctasnet_last_error(None).decode()}")
+        self._h = h
+        self._ws: Optional[torch.Tensor] = None
+        self._bound: Optional[list] = None
+        spec = convtasnet_state_dict_spec()
+        names = [self.lib.ctasnet_weight_name(h, i).decode() for i in range(self.lib.ctasnet_num_weights(h))]
+        if names != [k for k, _ in spec]:
+            raise RuntimeError("libdptnav's Conv-TasNet weight table disagrees with speech_separation_amd.spec")
+        self.slots = spec
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.ctasnet_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc: int, what: str):
+        raise RuntimeError(f"{what} failed ({rc}): {self.lib.ctasnet_last_error(self._h).decode()}")
+
+    _alloc = DptnEngine._alloc
+    _empty = DptnEngine._empty
+
+    def bind(self, params: Mapping[str, torch.Tensor]):
+        """Borrow the parameter storages (no copies): call again if they are re-allocated."""
+        keep, ptrs = [], (C.c_void_p * len(self.slots))()
+        for i, (key, shape) in enumerate(self.slots):
+            if key not in params:
+                raise KeyError(f"missing parameter {key}")
+            t = params[key].detach()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{key}: expected {tuple(shape)}, got {tuple(t.shape)}")
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
+            keep.append(t)
+            ptrs[i] = t.data_ptr()
+        rc = self.lib.ctasnet_bind_weights(self._h, ptrs, len(self.slots))
+        if rc:
+            self._raise(rc, "ctasnet_bind_weights")
+        self._bound = keep
+        self._bound_ptrs = tuple(t.data_ptr() for t in keep)
+
+    def bound_to(self, params: Mapping[str, torch.Tensor]) -> bool:
+        if self._bound is None:
+            return False
+        return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
+
+    def frames(self, T: int) -> int:
+        return int(self.lib.ctasnet_frames(T))
+
+    def out_len(self, T: int) -> int:
+        return int(self.lib.ctasnet_out_len(T))
+
+    def workspace_bytes(self, B: int, T: int) -> int:
+        n = int(self.lib.ctasnet_workspace_bytes(self._h, B, T))
+        if n == 0:
+            raise RuntimeError(f"unsupported shape: {self.lib.ctasnet_last_error(self._h).decode()}")
+        return n
+
+    def _workspace(self, B: int, T: int) -> torch.Tensor:
+        need = self.workspace_bytes(B, T)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = self._alloc(need)
+        return self._ws
+
+    def flops_per_mixture(self, T: int) -> float:
+        return float(self.lib.ctasnet_flops_per_mixture(self._h, T))
+
+    def min_bytes_per_mixture(self, T: int) -> float:
+        return float(self.lib.ctasnet_min_bytes_per_mixture(self._h, T))
+
+    def forward(self, mix: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mix [B][T] -> (s1_pred, s2_pred), each [B][16 * (T // 16)], enqueued on the current stream."""
+        if mix.dim() != 2:
+            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
+        B, T = mix.shape
+        mix = _check(mix, "mix", (B, T), self.device)
+        if self._bound is None:
+            raise RuntimeError("ConvTasNetEngine.forward: weights not bound (call bind first)")
+        ws = self._workspace(B, T)
+        L = self.out_len(T)
+        if out is None:
+            s1, s2 = self._empty(B, L), self._empty(B, L)
+        else:
+            s1 = _check(out[0], "out[0]", (B, L), self.device)
+            s2 = _check(out[1], "out[1]", (B, L), self.device)
+            if not (out[0].is_contiguous() and out[1].is_contiguous()):
+                raise ValueError("out tensors must be contiguous")
+        rc = self.lib.ctasnet_forward(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            self._raise(rc, "ctasnet_forward")
+        return s1, s2

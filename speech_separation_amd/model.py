@@ -5,6 +5,7 @@ Mirrors (does not import) the reference interface for this path:
     chunk_size, step_size, num_heads, dropout, bidir)``            src/model/dptn_wav.py:137-150
   * ``DPTNWavEncDec(num_features, kernel_size_enc, ...)``           src/model/dptn_wav.py:72-83
   * ``DPTNEncDec(num_features, kernel_size_enc, ...)``              src/model/dptn.py:154-165 (masked tail, dptn.py:103-115)
+  * ``ConvTasNet(N, L)`` (inference only)                           src/model/convtasnet.py:101-116
   * ``forward(mix, s1_embedding, s2_embedding, **batch) -> {"s1_pred","s2_pred"}``  dptn_wav.py:171,194
     -- called as ``self.model(**batch)`` by src/trainer/trainer.py:40 and inferencer.py:117, so unknown
     batch keys (mix_spectrogram, s1, s2, paths, ...) must be accepted and ignored.
@@ -27,8 +28,8 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .engine import DptnEngine
-from .spec import DPTNConfig, state_dict_spec
+from .engine import ConvTasNetEngine, DptnEngine
+from .spec import DPTNConfig, convtasnet_state_dict_spec, state_dict_spec
 
 
 class _Node(nn.Module):
@@ -262,3 +263,71 @@ class DPRNNAVEncDec(_DPTNBase):
 
     def forward(self, mix, s1_embedding, s2_embedding, **batch):
         return self._run(mix, s1_embedding, s2_embedding)
+
+
+class ConvTasNet(nn.Module):
+    """Conv-TasNet (BASELINE configs[0], src/configs/model/convtasnet.yaml) -- same constructor as the reference class of
+    that name (src/model/convtasnet.py:101-116): N and L are accepted and ignored, as there.  Inference only: the forward
+    runs on libdptnav (include/ctasnet.h); the training step is not built."""
+
+    def __init__(self, N=512, L=16):
+        super().__init__()
+        self.N = N
+        self.L = L
+        for key, shape in convtasnet_state_dict_spec():
+            parts = key.split(".")
+            node: nn.Module = self
+            for name in parts[:-1]:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            p = nn.Parameter(torch.empty(*shape))
+            node.register_parameter(parts[-1], p)
+        self.reset_parameters()
+        self._engine: Optional[ConvTasNetEngine] = None
+
+    def reset_parameters(self):
+        """torch's defaults for the reference's modules: Conv1d / ConvTranspose1d weights U(+-1/sqrt(fan_in)) (kaiming_uniform,
+        a=sqrt 5) and biases with the matching bound; PReLU 0.25; GlobalNorm / GroupNorm ones and zeros."""
+        params = dict(self.named_parameters())
+        with torch.no_grad():
+            for key, p in params.items():
+                if key.endswith(("PReLU_1.weight", "PReLU_2.weight", "seq.0.weight")):
+                    p.fill_(0.25)
+                elif key.endswith(("gamma", "norm_1.weight", "norm_2.weight")):
+                    p.fill_(1.0)
+                elif key.endswith(("beta", "norm_1.bias", "norm_2.bias")):
+                    p.zero_()
+                else:
+                    w = params[key[:-len("bias")] + "weight"] if key.endswith("bias") else p
+                    b = 1.0 / math.sqrt(w[0].numel())
+                    p.uniform_(-b, b)
+
+    def _get_engine(self, device: torch.device) -> ConvTasNetEngine:
+        if device.type != "cuda":
+            raise RuntimeError(f"ConvTasNet computes only on an AMD GPU through libdptnav (got a {device} tensor); there is "
+                               f"no CPU/PyTorch fallback")
+        eng = self._engine
+        if eng is None or eng.device != device:
+            eng = ConvTasNetEngine(device)
+            self._engine = eng
+        params = dict(self.named_parameters())
+        for k, p in params.items():
+            if p.device != device:
+                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
+        if not eng.bound_to(params):
+            eng.bind(params)
+        return eng
+
+    def forward(self, mix, **batch):
+        eng = self._get_engine(mix.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("ConvTasNet: training step not built; use torch.no_grad()")
+        s1, s2 = eng.forward(mix)
+        return {"s1_pred": s1, "s2_pred": s2}
+
+    def __str__(self):
+        all_parameters = sum(p.numel() for p in self.parameters())
+        trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
+        return (super().__str__() + f"\nAll parameters: {all_parameters}"
+                + f"\nTrainable parameters: {trainable_parameters}")

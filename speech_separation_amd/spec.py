@@ -179,6 +179,26 @@ def state_dict_spec(cfg: DPTNConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
+def convtasnet_state_dict_spec() -> List[Tuple[str, Tuple[int, ...]]]:
+    """Ordered (key, shape) list == ``ConvTasNet().state_dict()`` of the reference (src/model/convtasnet.py:101-108; the
+    model ignores its N / L arguments: Encoder :7-10, GlobalNorm :19-22, Separator :56-63 with N=512, B=128, H=512, X=8,
+    P=3, R=3, Conv1D_Block :33-44, Decoder :86-90).  The order is the slot order of include/ctasnet.h's weight table."""
+    N, L, B, H, X, P, R = 512, 16, 128, 512, 8, 3, 3
+    out: List[Tuple[str, Tuple[int, ...]]] = [
+        ("encoder.conv1d.weight", (N, 1, 2 * L)), ("separator.norm_1.gamma", (N, 1)), ("separator.norm_1.beta", (N, 1)),
+        ("separator.conv1d.weight", (B, N, 1)), ("separator.conv1d.bias", (B,))]
+    for i in range(P * X):
+        p = f"separator.separator.{i}."
+        out += [(p + "conv1d.weight", (H, B, 1)), (p + "conv1d.bias", (H,)), (p + "PReLU_1.weight", (1,)),
+                (p + "norm_1.weight", (H,)), (p + "norm_1.bias", (H,)), (p + "dconv1d.weight", (H, 1, R)),
+                (p + "dconv1d.bias", (H,)), (p + "PReLU_2.weight", (1,)), (p + "norm_2.weight", (H,)),
+                (p + "norm_2.bias", (H,)), (p + "conv.weight", (B, H, 1)), (p + "conv.bias", (B,)),
+                (p + "conv_sc.weight", (B, H, 1)), (p + "conv_sc.bias", (B,))]
+    out += [("separator.seq.0.weight", (1,)), ("separator.seq.1.weight", (2 * N, B, 1)), ("separator.seq.1.bias", (2 * N,)),
+            ("decoder.deconv.weight", (N, 1, 2 * L))]
+    return out
+
+
 def num_parameters(cfg: DPTNConfig) -> int:
     return int(sum(int(np.prod(s)) for _, s in state_dict_spec(cfg)))
 

@@ -6,7 +6,8 @@ and publish it an iteration later, so the atomic's round trip is hidden -- unles
 an AGPR, which needs the value at once (`s_waitcnt vmcnt(0)` directly behind `global_atomic_add`: the A-tile prefetch's
 HBM latency and the atomic's round trip exposed on every tile).  This script compiles csrc/dptnav.hip to assembly and
 lists, per kernel, its ticket atomics ('.' = free, 'X' = waited for within three instructions); the third one of a kernel
-is the one inside the tile loop.    python3 tools/ticket_waits.py [--all]"""
+is the one inside the tile loop.    python3 tools/ticket_waits.py [--all] [SOURCE]
+SOURCE: another translation unit that instantiates the engine (a file name under csrc/ or a path); default dptnav.hip."""
 import os
 import re
 import subprocess
@@ -14,9 +15,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "speech_separation_amd", "csrc", "dptnav.hip")
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+src = os.path.join(ROOT, "speech_separation_amd", "csrc", args[0] if args else "dptnav.hip")
 with tempfile.TemporaryDirectory() as tmp:
-    out = os.path.join(tmp, "dptnav.s")
+    out = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0] + ".s")
     subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm",
                     "-amdgpu-atomic-optimizer-strategy=None", "-S", "--cuda-device-only", "-w", src, "-o", out], check=True)
     lines = open(out).read().split("\n")
