@@ -93,6 +93,27 @@ CTASNET_SYMBOLS = {
     "ctasnet_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
 }
 
+DCTASNET_ABI_VERSION = 1
+
+#: name -> (restype, argtypes): every symbol include/dctasnet.h declares (deep Conv-TasNet forward, same shared object)
+DCTASNET_SYMBOLS = {
+    "dctasnet_abi_version": (_i, []),
+    "dctasnet_create": (_i, [C.POINTER(_vp), _i]),
+    "dctasnet_destroy": (None, [_vp]),
+    "dctasnet_last_error": (C.c_char_p, [_vp]),
+    "dctasnet_num_weights": (_i, [_vp]),
+    "dctasnet_weight_name": (C.c_char_p, [_vp, _i]),
+    "dctasnet_weight_numel": (_i64, [_vp, _i]),
+    "dctasnet_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "dctasnet_frames": (_i64, [_i64]),
+    "dctasnet_out_len": (_i64, [_i64]),
+    "dctasnet_workspace_bytes": (_sz, [_vp, _i, _i64, _i]),
+    "dctasnet_forward": (_i, [_vp, _fp, _fp, _fp, _i, _i64, _i, _fp, _fp, _vp, _sz, _vp]),
+    "dctasnet_flops_per_mixture": (C.c_double, [_vp, _i64]),
+    "dctasnet_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
+    "dctasnet_weight_pack_bytes": (_sz, [_vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -110,7 +131,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` at the repo root).  speech_separation_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -121,5 +142,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"libdptnav ABI {lib.dptnav_abi_version()} != binding {ABI_VERSION}: rebuild")
     if lib.ctasnet_abi_version() != CTASNET_ABI_VERSION:
         raise RuntimeError(f"ctasnet ABI {lib.ctasnet_abi_version()} != binding {CTASNET_ABI_VERSION}: rebuild")
+    if lib.dctasnet_abi_version() != DCTASNET_ABI_VERSION:
+        raise RuntimeError(f"dctasnet ABI {lib.dctasnet_abi_version()} != binding {DCTASNET_ABI_VERSION}: rebuild")
     _lib = lib
     return lib

@@ -34,11 +34,13 @@ SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "
            # mask_tail.hip: the masked tail of DPTNEncDec (plain VALU, no MFMA)
            "mask_tail.hip": [],
            # ctasnet.hip: Conv-TasNet forward; instantiates the GEMM engine (same atomic-optimizer reason as dptnav.hip)
-           "ctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+           "ctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+           # deepctasnet.hip: DeepConvTasNet / DeepAVConvTasNet forward; instantiates the GEMM engine (same reason)
+           "deepctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h")]
 
 
 def source_digest() -> str:

@@ -1,0 +1,558 @@
+// deepctasnet.hip -- DeepConvTasNet / DeepAVConvTasNet inference forward (src/model/deepconvtasnet.py,
+// src/model/deepavconvtasnet.py) for gfx950: kernels, handle and the extern "C" boundary declared in include/dctasnet.h.
+//
+// The Separator is Conv-TasNet's, unchanged (ctasnet_kernels.h).  New here are the deep encoder / decoder -- eight dense
+// dilated k = 3 convs 512 -> 512, about 65 % of the FLOPs -- and the audio-visual head.
+//
+// Dense k = 3 conv: out[f] = bias + sum_k W_k x[f + s_k], with s_k = (k - 1) d for the Conv1d and s_k = (1 - k) d, W_k =
+// weight[:, :, k]^T for the stride-1 ConvTranspose1d (weight stored (in, out, k)).  It runs as three accumulating passes of
+// the weights-stationary engine, one per tap, each a KIN = 512 contraction: the A loader reads row f + s_k of the same
+// sequence (zero outside [0, F)), the epilogue stores bias + v (tap 0), adds v (tap 1), adds v and applies the PReLU (tap 2).
+// A K = 1536 slice does not fit the engine (its 128-column x 512 slice already holds 256 registers per lane).
+// The weights are repacked in every forward, into the workspace, in the engine's fragment order: one launch for the three
+// taps of all eight layers.  A copy made at bind time would go stale when load_state_dict copies into the same storages.
+//
+// Rows: the encoder runs on M = B*F rows [b*F + f][512].  The decoder runs on 2*B*F rows in (b, f, speaker) order: the
+// masked separator output ym[b*F + f][speaker*512 + n] read as rows of 512, so a frame step is two rows.  This keeps
+// Conv-TasNet's mask epilogue, decoder taps and overlap-add layout unchanged.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dctasnet.h"
+#include "common.h"
+// see ctasnet.hip: only dptnav.hip may define the engine's weight-packing kernel
+#define gemm_pack_rows_kernel dctasnet_unused_gemm_pack_rows_kernel
+#include "gemm_ws.h"
+#undef gemm_pack_rows_kernel
+#include "ctasnet_kernels.h"
+
+namespace {
+
+constexpr int DC_ENC_W = 14;                                   // encoder.sequential.{0..8}
+constexpr int DC_DEC_W = 14;                                   // decoder.sequential.{0..8}
+constexpr int DC_NW_AUDIO = DC_ENC_W + CT_SEP_W + DC_DEC_W + 1;   // + decoder.deconv.weight (unused)
+constexpr int DC_NW_AV = DC_NW_AUDIO + 4;                      // + visual_compression.{weight,bias}, video_ln.{weight,bias}
+constexpr int DC_SEP0 = DC_ENC_W, DC_DEC0 = DC_ENC_W + CT_SEP_W, DC_AV0 = DC_NW_AUDIO;
+constexpr int DC_LAYERS = 8;                                   // dense k = 3 convs: 4 encoder + 4 decoder
+constexpr int64_t DC_TAP_FLOATS = (int64_t)CT_N * CT_N;        // one tap of one layer, fragment order
+constexpr int DC_HV = 256;                                     // hidden_video / 2
+constexpr int DC_VT = 8;                                       // video frames per workgroup of the linear kernel
+
+thread_local std::string g_create_error;
+
+// ------------------------------------------------------------------------------------------------
+// weights -> fragment order (gemm_ws.h, ldw == 0): dst[(layer*3 + k)][cb 16][m 64][lane 64][4] = W_k[32 cb + (lane & 31)]
+// [8 m + 4 (lane >> 5) ..+3], W_k[o][i] the tap-k matrix.  Conv1d weight (o, i, k): the 12 floats of (o, i..i+3, 0..2) are
+// contiguous.  ConvTranspose1d weight (i, o, k): W_k[o][i] = weight[i][o][k]; lanes with consecutive o read consecutive
+// 12-byte groups.
+// ------------------------------------------------------------------------------------------------
+struct PackSrc { const float* w[DC_LAYERS]; };
+
+__global__ __launch_bounds__(256) void dctasnet_pack_kernel(PackSrc src, float* __restrict__ dst) {
+  const int layer = blockIdx.y;
+  const int f = blockIdx.x * 256 + threadIdx.x;                // < 512 * 512 / 4
+  const int lane = f & 63, m = (f >> 6) & 63, cb = f >> 12;
+  const int o = 32 * cb + (lane & 31), i0 = 8 * m + 4 * (lane >> 5);
+  const float* W = src.w[layer];
+  float v[4][3];
+  if (layer < DC_LAYERS / 2) {
+    const float4* p = reinterpret_cast<const float4*>(W + (int64_t)o * 3 * CT_N + 3 * i0);
+    const float4 a = p[0], b = p[1], c = p[2];
+    const float t[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[i][k] = t[3 * i + k];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[i][k] = W[((int64_t)(i0 + i) * CT_N + o) * 3 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    *reinterpret_cast<float4*>(dst + (layer * 3 + k) * DC_TAP_FLOATS + 4 * (int64_t)f) =
+        make_float4(v[0][k], v[1][k], v[2][k], v[3][k]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// engine hooks of the dense conv
+// ------------------------------------------------------------------------------------------------
+// row r of a pass reads row r + shift * 2^lg when frame (r >> lg) % F + shift lies in the sequence, else zeros
+struct ALoadTapShift {
+  const float* A;    // rows of 512
+  int M;             // rows (M * 512 < 2^31: dctasnet's plan)
+  int F;             // frames per sequence
+  int lg;            // log2(rows per frame): 0 encoder, 1 decoder (two speakers per frame)
+  int shift;         // tap offset in frames
+  DEV float4 load4(int tile, int row, int k4) const {
+    const int r = tile * CT_BM + row;
+    if (r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const int f = (r >> lg) % F + shift;
+    if (f < 0 || f >= F) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return *reinterpret_cast<const float4*>(A + (int64_t)(r + shift * (1 << lg)) * CT_N + 4 * k4);
+  }
+};
+
+// tap 0: out = v + bias; tap 1: out += v; tap 2: out = PReLU(out + v), then (last encoder conv) + the video row and the
+// row partials (n = 128 per column group) of the result for the GlobalNorm that follows.
+struct EpiTapConv {
+  static constexpr bool DIRECT = false;
+  static constexpr bool HAS_FINISH = false;
+  float* out;          // [M][512]
+  const float* bias;
+  const float* slope;
+  const float* vid;    // [M][512] or null
+  float2* part;        // [M][4] or null
+  int64_t M;
+  int tap;
+  struct Cols { float4 b; float a; };
+  DEV Cols cols(int colgroup, int c4) const {
+    return Cols{*reinterpret_cast<const float4*>(bias + colgroup * 128 + 4 * c4), *slope};
+  }
+  // the partial sum of the earlier taps: independent of the product (blockIdx.y is the engine's column group)
+  DEV float4 prefetch(int tile, int row, int c4) const {
+    const int64_t r = (int64_t)tile * CT_BM + row;
+    if (tap == 0 || r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return *reinterpret_cast<const float4*>(out + r * CT_N + blockIdx.y * 128 + 4 * c4);
+  }
+  DEV void row(int tile, int row, int colgroup, int c4, float4 v, float4 prev, const Cols& k) const {
+    const int64_t r = (int64_t)tile * CT_BM + row;
+    const int col = colgroup * 128 + 4 * c4;
+    if (tap == 0) {
+      v = make_float4(v.x + k.b.x, v.y + k.b.y, v.z + k.b.z, v.w + k.b.w);
+    } else {
+      v = make_float4(prev.x + v.x, prev.y + v.y, prev.z + v.z, prev.w + v.w);
+    }
+    if (tap == 2) {
+      v = make_float4(prelu(v.x, k.a), prelu(v.y, k.a), prelu(v.z, k.a), prelu(v.w, k.a));
+      if (vid != nullptr && r < M) {
+        const float4 e = *reinterpret_cast<const float4*>(vid + r * CT_N + col);
+        v = make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w);
+      }
+      if (part != nullptr) {       // uniform across the launch: every lane of the 32-lane group takes part
+        const float s = group_sum<32>((v.x + v.y) + (v.z + v.w));
+        const float mu = s * (1.0f / 128.0f);
+        const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
+        const float q = group_sum<32>((dx * dx + dy * dy) + (dz * dz + dw * dw));
+        if (r < M && c4 == 0) part[r * 4 + colgroup] = make_float2(s, q);
+      }
+    }
+    if (r >= M) return;
+    *reinterpret_cast<float4*>(out + r * CT_N + col) = v;
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
+// video head (deepavconvtasnet.py:140-151)
+// (1) vcat[b*Tv + t][s*256 + j] = bias[j] + sum_k Wvc[j][k] e_s[b][k][t]: one workgroup per (b, 8 frames), both speakers'
+//     embedding columns staged in LDS, thread j owns output column j
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dctasnet_video_linear_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
+                                                                    const float* __restrict__ Wvc, const float* __restrict__ bvc,
+                                                                    int Tv, float* __restrict__ vcat) {
+  __shared__ __attribute__((aligned(16))) float es[2][DC_VT][CT_N];
+  const int b = blockIdx.y, t0 = blockIdx.x * DC_VT, tid = threadIdx.x;
+  for (int i = tid; i < 2 * DC_VT * CT_N; i += 256) {          // t fastest: coalesced along the embedding's time axis
+    const int tt = i % DC_VT, k = (i / DC_VT) % CT_N, s = i / (DC_VT * CT_N);
+    const float* e = s ? e2 : e1;
+    es[s][tt][k] = t0 + tt < Tv ? e[((int64_t)b * CT_N + k) * Tv + t0 + tt] : 0.f;
+  }
+  __syncthreads();
+  const int j = tid;
+  const float bj = bvc[j];
+  float acc[2][DC_VT];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int tt = 0; tt < DC_VT; ++tt) acc[s][tt] = bj;
+  const float* wr = Wvc + (int64_t)j * CT_N;
+  for (int k4 = 0; k4 < CT_N / 4; ++k4) {
+    const float4 w = *reinterpret_cast<const float4*>(wr + 4 * k4);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int tt = 0; tt < DC_VT; ++tt) {
+        const float4 x = *reinterpret_cast<const float4*>(&es[s][tt][4 * k4]);
+        acc[s][tt] = fmaf(w.w, x.w, fmaf(w.z, x.z, fmaf(w.y, x.y, fmaf(w.x, x.x, acc[s][tt]))));
+      }
+  }
+#pragma unroll
+  for (int tt = 0; tt < DC_VT; ++tt)
+    if (t0 + tt < Tv) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) vcat[((int64_t)b * Tv + t0 + tt) * CT_N + s * DC_HV + j] = acc[s][tt];
+    }
+}
+
+// (2) vid[b*F + f] = LayerNorm_512(interpolate(vcat[b], Tv -> F, linear, align_corners=False)[f]): one wave per frame,
+//     lane: channels 4 lane .. +3 and 256 + 4 lane .. +3.  Interpolation arithmetic as the DPTN-AV head (headtail.h).
+__global__ __launch_bounds__(256) void dctasnet_video_frames_kernel(const float* __restrict__ vcat, const float* __restrict__ g,
+                                                                    const float* __restrict__ be, int F, int Tv, int64_t M,
+                                                                    float* __restrict__ vid) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  if (r >= M) return;                                          // wave-uniform
+  const int64_t b = r / F;
+  const int f = (int)(r - b * F);
+  const float scale = (float)Tv / (float)F;
+  float src = ((float)f + 0.5f) * scale - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  const int i0 = (int)floorf(src);
+  const int i1 = i0 + 1 < Tv ? i0 + 1 : Tv - 1;
+  const float lam = src - (float)i0;
+  float u[8];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ch = h * 256 + 4 * lane;
+    const float4 a = *reinterpret_cast<const float4*>(vcat + (b * Tv + i0) * CT_N + ch);
+    const float4 c = *reinterpret_cast<const float4*>(vcat + (b * Tv + i1) * CT_N + ch);
+    u[4 * h + 0] = a.x * (1.f - lam) + c.x * lam;
+    u[4 * h + 1] = a.y * (1.f - lam) + c.y * lam;
+    u[4 * h + 2] = a.z * (1.f - lam) + c.z * lam;
+    u[4 * h + 3] = a.w * (1.f - lam) + c.w * lam;
+  }
+  const float mu = wave_sum(((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7]))) * (1.0f / CT_N);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    u[i] -= mu;
+    q += u[i] * u[i];
+  }
+  const float rstd = rsqrtf(wave_sum(q) * (1.0f / CT_N) + 1e-5f);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ch = h * 256 + 4 * lane;
+    const float4 ga = *reinterpret_cast<const float4*>(g + ch), bb = *reinterpret_cast<const float4*>(be + ch);
+    *reinterpret_cast<float4*>(vid + r * CT_N + ch) =
+        make_float4(u[4 * h] * rstd * ga.x + bb.x, u[4 * h + 1] * rstd * ga.y + bb.y, u[4 * h + 2] * rstd * ga.z + bb.z,
+                    u[4 * h + 3] * rstd * ga.w + bb.w);
+  }
+}
+
+// overlap-add and crop with the output bias (deepconvtasnet.py:110, :116-118): as ctasnet_overlap_add_kernel, + bias
+__global__ __launch_bounds__(256) void dctasnet_overlap_add_kernel(const float* __restrict__ taps, const float* __restrict__ bias,
+                                                                   int B, int F, int64_t Lout, float* __restrict__ s1,
+                                                                   float* __restrict__ s2) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * (int64_t)B * Lout) return;
+  const int64_t bs = i / Lout, t = i - bs * Lout;
+  const int64_t b = bs >> 1;
+  const int s = (int)(bs & 1);
+  const int64_t j = t + CT_L, f = j / CT_L, k = j - f * CT_L;
+  const float* tp = taps + (b * F + f) * (4 * CT_L) + s * 2 * CT_L;
+  (s ? s2 : s1)[b * Lout + t] = (tp[k] + tp[k + CT_L - 4 * CT_L]) + *bias;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct Plan {
+  int64_t F, M, Lout;
+  size_t off_wpk, off_enc, off_x, off_skip, off_c, off_dec, off_taps, off_part, off_stats, off_vcat, total;
+};
+
+}  // namespace
+
+struct dctasnet_ctx {
+  std::string err;
+  std::vector<std::string> names;
+  std::vector<int64_t> numels;
+  std::vector<const float*> w;
+  bool av = false;
+  bool bound = false;
+  int device_id = 0;
+  int num_cus = 256;
+  int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    err = buf;
+    return code;
+  }
+};
+
+namespace {
+
+void build_names(dctasnet_ctx* c) {
+  auto add = [&](const std::string& n, int64_t numel) { c->names.push_back(n); c->numels.push_back(numel); };
+  const int64_t dense = (int64_t)CT_N * CT_N * 3;
+  add("encoder.sequential.0.weight", (int64_t)CT_N * 2 * CT_L);
+  add("encoder.sequential.0.bias", CT_N);
+  for (int i = 1; i <= 7; i += 2) {
+    const std::string p = "encoder.sequential.";
+    add(p + std::to_string(i) + ".weight", dense);
+    add(p + std::to_string(i) + ".bias", CT_N);
+    add(p + std::to_string(i + 1) + ".weight", 1);
+  }
+  add("separator.norm_1.gamma", CT_N);
+  add("separator.norm_1.beta", CT_N);
+  add("separator.conv1d.weight", (int64_t)CT_B * CT_N);
+  add("separator.conv1d.bias", CT_B);
+  for (int i = 0; i < CT_BLOCKS; ++i) {
+    const std::string p = "separator.separator." + std::to_string(i) + ".";
+    add(p + "conv1d.weight", (int64_t)CT_H * CT_B);
+    add(p + "conv1d.bias", CT_H);
+    add(p + "PReLU_1.weight", 1);
+    add(p + "norm_1.weight", CT_H);
+    add(p + "norm_1.bias", CT_H);
+    add(p + "dconv1d.weight", (int64_t)CT_H * CT_R);
+    add(p + "dconv1d.bias", CT_H);
+    add(p + "PReLU_2.weight", 1);
+    add(p + "norm_2.weight", CT_H);
+    add(p + "norm_2.bias", CT_H);
+    add(p + "conv.weight", (int64_t)CT_B * CT_H);
+    add(p + "conv.bias", CT_B);
+    add(p + "conv_sc.weight", (int64_t)CT_B * CT_H);
+    add(p + "conv_sc.bias", CT_B);
+  }
+  add("separator.seq.0.weight", 1);
+  add("separator.seq.1.weight", (int64_t)2 * CT_N * CT_B);
+  add("separator.seq.1.bias", 2 * CT_N);
+  for (int i = 0; i <= 6; i += 2) {
+    const std::string p = "decoder.sequential.";
+    add(p + std::to_string(i) + ".weight", dense);
+    add(p + std::to_string(i) + ".bias", CT_N);
+    add(p + std::to_string(i + 1) + ".weight", 1);
+  }
+  add("decoder.sequential.8.weight", (int64_t)CT_N * 2 * CT_L);
+  add("decoder.sequential.8.bias", 1);
+  add("decoder.deconv.weight", (int64_t)CT_N * 2 * CT_L);
+  if (c->av) {
+    add("visual_compression.weight", (int64_t)DC_HV * CT_N);
+    add("visual_compression.bias", DC_HV);
+    add("video_ln.weight", CT_N);
+    add("video_ln.bias", CT_N);
+  }
+}
+
+int64_t frames_of(int64_t T) { return T < CT_L ? 0 : (T + CT_L) / CT_L + 1; }
+
+int make_plan(dctasnet_ctx* c, int B, int64_t T, int Tv, Plan& p) {
+  if (B <= 0) return c->fail(DCTASNET_ERR_INVALID, "B must be >= 1 (got %d)", B);
+  if (T < CT_L) return c->fail(DCTASNET_ERR_INVALID, "T must be >= %d samples (got %lld): the output would be empty", CT_L,
+                               (long long)T);
+  if (c->av && Tv < 1) return c->fail(DCTASNET_ERR_INVALID, "Tv must be >= 1 for the audio-visual model (got %d)", Tv);
+  p.F = frames_of(T);
+  p.M = (int64_t)B * p.F;
+  // the decoder runs on 2*B*F rows of 512
+  if (2 * p.M * CT_N > (int64_t)INT32_MAX)
+    return c->fail(DCTASNET_ERR_INVALID, "2*B*F*512 = %lld exceeds 32-bit indexing (B=%d, T=%lld)", (long long)(2 * p.M * CT_N),
+                   B, (long long)T);
+  if (c->av && (int64_t)B * Tv * CT_N > (int64_t)INT32_MAX)
+    return c->fail(DCTASNET_ERR_INVALID, "B*Tv*512 = %lld exceeds 32-bit indexing (B=%d, Tv=%d)", (long long)B * Tv * CT_N, B, Tv);
+  p.Lout = CT_L * (T / CT_L);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
+  const size_t M = (size_t)p.M;
+  p.off_wpk = take((size_t)DC_LAYERS * 3 * DC_TAP_FLOATS * 4);
+  p.off_enc = take(M * CT_N * 4);       // encoder output (AV: fused with the video rows); the mask epilogue reads it
+  p.off_x = take(M * CT_B * 4);
+  p.off_skip = take(M * CT_B * 4);
+  p.off_c = take(M * 2 * CT_N * 4);     // separator c | w, then ym [M][1024]; encoder ping-pong buffer before that
+  p.off_dec = take(M * 2 * CT_N * 4);   // decoder ping-pong buffer; the video rows [M][512] before that
+  p.off_taps = take(M * 4 * CT_L * 4);
+  p.off_part = take(M * 4 * sizeof(float2));
+  p.off_stats = take((size_t)B * 2 * sizeof(float2));
+  p.off_vcat = take(c->av ? (size_t)B * Tv * CT_N * 4 : 0);
+  p.total = o;
+  return DCTASNET_OK;
+}
+
+// one dense k = 3 conv: three passes of the engine on the fragment-order taps wpk[3][512 * 512]
+int launch_dense(dctasnet_ctx* c, hipStream_t st, const float* wpk, bool transposed, int dil, const float* x, float* y,
+                 int64_t rows, int F, int lg, const float* bias, const float* slope, const float* vid, float2* part) {
+  for (int k = 0; k < 3; ++k) {
+    const int shift = transposed ? (1 - k) * dil : (k - 1) * dil;
+    if (int rc = launch_gemm<CT_N>(c, st, "dctasnet dense conv", wpk + k * DC_TAP_FLOATS, nullptr, rows, CT_N / 128,
+                                   ALoadTapShift{x, (int)rows, F, lg, shift},
+                                   EpiTapConv{y, bias, slope, k == 2 ? vid : nullptr, k == 2 ? part : nullptr, rows, k}, 0))
+      return rc;
+  }
+  return DCTASNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dctasnet_abi_version(void) { return DCTASNET_ABI_VERSION; }
+
+int dctasnet_create(dctasnet_handle* out, int av) {
+  if (!out) {
+    g_create_error = "out must not be NULL";
+    return DCTASNET_ERR_INVALID;
+  }
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    g_create_error = "no HIP device visible: libdptnav's deep Conv-TasNet has no CPU path";
+    return DCTASNET_ERR_INVALID;
+  }
+  dctasnet_ctx* c = new dctasnet_ctx();
+  c->av = av != 0;
+  int devid = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDevice(&devid) == hipSuccess) c->device_id = devid;
+  if (hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
+  build_names(c);
+  c->w.assign(c->names.size(), nullptr);
+  *out = c;
+  return DCTASNET_OK;
+}
+
+void dctasnet_destroy(dctasnet_handle h) { delete h; }
+
+const char* dctasnet_last_error(dctasnet_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int dctasnet_num_weights(dctasnet_handle h) { return h ? (int)h->names.size() : 0; }
+
+const char* dctasnet_weight_name(dctasnet_handle h, int i) {
+  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
+}
+
+int64_t dctasnet_weight_numel(dctasnet_handle h, int i) {
+  return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1;
+}
+
+int dctasnet_bind_weights(dctasnet_handle h, const float* const* dev_ptrs, int n) {
+  if (!h) return DCTASNET_ERR_INVALID;
+  const int nw = (int)h->names.size();
+  if (n != nw || !dev_ptrs) return h->fail(DCTASNET_ERR_WEIGHTS, "expected %d weight pointers, got %d", nw, n);
+  for (int i = 0; i < n; ++i) {
+    if (!dev_ptrs[i]) return h->fail(DCTASNET_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
+    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 16)
+      return h->fail(DCTASNET_ERR_WEIGHTS, "weight %d (%s) is not 16-byte aligned", i, h->names[i].c_str());
+  }
+  h->w.assign(dev_ptrs, dev_ptrs + n);
+  h->bound = true;
+  return DCTASNET_OK;
+}
+
+int64_t dctasnet_frames(int64_t T) { return frames_of(T); }
+
+int64_t dctasnet_out_len(int64_t T) { return T < CT_L ? 0 : CT_L * (T / CT_L); }
+
+size_t dctasnet_workspace_bytes(dctasnet_handle h, int B, int64_t T, int Tv) {
+  if (!h) return 0;
+  Plan p;
+  if (make_plan(h, B, T, Tv, p)) return 0;
+  return p.total;
+}
+
+int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,
+                     float* s1_pred, float* s2_pred, void* ws, size_t ws_bytes, void* stream) {
+  if (!h) return DCTASNET_ERR_INVALID;
+  dctasnet_ctx* c = h;
+  if (!c->bound) return c->fail(DCTASNET_ERR_WEIGHTS, "weights not bound (dctasnet_bind_weights)");
+  if (!mix || !s1_pred || !s2_pred) return c->fail(DCTASNET_ERR_INVALID, "mix / s1_pred / s2_pred must not be NULL");
+  if (c->av && (!e1 || !e2)) return c->fail(DCTASNET_ERR_INVALID, "the audio-visual model needs both speaker embeddings");
+  if (!c->av && (e1 || e2)) return c->fail(DCTASNET_ERR_INVALID, "the audio-only model takes no embeddings (pass NULL)");
+  Plan p;
+  if (int rc = make_plan(c, B, T, Tv, p)) return rc;
+  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
+    return c->fail(DCTASNET_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  float* wpk = reinterpret_cast<float*>(base + p.off_wpk);
+  float* enc = reinterpret_cast<float*>(base + p.off_enc);
+  float* cbuf = reinterpret_cast<float*>(base + p.off_c);
+  float* dec = reinterpret_cast<float*>(base + p.off_dec);
+  float* taps = reinterpret_cast<float*>(base + p.off_taps);
+  float2* part = reinterpret_cast<float2*>(base + p.off_part);
+  float2* stats1 = reinterpret_cast<float2*>(base + p.off_stats);
+  const SepBuffers sb{reinterpret_cast<float*>(base + p.off_x), reinterpret_cast<float*>(base + p.off_skip), cbuf,
+                      cbuf + p.M * CT_N, part, stats1, stats1 + B};
+  const int F = (int)p.F;
+  const int64_t M = p.M;
+  const auto& W = c->w;
+
+  // weights of the eight dense convs -> fragment order, this forward's copy
+  PackSrc ps;
+  for (int l = 0; l < 4; ++l) {
+    ps.w[l] = W[2 + 3 * l];                   // encoder.sequential.{1,3,5,7}.weight
+    ps.w[4 + l] = W[DC_DEC0 + 3 * l];         // decoder.sequential.{0,2,4,6}.weight
+  }
+  hipLaunchKernelGGL(dctasnet_pack_kernel, dim3((unsigned)(DC_TAP_FLOATS / 4 / 256), DC_LAYERS), dim3(256), 0, st, ps, wpk);
+  CT_LAUNCH_CHECK(c, "dctasnet weight pack");
+
+  // video rows (deepavconvtasnet.py:140-151), kept in the decoder's buffer until the encoder is done
+  float* vid = nullptr;
+  if (c->av) {
+    float* vcat = reinterpret_cast<float*>(base + p.off_vcat);
+    hipLaunchKernelGGL(dctasnet_video_linear_kernel, dim3((unsigned)((Tv + DC_VT - 1) / DC_VT), B), dim3(256), 0, st, e1, e2,
+                       W[DC_AV0], W[DC_AV0 + 1], Tv, vcat);
+    CT_LAUNCH_CHECK(c, "dctasnet video linear");
+    vid = dec;
+    hipLaunchKernelGGL(dctasnet_video_frames_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, vcat, W[DC_AV0 + 2],
+                       W[DC_AV0 + 3], F, Tv, M, vid);
+    CT_LAUNCH_CHECK(c, "dctasnet video frames");
+  }
+
+  // deep encoder (deepconvtasnet.py:7-26): Conv1d(1, 512, 32, 16) + bias, then 4 x [dense conv d, PReLU], d = 1, 2, 4, 8.
+  // Ping-pong enc <-> c; the last conv lands in enc, adds the video rows and writes the GlobalNorm partials.
+  const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
+  hipLaunchKernelGGL(ctasnet_encoder_kernel<true>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], W[1], enc, nullptr);
+  CT_LAUNCH_CHECK(c, "dctasnet encoder");
+  for (int l = 0; l < 4; ++l) {
+    const float* x = (l & 1) ? cbuf : enc;
+    float* y = (l & 1) ? enc : cbuf;
+    if (int rc = launch_dense(c, st, wpk + (int64_t)l * 3 * DC_TAP_FLOATS, false, 1 << l, x, y, M, F, 0, W[3 + 3 * l],
+                              W[4 + 3 * l], l == 3 ? vid : nullptr, l == 3 ? part : nullptr))
+      return rc;
+  }
+
+  // Separator: masks times the (fused) encoder output -> ym [M][1024] in c
+  if (int rc = launch_separator(c, st, W.data() + DC_SEP0, enc, 4, 128.0f, B, F, M, sb)) return rc;
+
+  // deep decoder (deepconvtasnet.py:96-120) on 2M rows (b, f, speaker): 4 x [dense ConvTranspose d, PReLU], d = 8, 4, 2, 1,
+  // ping-pong c <-> dec, ending in c; then ConvTranspose1d(512, 1, 32, 16) + bias as taps + overlap-add
+  for (int l = 0; l < 4; ++l) {
+    const float* x = (l & 1) ? dec : cbuf;
+    float* y = (l & 1) ? cbuf : dec;
+    if (int rc = launch_dense(c, st, wpk + (int64_t)(4 + l) * 3 * DC_TAP_FLOATS, true, 8 >> l, x, y, 2 * M, F, 1,
+                              W[DC_DEC0 + 1 + 3 * l], W[DC_DEC0 + 2 + 3 * l], nullptr, nullptr))
+      return rc;
+  }
+  if (int rc = launch_taps(c, st, cbuf, W[DC_DEC0 + 12], M, taps)) return rc;
+  const int64_t n_out = 2 * (int64_t)B * p.Lout;
+  hipLaunchKernelGGL(dctasnet_overlap_add_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, taps,
+                     W[DC_DEC0 + 13], B, F, p.Lout, s1_pred, s2_pred);
+  CT_LAUNCH_CHECK(c, "dctasnet overlap-add");
+  return DCTASNET_OK;
+}
+
+double dctasnet_flops_per_mixture(dctasnet_handle, int64_t T) {
+  const double F = (double)frames_of(T);
+  const double dense = 3.0 * CT_N * CT_N;
+  const double per_block = (double)CT_B * CT_H + (double)CT_H * CT_R + 2.0 * CT_H * CT_B;
+  const double sep = (double)CT_N * CT_B + CT_BLOCKS * per_block + (double)CT_B * 2 * CT_N;
+  const double mac = (double)CT_N * 2 * CT_L + 4.0 * dense + sep + 2.0 * 4.0 * dense + 2.0 * CT_N * 2 * CT_L;
+  return 2.0 * mac * F;
+}
+
+double dctasnet_min_bytes_per_mixture(dctasnet_handle h, int64_t T) {
+  // floats per frame that the launches read + write once each (row partials and per-mixture statistics are ~1 % and left out)
+  const double F = (double)frames_of(T);
+  const double dense = 3.0 * CT_N + 5.0 * CT_N;              // per row: 3 taps' A rows; out written, then twice read + written
+  const double enc = CT_N + 4.0 * dense + (h && h->av ? 2.0 * CT_N : 0.0);   // first conv; 4 dense; video rows out + in
+  const double sep = (CT_N + CT_B)                           // bottleneck: enc in, x out
+                     + CT_BLOCKS * ((CT_B + CT_H) + (CT_R * CT_H + CT_H) + (CT_H + 4.0 * CT_B))
+                     + (CT_B + CT_N + 2 * CT_N);               // mask GEMM: skip, enc in; ym out
+  const double dec = 2.0 * 4.0 * dense + (2 * CT_N + 4 * CT_L) + (4 * CT_L + 2 * CT_L);
+  return 4.0 * F * (enc + sep + dec) + 4.0 * (double)T;
+}
+
+size_t dctasnet_weight_pack_bytes(dctasnet_handle) { return (size_t)2 * DC_LAYERS * 3 * DC_TAP_FLOATS * 4; }
+
+}  // extern "C"

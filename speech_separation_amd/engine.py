@@ -581,3 +581,129 @@ class ConvTasNetEngine:
         if rc:
             self._raise(rc, "ctasnet_forward")
         return s1, s2
+
+
+class DeepConvTasNetEngine:
+    """DeepConvTasNet / DeepAVConvTasNet forward (include/dctasnet.h): one handle <-> one device <-> the caller's current
+    stream.  Same conventions as ConvTasNetEngine: borrowed weights (bind / bound_to), a cached workspace taken through the
+    optional `alloc` hook.  The library repacks the dense convs' weights in every forward, so nothing bound goes stale."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", av: bool = False, alloc=None):
+        from .spec import deepconvtasnet_state_dict_spec
+        self.device = torch.device(device)
+        self.av = bool(av)
+        self._alloc_hook = alloc
+        if self.device.type != "cuda":
+            raise RuntimeError("DeepConvTasNetEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _DeviceBoundLib(_lib.load(), self.device)
+        h = C.c_void_p()
+        rc = self.lib.dctasnet_create(C.byref(h), int(self.av))
+        if rc != 0:
+            raise RuntimeError(f"dctasnet_create failed ({rc}): {self.lib.dctasnet_last_error(None).decode()}")
+        self._h = h
+        self._ws: Optional[torch.Tensor] = None
+        self._bound: Optional[list] = None
+        spec = deepconvtasnet_state_dict_spec(self.av)
+        names = [self.lib.dctasnet_weight_name(h, i).decode() for i in range(self.lib.dctasnet_num_weights(h))]
+        if names != [k for k, _ in spec]:
+            raise RuntimeError("libdptnav's deep Conv-TasNet weight table disagrees with speech_separation_amd.spec")
+        self.slots = spec
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.dctasnet_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc: int, what: str):
+        raise RuntimeError(f"{what} failed ({rc}): {self.lib.dctasnet_last_error(self._h).decode()}")
+
+    _alloc = DptnEngine._alloc
+    _empty = DptnEngine._empty
+
+    def bind(self, params: Mapping[str, torch.Tensor]):
+        """Borrow the parameter storages (no copies): call again if they are re-allocated."""
+        keep, ptrs = [], (C.c_void_p * len(self.slots))()
+        for i, (key, shape) in enumerate(self.slots):
+            if key not in params:
+                raise KeyError(f"missing parameter {key}")
+            t = params[key].detach()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{key}: expected {tuple(shape)}, got {tuple(t.shape)}")
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
+            keep.append(t)
+            ptrs[i] = t.data_ptr()
+        rc = self.lib.dctasnet_bind_weights(self._h, ptrs, len(self.slots))
+        if rc:
+            self._raise(rc, "dctasnet_bind_weights")
+        self._bound = keep
+        self._bound_ptrs = tuple(t.data_ptr() for t in keep)
+
+    def bound_to(self, params: Mapping[str, torch.Tensor]) -> bool:
+        if self._bound is None:
+            return False
+        return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
+
+    def frames(self, T: int) -> int:
+        return int(self.lib.dctasnet_frames(T))
+
+    def out_len(self, T: int) -> int:
+        return int(self.lib.dctasnet_out_len(T))
+
+    def workspace_bytes(self, B: int, T: int, Tv: int = 0) -> int:
+        n = int(self.lib.dctasnet_workspace_bytes(self._h, B, T, Tv))
+        if n == 0:
+            raise RuntimeError(f"unsupported shape: {self.lib.dctasnet_last_error(self._h).decode()}")
+        return n
+
+    def _workspace(self, B: int, T: int, Tv: int) -> torch.Tensor:
+        need = self.workspace_bytes(B, T, Tv)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = self._alloc(need)
+        return self._ws
+
+    def flops_per_mixture(self, T: int) -> float:
+        return float(self.lib.dctasnet_flops_per_mixture(self._h, T))
+
+    def min_bytes_per_mixture(self, T: int) -> float:
+        return float(self.lib.dctasnet_min_bytes_per_mixture(self._h, T))
+
+    def weight_pack_bytes(self) -> int:
+        return int(self.lib.dctasnet_weight_pack_bytes(self._h))
+
+    def forward(self, mix: torch.Tensor, s1_embedding: Optional[torch.Tensor] = None,
+                s2_embedding: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mix [B][T] (+ s1/s2_embedding [B][512][Tv] for the audio-visual model) -> (s1_pred, s2_pred), each
+        [B][16 * (T // 16)], enqueued on the current stream."""
+        if mix.dim() != 2:
+            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
+        B, T = mix.shape
+        mix = _check(mix, "mix", (B, T), self.device)
+        Tv, e1, e2 = 0, None, None
+        if self.av:
+            if s1_embedding is None or s2_embedding is None:
+                raise ValueError("DeepAVConvTasNet needs s1_embedding and s2_embedding")
+            if s1_embedding.dim() != 3:
+                raise ValueError(f"s1_embedding: expected (B,512,Tv), got {tuple(s1_embedding.shape)}")
+            Tv = int(s1_embedding.shape[-1])
+            e1 = _check(s1_embedding, "s1_embedding", (B, 512, Tv), self.device)
+            e2 = _check(s2_embedding, "s2_embedding", (B, 512, Tv), self.device)
+        if self._bound is None:
+            raise RuntimeError("DeepConvTasNetEngine.forward: weights not bound (call bind first)")
+        ws = self._workspace(B, T, Tv)
+        L = self.out_len(T)
+        s1, s2 = self._empty(B, L), self._empty(B, L)
+        rc = self.lib.dctasnet_forward(self._h, mix.data_ptr(), _ptr(e1), _ptr(e2), B, T, Tv, s1.data_ptr(), s2.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            self._raise(rc, "dctasnet_forward")
+        return s1, s2

@@ -6,6 +6,8 @@ Mirrors (does not import) the reference interface for this path:
   * ``DPTNWavEncDec(num_features, kernel_size_enc, ...)``           src/model/dptn_wav.py:72-83
   * ``DPTNEncDec(num_features, kernel_size_enc, ...)``              src/model/dptn.py:154-165 (masked tail, dptn.py:103-115)
   * ``ConvTasNet(N, L)`` (inference only)                           src/model/convtasnet.py:101-116
+  * ``DeepConvTasNet(N, L)``, ``DeepAVConvTasNet(N, L, video_emb_size, hidden_video)`` (inference only)
+                                                                    src/model/deepconvtasnet.py:122-136, deepavconvtasnet.py:122-156
   * ``forward(mix, s1_embedding, s2_embedding, **batch) -> {"s1_pred","s2_pred"}``  dptn_wav.py:171,194
     -- called as ``self.model(**batch)`` by src/trainer/trainer.py:40 and inferencer.py:117, so unknown
     batch keys (mix_spectrogram, s1, s2, paths, ...) must be accepted and ignored.
@@ -28,8 +30,8 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .engine import ConvTasNetEngine, DptnEngine
-from .spec import DPTNConfig, convtasnet_state_dict_spec, state_dict_spec
+from .engine import ConvTasNetEngine, DeepConvTasNetEngine, DptnEngine
+from .spec import DPTNConfig, convtasnet_state_dict_spec, deepconvtasnet_state_dict_spec, state_dict_spec
 
 
 class _Node(nn.Module):
@@ -331,3 +333,93 @@ class ConvTasNet(nn.Module):
         trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
         return (super().__str__() + f"\nAll parameters: {all_parameters}"
                 + f"\nTrainable parameters: {trainable_parameters}")
+
+
+class DeepConvTasNet(nn.Module):
+    """Deep encoder / decoder Conv-TasNet (src/configs/model/deepconvtasnet.yaml) -- same constructor as the reference class
+    of that name (src/model/deepconvtasnet.py:122-136): N and L are accepted and ignored, as there.  Inference only: the
+    forward runs on libdptnav (include/dctasnet.h); the training step is not built."""
+
+    _AV = False
+
+    def __init__(self, N=512, L=16):
+        super().__init__()
+        self.N = N
+        self.L = L
+        for key, shape in deepconvtasnet_state_dict_spec(self._AV):
+            parts = key.split(".")
+            node: nn.Module = self
+            for name in parts[:-1]:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            node.register_parameter(parts[-1], nn.Parameter(torch.empty(*shape)))
+        self.reset_parameters()
+        self._engine: Optional[DeepConvTasNetEngine] = None
+
+    def reset_parameters(self):
+        """torch's defaults for the reference's modules: Conv1d / ConvTranspose1d / Linear weights U(+-1/sqrt(fan_in))
+        (kaiming_uniform, a=sqrt 5, fan_in = weight[0].numel()) and biases with the matching bound; PReLU 0.25; GlobalNorm /
+        GroupNorm / LayerNorm ones and zeros."""
+        params = dict(self.named_parameters())
+        with torch.no_grad():
+            for key, p in params.items():
+                if p.numel() == 1 and key.endswith(".weight") and not key.startswith("decoder.sequential.8"):
+                    p.fill_(0.25)                                   # every PReLU of the model
+                elif key.endswith(("gamma", "norm_1.weight", "norm_2.weight", "video_ln.weight")):
+                    p.fill_(1.0)
+                elif key.endswith(("beta", "norm_1.bias", "norm_2.bias", "video_ln.bias")):
+                    p.zero_()
+                else:
+                    w = params[key[:-len("bias")] + "weight"] if key.endswith("bias") else p
+                    b = 1.0 / math.sqrt(w[0].numel())
+                    p.uniform_(-b, b)
+
+    def _get_engine(self, device: torch.device) -> DeepConvTasNetEngine:
+        if device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} computes only on an AMD GPU through libdptnav (got a {device} tensor); "
+                               f"there is no CPU/PyTorch fallback")
+        eng = self._engine
+        if eng is None or eng.device != device:
+            eng = DeepConvTasNetEngine(device, av=self._AV)
+            self._engine = eng
+        params = dict(self.named_parameters())
+        for k, p in params.items():
+            if p.device != device:
+                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
+        if not eng.bound_to(params):
+            eng.bind(params)
+        return eng
+
+    def _run(self, mix, s1_embedding=None, s2_embedding=None):
+        eng = self._get_engine(mix.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(f"{type(self).__name__}: training step not built; use torch.no_grad()")
+        s1, s2 = eng.forward(mix, s1_embedding, s2_embedding)
+        return {"s1_pred": s1, "s2_pred": s2}
+
+    def forward(self, mix, **batch):
+        return self._run(mix)
+
+    def __str__(self):
+        all_parameters = sum(p.numel() for p in self.parameters())
+        trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
+        return (super().__str__() + f"\nAll parameters: {all_parameters}"
+                + f"\nTrainable parameters: {trainable_parameters}")
+
+
+class DeepAVConvTasNet(DeepConvTasNet):
+    """Audio-visual deep Conv-TasNet (src/configs/model/deepavconvtasnet.yaml) -- same constructor as the reference class
+    (src/model/deepavconvtasnet.py:122-134); N and L are ignored as there.  Only the built sizes video_emb_size = hidden_video
+    = 512 exist.  Inference only (include/dctasnet.h)."""
+
+    _AV = True
+
+    def __init__(self, N=512, L=16, video_emb_size=512, hidden_video=512):
+        if video_emb_size != 512 or hidden_video != 512:
+            raise NotImplementedError(f"DeepAVConvTasNet is built for video_emb_size=512, hidden_video=512 only (got "
+                                      f"video_emb_size={video_emb_size}, hidden_video={hidden_video})")
+        super().__init__(N=N, L=L)
+
+    def forward(self, mix, s1_embedding, s2_embedding, **batch):
+        return self._run(mix, s1_embedding, s2_embedding)

@@ -199,6 +199,28 @@ def convtasnet_state_dict_spec() -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
+def deepconvtasnet_state_dict_spec(av: bool = False) -> List[Tuple[str, Tuple[int, ...]]]:
+    """Ordered (key, shape) list == ``DeepConvTasNet().state_dict()`` (src/model/deepconvtasnet.py:122-129; 372 tensors,
+    11 379 386 parameters) or, with ``av``, ``DeepAVConvTasNet().state_dict()`` (src/model/deepavconvtasnet.py:122-134; 376
+    tensors, 11 511 738 parameters).  Encoder :7-21, the Separator of ConvTasNet, Decoder :96-112 (``decoder.deconv`` is
+    registered but never used by the forward), then the video head.  The order is the slot order of include/dctasnet.h."""
+    N, L = 512, 16
+    out: List[Tuple[str, Tuple[int, ...]]] = [("encoder.sequential.0.weight", (N, 1, 2 * L)), ("encoder.sequential.0.bias", (N,))]
+    for i in (1, 3, 5, 7):
+        out += [(f"encoder.sequential.{i}.weight", (N, N, 3)), (f"encoder.sequential.{i}.bias", (N,)),
+                (f"encoder.sequential.{i + 1}.weight", (1,))]
+    out += [(k, s) for k, s in convtasnet_state_dict_spec() if k.startswith("separator.")]
+    for i in (0, 2, 4, 6):
+        out += [(f"decoder.sequential.{i}.weight", (N, N, 3)), (f"decoder.sequential.{i}.bias", (N,)),
+                (f"decoder.sequential.{i + 1}.weight", (1,))]
+    out += [("decoder.sequential.8.weight", (N, 1, 2 * L)), ("decoder.sequential.8.bias", (1,)),
+            ("decoder.deconv.weight", (N, 1, 2 * L))]
+    if av:
+        out += [("visual_compression.weight", (N // 2, N)), ("visual_compression.bias", (N // 2,)),
+                ("video_ln.weight", (N,)), ("video_ln.bias", (N,))]
+    return out
+
+
 def num_parameters(cfg: DPTNConfig) -> int:
     return int(sum(int(np.prod(s)) for _, s in state_dict_spec(cfg)))
 
