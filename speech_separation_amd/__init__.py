@@ -2,16 +2,16 @@
 from .spec import DPRNN_AUDIO, DPRNN_AV, DPTN_AUDIO, DPTN_AV, DPTN_MASK, DPTNConfig, state_dict_spec, synthetic_inputs, synthetic_state_dict
 
 __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "DPRNN_AV", "DPRNNEncDec", "DPRNNAVEncDec", "state_dict_spec", "synthetic_state_dict", "synthetic_inputs",
-           "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "DeepConvTasNet", "DeepAVConvTasNet",
+           "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
            "DeepConvTasNetEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
-    if name in ("DptnEngine", "ConvTasNetEngine", "DeepConvTasNetEngine"):
+    if name in ("DptnEngine", "ConvTasNetEngine", "ConvTasNetTrainEngine", "DeepConvTasNetEngine"):
         from . import engine
         return getattr(engine, name)
     if name in ("DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "DPRNNEncDec", "DPRNNAVEncDec", "ConvTasNet",
-                "DeepConvTasNet", "DeepAVConvTasNet"):
+                "TrainableConvTasNet", "DeepConvTasNet", "DeepAVConvTasNet"):
         from . import model
         return getattr(model, name)
     if name in ("FusedAdamW", "clip_grad_norm_"):

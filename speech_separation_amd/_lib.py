@@ -114,6 +114,34 @@ DCTASNET_SYMBOLS = {
     "dctasnet_weight_pack_bytes": (_sz, [_vp]),
 }
 
+CTTRAIN_ABI_VERSION = 1
+
+#: name -> (restype, argtypes): every symbol include/ctasnet_train.h declares (Conv-TasNet training step, same shared object)
+CTTRAIN_SYMBOLS = {
+    "cttrain_abi_version": (_i, []),
+    "cttrain_create": (_i, [C.POINTER(_vp)]),
+    "cttrain_destroy": (None, [_vp]),
+    "cttrain_last_error": (C.c_char_p, [_vp]),
+    "cttrain_num_weights": (_i, [_vp]),
+    "cttrain_weight_name": (C.c_char_p, [_vp, _i]),
+    "cttrain_weight_numel": (_i64, [_vp, _i]),
+    "cttrain_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "cttrain_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
+    "cttrain_flat_offset": (_i64, [_vp, _i]),
+    "cttrain_flat_numel": (_i64, [_vp]),
+    "cttrain_frames": (_i64, [_i64]),
+    "cttrain_out_len": (_i64, [_i64]),
+    "cttrain_workspace_bytes": (_sz, [_vp, _i, _i64]),
+    "cttrain_train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+    "cttrain_train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+    "cttrain_tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
+    "cttrain_clip_scratch_bytes": (_sz, [_vp]),
+    "cttrain_grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
+    "cttrain_adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                                _vp]),
+    "cttrain_flops_per_mixture": (C.c_double, [_vp, _i64]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -131,7 +159,8 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` at the repo root).  speech_separation_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
+                      + list(CTTRAIN_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -144,5 +173,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"ctasnet ABI {lib.ctasnet_abi_version()} != binding {CTASNET_ABI_VERSION}: rebuild")
     if lib.dctasnet_abi_version() != DCTASNET_ABI_VERSION:
         raise RuntimeError(f"dctasnet ABI {lib.dctasnet_abi_version()} != binding {DCTASNET_ABI_VERSION}: rebuild")
+    if lib.cttrain_abi_version() != CTTRAIN_ABI_VERSION:
+        raise RuntimeError(f"cttrain ABI {lib.cttrain_abi_version()} != binding {CTTRAIN_ABI_VERSION}: rebuild")
     _lib = lib
     return lib

@@ -36,11 +36,13 @@ SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "
            # ctasnet.hip: Conv-TasNet forward; instantiates the GEMM engine (same atomic-optimizer reason as dptnav.hip)
            "ctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
            # deepctasnet.hip: DeepConvTasNet / DeepAVConvTasNet forward; instantiates the GEMM engine (same reason)
-           "deepctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+           "deepctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+           # ctasnet_train.hip: Conv-TasNet training step; instantiates the GEMM engine (same reason)
+           "ctasnet_train.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h")]
 
 
 def source_digest() -> str:

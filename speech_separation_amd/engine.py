@@ -707,3 +707,206 @@ class DeepConvTasNetEngine:
         if rc:
             self._raise(rc, "dctasnet_forward")
         return s1, s2
+
+
+class ConvTasNetTrainEngine:
+    """Conv-TasNet training step (include/ctasnet_train.h): one handle <-> one device <-> the caller's current stream.
+    Borrowed weights (bind / bound_to) as ConvTasNetEngine; gradient buffers the library writes, all views of ONE flat
+    tensor in the layout of cttrain_flat_offset (bind_grads), and the clip / AdamW step over that layout, so that
+    optim.clip_grad_norm_, optim.FusedAdamW and train.allreduce_gradients take their fused paths.  The workspace holds the
+    tape of the last train_forward; train_backward refuses a tape that a later train_forward has overwritten."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import convtasnet_state_dict_spec
+        self.device = torch.device(device)
+        self._alloc_hook = alloc
+        if self.device.type != "cuda":
+            raise RuntimeError("ConvTasNetTrainEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _DeviceBoundLib(_lib.load(), self.device)
+        h = C.c_void_p()
+        rc = self.lib.cttrain_create(C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"cttrain_create failed ({rc}): {self.lib.cttrain_last_error(None).decode()}")
+        self._h = h
+        self._ws: Optional[torch.Tensor] = None
+        self._bound: Optional[list] = None
+        self._grads: Optional[Dict[str, torch.Tensor]] = None
+        self._grads_flat: Optional[torch.Tensor] = None
+        self._clip_ws: Optional[torch.Tensor] = None
+        self._tape_id = 0
+        spec = convtasnet_state_dict_spec()
+        names = [self.lib.cttrain_weight_name(h, i).decode() for i in range(self.lib.cttrain_num_weights(h))]
+        if names != [k for k, _ in spec]:
+            raise RuntimeError("libdptnav's Conv-TasNet training weight table disagrees with speech_separation_amd.spec")
+        self.slots = spec
+        self._grad_offsets = self.flat_offsets()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.cttrain_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc: int, what: str):
+        raise RuntimeError(f"{what} failed ({rc}): {self.lib.cttrain_last_error(self._h).decode()}")
+
+    _alloc = DptnEngine._alloc
+    _empty = DptnEngine._empty
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def bind(self, params: Mapping[str, torch.Tensor]):
+        """Borrow the parameter storages (no copies): call again if they are re-allocated."""
+        keep, ptrs = [], (C.c_void_p * len(self.slots))()
+        for i, (key, shape) in enumerate(self.slots):
+            if key not in params:
+                raise KeyError(f"missing parameter {key}")
+            t = params[key].detach()
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{key}: expected {tuple(shape)}, got {tuple(t.shape)}")
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
+            keep.append(t)
+            ptrs[i] = t.data_ptr()
+        rc = self.lib.cttrain_bind_weights(self._h, ptrs, len(self.slots))
+        if rc:
+            self._raise(rc, "cttrain_bind_weights")
+        self._bound = keep
+        self._bound_ptrs = tuple(t.data_ptr() for t in keep)
+
+    def bound_to(self, params: Mapping[str, torch.Tensor]) -> bool:
+        if self._bound is None:
+            return False
+        return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
+
+    def flat_offsets(self) -> Dict[str, int]:
+        """{state_dict key: offset in floats} of the flat gradient / optimizer-state layout (cttrain_flat_offset)."""
+        return {key: int(self.lib.cttrain_flat_offset(self._h, i)) for i, (key, _) in enumerate(self.slots)}
+
+    def flat_numel(self) -> int:
+        return int(self.lib.cttrain_flat_numel(self._h))
+
+    def bind_grads(self) -> Dict[str, torch.Tensor]:
+        """Allocate the gradient buffers the backward overwrites, as views of one flat tensor (`_grads_flat`, padding
+        zero), and bind them; returns {key: tensor}."""
+        offs = self._grad_offsets
+        flat = self._empty(self.flat_numel()).zero_()
+        grads, ptrs = {}, (C.c_void_p * len(self.slots))()
+        for i, (key, shape) in enumerate(self.slots):
+            n = 1
+            for d in shape:
+                n *= int(d)
+            g = flat[offs[key]:offs[key] + n].view(*shape)
+            grads[key] = g
+            ptrs[i] = g.data_ptr()
+        rc = self.lib.cttrain_bind_grads(self._h, ptrs, len(self.slots))
+        if rc:
+            self._raise(rc, "cttrain_bind_grads")
+        self._grads, self._grads_flat = grads, flat
+        return grads
+
+    def frames(self, T: int) -> int:
+        return int(self.lib.cttrain_frames(T))
+
+    def out_len(self, T: int) -> int:
+        return int(self.lib.cttrain_out_len(T))
+
+    def workspace_bytes(self, B: int, T: int) -> int:
+        n = int(self.lib.cttrain_workspace_bytes(self._h, B, T))
+        if n == 0:
+            raise RuntimeError(f"unsupported shape: {self.lib.cttrain_last_error(self._h).decode()}")
+        return n
+
+    def _workspace(self, B: int, T: int) -> torch.Tensor:
+        need = self.workspace_bytes(B, T)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = self._alloc(need)
+        return self._ws
+
+    def flops_per_mixture(self, T: int) -> float:
+        return float(self.lib.cttrain_flops_per_mixture(self._h, T))
+
+    def train_forward(self, mix: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, tuple]:
+        """mix [B][T] -> (s1_pred, s2_pred, tape); the tape lives in the engine's workspace until the next train_forward."""
+        if mix.dim() != 2:
+            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
+        B, T = mix.shape
+        mix = _check(mix, "mix", (B, T), self.device)
+        if self._bound is None:
+            raise RuntimeError("ConvTasNetTrainEngine.train_forward: weights not bound (call bind first)")
+        ws = self._workspace(B, T)
+        L = self.out_len(T)
+        s1, s2 = self._empty(B, L), self._empty(B, L)
+        rc = self.lib.cttrain_train_forward(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), self._stream())
+        if rc:
+            self._raise(rc, "cttrain_train_forward")
+        self._tape_id += 1
+        return s1, s2, (self._tape_id, B, T, ws.data_ptr())
+
+    TAPE_V1, TAPE_U, TAPE_SKIP = 0, 1, 2
+
+    def tape_tensor(self, tape: tuple, which: int, block: int = 0) -> torch.Tensor:
+        """A view of a pre-activation the forward of `tape` stored (cttrain_tape_offset): TAPE_V1 / TAPE_U of `block`
+        [B*F][512], TAPE_SKIP [B*F][128], frame-major.  Valid until the next train_forward (tests: PReLU branch masks)."""
+        tid, B, T, wsp = tape
+        if tid != self._tape_id or self._ws is None or self._ws.data_ptr() != wsp:
+            raise RuntimeError("tape_tensor: the tape was overwritten by a later train_forward")
+        off = int(self.lib.cttrain_tape_offset(self._h, B, T, which, block))
+        if off < 0:
+            self._raise(1, "cttrain_tape_offset")
+        M, C = B * self.frames(T), (128 if which == self.TAPE_SKIP else 512)
+        return self._ws[off:off + 4 * M * C].view(torch.float32).view(M, C)
+
+    def train_backward(self, mix: torch.Tensor, d_s1: torch.Tensor, d_s2: torch.Tensor, tape: tuple):
+        """d loss / d predictions -> the bound gradient buffers (overwritten), from the tape of `train_forward`."""
+        if self._grads is None:
+            raise RuntimeError("ConvTasNetTrainEngine.train_backward: gradients not bound (call bind_grads first)")
+        B, T = mix.shape
+        tid, tB, tT, tws = tape
+        if tid != self._tape_id or (tB, tT) != (B, T) or self._ws is None or self._ws.data_ptr() != tws:
+            raise RuntimeError("ConvTasNetTrainEngine.train_backward: the tape was overwritten by a later train_forward "
+                               "(one backward per forward, in order)")
+        mix = _check(mix, "mix", (B, T), self.device)
+        L = self.out_len(T)
+        d1 = _check(d_s1, "d_s1", (B, L), self.device)
+        d2 = _check(d_s2, "d_s2", (B, L), self.device)
+        ws = self._ws
+        rc = self.lib.cttrain_train_backward(self._h, mix.data_ptr(), B, T, d1.data_ptr(), d2.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), self._stream())
+        if rc:
+            self._raise(rc, "cttrain_train_backward")
+
+    def grad_clip(self, flat_grad: torch.Tensor, max_norm: Optional[float]) -> torch.Tensor:
+        """Scales `flat_grad` (flat layout) in place like clip_grad_norm_; returns the pre-clip norm as a 0-dim device tensor."""
+        flat_grad = _check(flat_grad, "flat_grad", (self.flat_numel(),), self.device)
+        need = int(self.lib.cttrain_clip_scratch_bytes(self._h))
+        if self._clip_ws is None:
+            self._clip_ws = self._alloc(need)
+        norm = self._empty(1)
+        rc = self.lib.cttrain_grad_clip(self._h, flat_grad.data_ptr(), flat_grad.numel(),
+                                        float(max_norm) if max_norm is not None else 0.0, self._clip_ws.data_ptr(), need,
+                                        norm.data_ptr(), self._stream())
+        if rc:
+            self._raise(rc, "cttrain_grad_clip")
+        return norm[0]
+
+    def adamw_step(self, flat_grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step: int):
+        n = self.flat_numel()
+        for t, name in ((flat_grad, "flat_grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            _check(t, name, (n,), self.device)
+        if self._bound is None:
+            raise RuntimeError("adamw_step: weights not bound")
+        rc = self.lib.cttrain_adamw_step(self._h, flat_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, float(lr),
+                                         float(beta1), float(beta2), float(eps), float(weight_decay), int(step), self._stream())
+        if rc:
+            self._raise(rc, "cttrain_adamw_step")

@@ -6,6 +6,7 @@ Mirrors (does not import) the reference interface for this path:
   * ``DPTNWavEncDec(num_features, kernel_size_enc, ...)``           src/model/dptn_wav.py:72-83
   * ``DPTNEncDec(num_features, kernel_size_enc, ...)``              src/model/dptn.py:154-165 (masked tail, dptn.py:103-115)
   * ``ConvTasNet(N, L)`` (inference only)                           src/model/convtasnet.py:101-116
+  * ``TrainableConvTasNet(N, L)`` (ConvTasNet with the training step) src/model/convtasnet.py:101-116
   * ``DeepConvTasNet(N, L)``, ``DeepAVConvTasNet(N, L, video_emb_size, hidden_video)`` (inference only)
                                                                     src/model/deepconvtasnet.py:122-136, deepavconvtasnet.py:122-156
   * ``forward(mix, s1_embedding, s2_embedding, **batch) -> {"s1_pred","s2_pred"}``  dptn_wav.py:171,194
@@ -30,7 +31,7 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .engine import ConvTasNetEngine, DeepConvTasNetEngine, DptnEngine
+from .engine import ConvTasNetEngine, ConvTasNetTrainEngine, DeepConvTasNetEngine, DptnEngine
 from .spec import DPTNConfig, convtasnet_state_dict_spec, deepconvtasnet_state_dict_spec, state_dict_spec
 
 
@@ -333,6 +334,94 @@ class ConvTasNet(nn.Module):
         trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
         return (super().__str__() + f"\nAll parameters: {all_parameters}"
                 + f"\nTrainable parameters: {trainable_parameters}")
+
+
+class _ConvTasNetTrainFn(torch.autograd.Function):
+    """TrainableConvTasNet's model part of the training step, as _SeparateFn: forward records the tape
+    (cttrain_train_forward), backward turns d loss / d predictions into every parameter's gradient
+    (cttrain_train_backward) and hands autograd views of one flat copy."""
+
+    @staticmethod
+    def forward(ctx, module, mix, *params):
+        eng = module._get_engine(mix.device)
+        if eng._grads is None:
+            eng.bind_grads()
+        s1, s2, tape = eng.train_forward(mix)
+        ctx.module, ctx.tape, ctx.mix = module, tape, mix
+        return s1, s2
+
+    @staticmethod
+    def backward(ctx, d_s1, d_s2):
+        eng = ctx.module._engine
+        mix = ctx.mix
+        L = eng.out_len(mix.shape[1])
+        zeros = lambda g: torch.zeros(mix.shape[0], L, device=mix.device) if g is None else g.contiguous()
+        eng.train_backward(mix, zeros(d_s1), zeros(d_s2), ctx.tape)
+        ctx.tape = None
+        # the library's gradient buffers are reused by the next step: autograd gets its own flat copy, whose views become
+        # .grad (train.allreduce_gradients and the fused clip / AdamW find it again through `_flat_grad`)
+        flat = eng._grads_flat.clone()
+        ctx.module._flat_grad = flat
+        outs = []
+        for k, shape in eng.slots:
+            o = eng._grad_offsets[k]
+            outs.append(flat[o:o + eng._grads[k].numel()].view(*shape))
+        return (None, None) + tuple(outs)
+
+
+class TrainableConvTasNet(ConvTasNet):
+    """ConvTasNet with the training step on libdptnav (include/ctasnet_train.h): same constructor, state_dict keys and
+    order, initialisation and parameter-count lines as ConvTasNet, and checkpoints load strictly either way.  Under
+    torch.no_grad() the forward is ConvTasNet's inference engine (bitwise the same outputs); with grad enabled it records
+    a tape and its backward computes every parameter's gradient in HIP.  `_get_engine` is the training engine, so
+    optim.clip_grad_norm_ / optim.FusedAdamW / train.train_step take their fused paths; stock torch optimizers work too."""
+
+    def __init__(self, N=512, L=16):
+        super().__init__(N, L)
+        self._engine: Optional[ConvTasNetTrainEngine] = None
+        self._infer_engine: Optional[ConvTasNetEngine] = None
+        self._flat_grad: Optional[torch.Tensor] = None
+        for p in self.parameters():
+            p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
+
+    def _bind(self, eng, device: torch.device):
+        params = dict(self.named_parameters())
+        for k, p in params.items():
+            if p.device != device:
+                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
+        if not eng.bound_to(params):
+            eng.bind(params)
+        return eng
+
+    @staticmethod
+    def _need_gpu(device: torch.device):
+        if device.type != "cuda":
+            raise RuntimeError(f"TrainableConvTasNet computes only on an AMD GPU through libdptnav (got a {device} tensor); "
+                               f"there is no CPU/PyTorch fallback")
+
+    def _get_engine(self, device: torch.device) -> ConvTasNetTrainEngine:
+        self._need_gpu(device)
+        eng = self._engine
+        if eng is None or eng.device != device:
+            eng = ConvTasNetTrainEngine(device)
+            self._engine = eng
+        return self._bind(eng, device)
+
+    def _get_infer_engine(self, device: torch.device) -> ConvTasNetEngine:
+        self._need_gpu(device)
+        eng = self._infer_engine
+        if eng is None or eng.device != device:
+            eng = ConvTasNetEngine(device)
+            self._infer_engine = eng
+        return self._bind(eng, device)
+
+    def forward(self, mix, **batch):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            self._need_gpu(mix.device)
+            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
+            return {"s1_pred": s1, "s2_pred": s2}
+        s1, s2 = self._get_infer_engine(mix.device).forward(mix)
+        return {"s1_pred": s1, "s2_pred": s2}
 
 
 class DeepConvTasNet(nn.Module):

@@ -1,0 +1,88 @@
+"""TEST INFRASTRUCTURE: the memory-safety child of tests/test_gpu_convtasnet_train.py (as tests/ctasnet_memsafety_child.py is
+for the inference forward), covering cttrain_train_forward and cttrain_train_backward.  One mode per process:
+
+mode  poison       the workspace, gradients and outputs the engine allocates start filled with 0xFF bytes
+      guard_end    every buffer (weights, inputs, upstream gradients, workspace, gradients, outputs) ENDS flush against an
+                   unmapped page (tests/guardmem)
+      guard_start  every buffer STARTS flush against an unmapped page
+
+The call sequence (a big batch, then smaller shapes on the cached workspace) runs under test first, then with plain
+zero-filled buffers; predictions and gradients must be bit-identical (fixed reduction order everywhere).
+
+    python -m tests.ctasnet_train_memsafety_child <mode>
+"""
+from __future__ import annotations
+
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from oracle.convtasnet_stock import synthetic_convtasnet_weights  # noqa: E402
+from speech_separation_amd.engine import ConvTasNetTrainEngine  # noqa: E402
+from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
+
+SHAPES = [(3, 4001), (1, 400), (2, 17)]
+
+
+def say(msg):
+    print(msg, flush=True)
+
+
+def run(dev, alloc, place):
+    eng = ConvTasNetTrainEngine(dev, alloc=alloc)
+    sd = synthetic_convtasnet_weights(seed=3)
+    eng.bind({k: place(torch.from_numpy(v)) for k, v in sd.items()})
+    eng.bind_grads()
+    res = {}
+    for B, T in SHAPES:
+        mix = place(torch.from_numpy(synthetic_inputs(DPTN_AUDIO, B=B, T=T, seed=B * 7 + T)["mix"]))
+        s1, s2, tape = eng.train_forward(mix)
+        g = torch.Generator().manual_seed(B * 11 + T)
+        L = eng.out_len(T)
+        d1, d2 = (place(torch.randn(B, L, generator=g)) for _ in range(2))
+        eng.train_backward(mix, d1, d2, tape)
+        torch.cuda.synchronize()
+        res[f"{B}x{T}.s1"], res[f"{B}x{T}.s2"] = s1.cpu().numpy(), s2.cpu().numpy()
+        res[f"{B}x{T}.grad"] = eng._grads_flat.cpu().numpy()
+    eng.close()
+    return res
+
+
+def main(mode):
+    dev = torch.device("cuda:0")
+    arena = None
+    say(f"== {mode} cttrain: run under test")
+    if mode == "poison":
+        got = run(dev, lambda n: torch.full((n,), 0xFF, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
+    elif mode in ("guard_end", "guard_start"):
+        from tests.guardmem import GuardArena
+        arena = GuardArena(0, flush="end" if mode == "guard_end" else "start", fill=0xFF)
+        got = run(dev, lambda n: arena.bytes(n, 256), lambda t: arena.like(t.contiguous()))
+    else:
+        raise SystemExit(f"unknown mode {mode}")
+    torch.cuda.synchronize()
+    if arena is not None:
+        say(f"guard arena: {len(arena.handles)} allocations, {arena.total / 2**20:.1f} MiB")
+        arena.close()
+    torch.cuda.empty_cache()
+    say(f"== {mode} cttrain: plain run")
+    want = run(dev, lambda n: torch.zeros(n, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
+    bad = [k for k in want if not (np.all(np.isfinite(got[k])) and np.array_equal(got[k], want[k]))]
+    for k in bad:
+        say(f"MISMATCH {k}")
+    if bad:
+        return 1
+    say(f"OK {mode} cttrain")
+    return 0
+
+
+if __name__ == "__main__":
+    rc = main(sys.argv[1])
+    sys.stdout.flush()
+    os._exit(rc)      # no interpreter teardown with guard mappings still referenced by tensors
