@@ -14,10 +14,12 @@ OUT = os.path.join(HERE, "libdptnav.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # translation units and their extra flags.  lstm.hip / lstm16.hip: MFMA accumulators in architectural VGPRs so that the 256 W_hh
 # fragments own the AGPRs and the step loop carries no v_accvgpr moves (see the file's header).
-# dptnav.hip: the GEMM engine's tile-ticket atomicAdd is issued by ONE lane a whole MFMA block before its result is used;
-# LLVM's atomic optimizer would turn it into a wave reduction + broadcast that waits for the result on the spot (wave 0
-# then sits out the round trip of a contended atomic every tile, the other waves wait for it at the next barrier).
-SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "lstm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "lstm16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+# Units that instantiate the GEMM engine (_GEMM_ENGINE_FLAGS): its tile-ticket atomicAdd is issued by ONE lane a whole MFMA
+# block before its result is used; LLVM's atomic optimizer would turn it into a wave reduction + broadcast that waits for
+# the result on the spot (wave 0 then sits out the round trip of a contended atomic every tile, the other waves wait for it
+# at the next barrier).
+_GEMM_ENGINE_FLAGS = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "lstm16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            "lstm_bptt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            "lstm_bptt16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # attn_block.hip: the softmax works on MFMA results with plain VALU instructions -> accumulators in architectural VGPRs
@@ -33,12 +35,9 @@ SOURCES = {"dptnav.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"], "
            "lstm16x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "fcln.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # mask_tail.hip: the masked tail of DPTNEncDec (plain VALU, no MFMA)
            "mask_tail.hip": [],
-           # ctasnet.hip: Conv-TasNet forward; instantiates the GEMM engine (same atomic-optimizer reason as dptnav.hip)
-           "ctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
-           # deepctasnet.hip: DeepConvTasNet / DeepAVConvTasNet forward; instantiates the GEMM engine (same reason)
-           "deepctasnet.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
-           # ctasnet_train.hip: Conv-TasNet training step; instantiates the GEMM engine (same reason)
-           "ctasnet_train.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+           # ctasnet.hip (Conv-TasNet forward), deepctasnet.hip (DeepConvTasNet / DeepAVConvTasNet forward), ctasnet_train.hip
+           # (Conv-TasNet training step): each instantiates the GEMM engine
+           "ctasnet.hip": _GEMM_ENGINE_FLAGS, "deepctasnet.hip": _GEMM_ENGINE_FLAGS, "ctasnet_train.hip": _GEMM_ENGINE_FLAGS}
 
 
 def _headers():

@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ Y
 // out[i] (+)= sum_s slab[s][i] in a FIXED association order: a block owns 32 consecutive elements,
 // its 8 slab-lanes each sum the slabs s = lane, lane+8, ... with four loads in flight, then the lanes are combined in
 // lane order.  (A single thread walking all slabs serially was latency-bound: ~10 % of the training step.)
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int nslabs, int64_t count,
+static __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int nslabs, int64_t count,
                                                            float* __restrict__ out, int accumulate) {
   __shared__ float red[8][32];
   const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(256) void ln_backward_kernel(const float* __restric
 // slab_reduce_kernel with two destinations (overwrite): split >= 0: elements [0, split) go to out_a, the rest to out_b
 // (LayerNorm: d gamma | d beta from one slab row); split < 0: every element goes to both (b_ih and b_hh have the same
 // gradient).  Same association order as slab_reduce_kernel.
-__global__ __launch_bounds__(256) void slab_reduce_to2_kernel(const float* __restrict__ slab, int nslabs, int64_t count,
+static __global__ __launch_bounds__(256) void slab_reduce_to2_kernel(const float* __restrict__ slab, int nslabs, int64_t count,
                                                                float* __restrict__ out_a, float* __restrict__ out_b, int split) {
   __shared__ float red[8][32];
   const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -969,7 +969,7 @@ __global__ __launch_bounds__(64 * NKB, (NKB >= 4 && NKB <= 6) ? 3 : 2) void atte
 
 // test helper: materialise the dropout keep-mask exactly as the attention kernels regenerate it
 //   mask[seq][head][query][key] in {0,1}
-__global__ void dropout_mask_kernel(float* __restrict__ mask, SeqGeom g, int heads, DropCfg drop) {
+static __global__ void dropout_mask_kernel(float* __restrict__ mask, SeqGeom g, int heads, DropCfg drop) {
   const int seq = blockIdx.x, head = blockIdx.y;
   const int64_t tok0 = seq_token_base(g, seq);
   const int tstride = seq_token_stride(g);

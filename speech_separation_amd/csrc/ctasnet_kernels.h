@@ -2,9 +2,10 @@
 // deepctasnet.hip (DeepConvTasNet / DeepAVConvTasNet) share: the encoder Conv1d(1, 512, 32, stride 16), the per-mixture
 // statistics, the 24-block separator (src/model/convtasnet.py:18-83, used unchanged by the deep variants), the mask GEMM and
 // the decoder's taps.  Everything sits in an anonymous namespace, so each including unit compiles its own copy.
-//
-// Include gemm_ws.h first, with its weight-packing kernel renamed (see ctasnet.hip): that kernel has external linkage and
-// only dptnav.hip may own it.
+// ctasnet_train.hip runs the same separator with TAPE = true: every block writes into its own slice of a tape and two
+// pre-activations are stored instead of the post-PReLU tensors (v1 = conv1d(x) + b instead of c = PReLU_1(v1), u =
+// dconv(...) + b instead of w = PReLU_2(u)); their consumers apply the PReLU while they load, with the same float
+// operations, so the predictions are bitwise those of the inference mode.
 //
 // Layout: frame-major, channel-last [row = b*F + f][channel], so every 1x1 conv is a row GEMM with M = B*F on the
 // weights-stationary engine (gemm_ws.h) and the depthwise conv reads rows f +- dil coalesced along channels.
@@ -150,12 +151,15 @@ __global__ __launch_bounds__(256) void ctasnet_stats_kernel(const float2* __rest
 // ------------------------------------------------------------------------------------------------
 // (b) depthwise dilated conv of the normalised c (convtasnet.py:49-51): w = PReLU_2(dconv(norm_1(c)))
 // Same thread map as the encoder; the zero padding applies to norm_1(c), so out-of-range taps contribute nothing.
+// TAPE: c holds v1 (PReLU_1 with slope1 on load; slope1 is not read otherwise) and w gets u, the pre-activation of PReLU_2.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ctasnet_dconv_kernel(const float* __restrict__ c, const float2* __restrict__ stats,
-                                                            const float* __restrict__ g1, const float* __restrict__ b1,
-                                                            const float* __restrict__ wd, const float* __restrict__ bd,
-                                                            const float* __restrict__ slope2, int dil, int F, int64_t M,
-                                                            float* __restrict__ w, float2* __restrict__ part) {
+template <bool TAPE>
+__global__ __launch_bounds__(256) void ctasnet_dconv_kernel(const float* __restrict__ c, const float* __restrict__ slope1,
+                                                            const float2* __restrict__ stats, const float* __restrict__ g1,
+                                                            const float* __restrict__ b1, const float* __restrict__ wd,
+                                                            const float* __restrict__ bd, const float* __restrict__ slope2,
+                                                            int dil, int F, int64_t M, float* __restrict__ w,
+                                                            float2* __restrict__ part) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int half = wave & 1, rsub = wave >> 1;
   const int ch = half * 256 + 4 * lane;
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(256) void ctasnet_dconv_kernel(const float* __restr
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int k = 0; k < CT_R; ++k) tap[j][k] = wd[(ch + j) * CT_R + k];
-  const float a2 = *slope2;
+  const float a1 = TAPE ? *slope1 : 0.f, a2 = *slope2;
   for (int i = 0; i < CT_ROWS_PER_WG / 2; ++i) {
     const int64_t r = (int64_t)blockIdx.x * CT_ROWS_PER_WG + 2 * i + rsub;
     if (r >= M) break;                              // wave-uniform
@@ -177,14 +181,16 @@ __global__ __launch_bounds__(256) void ctasnet_dconv_kernel(const float* __restr
     for (int k = 0; k < CT_R; ++k) {
       const int64_t fk = f + (int64_t)(k - 1) * dil;
       if (fk < 0 || fk >= F) continue;              // wave-uniform
-      const float4 v = *reinterpret_cast<const float4*>(c + (b * F + fk) * CT_H + ch);
+      float4 v = *reinterpret_cast<const float4*>(c + (b * F + fk) * CT_H + ch);
+      if constexpr (TAPE) v = make_float4(prelu(v.x, a1), prelu(v.y, a1), prelu(v.z, a1), prelu(v.w, a1));
       acc.x = fmaf(tap[0][k], (v.x - st.x) * st.y * ga.x + be.x, acc.x);
       acc.y = fmaf(tap[1][k], (v.y - st.x) * st.y * ga.y + be.y, acc.y);
       acc.z = fmaf(tap[2][k], (v.z - st.x) * st.y * ga.z + be.z, acc.z);
       acc.w = fmaf(tap[3][k], (v.w - st.x) * st.y * ga.w + be.w, acc.w);
     }
+    if constexpr (TAPE) *reinterpret_cast<float4*>(w + r * CT_H + ch) = acc;
     acc = make_float4(prelu(acc.x, a2), prelu(acc.y, a2), prelu(acc.z, a2), prelu(acc.w, a2));
-    *reinterpret_cast<float4*>(w + r * CT_H + ch) = acc;
+    if constexpr (!TAPE) *reinterpret_cast<float4*>(w + r * CT_H + ch) = acc;
     const float2 p = wave_partial(acc);
     if (lane == 0) part[r * 2 + half] = p;
   }
@@ -195,8 +201,11 @@ __global__ __launch_bounds__(256) void ctasnet_dconv_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 // A rows normalised on the fly with their mixture's statistics: gamma[k] (a - mean) rstd + beta[k]
 // (GlobalNorm convtasnet.py:25-29 in front of the bottleneck conv; norm_2 in front of conv / conv_sc)
+// PRE: a = PReLU(A row) with *slope first (the tape holds u, not w); slope is not read otherwise
+template <bool PRE>
 struct ALoadNormRows {
   const float* A;
+  const float* slope;
   const float2* stats;
   const float* gamma;
   const float* beta;
@@ -207,7 +216,11 @@ struct ALoadNormRows {
     const int64_t r = (int64_t)tile * CT_BM + row;
     if (r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
     const float2 st = stats[r / F];
-    const float4 v = *reinterpret_cast<const float4*>(A + r * lda + 4 * k4);
+    float4 v = *reinterpret_cast<const float4*>(A + r * lda + 4 * k4);
+    if constexpr (PRE) {
+      const float a = *slope;
+      v = make_float4(prelu(v.x, a), prelu(v.y, a), prelu(v.z, a), prelu(v.w, a));
+    }
     const float4 g = *reinterpret_cast<const float4*>(gamma + 4 * k4), bb = *reinterpret_cast<const float4*>(beta + 4 * k4);
     return make_float4((v.x - st.x) * st.y * g.x + bb.x, (v.y - st.x) * st.y * g.y + bb.y,
                        (v.z - st.x) * st.y * g.z + bb.z, (v.w - st.x) * st.y * g.w + bb.w);
@@ -215,6 +228,8 @@ struct ALoadNormRows {
 };
 
 // (a) c = PReLU_1(v + bias) -> out[row][128 colgroup + 4 c4 ..]; row partials (n = 128) -> part[row][colgroup]
+// TAPE: out gets v1 = v + bias (PReLU_1 is applied by the consumers); the partials are those of PReLU_1(v1) either way
+template <bool TAPE>
 struct EpiPReLUStats {
   static constexpr bool DIRECT = false;
   static constexpr bool HAS_FINISH = false;
@@ -230,13 +245,14 @@ struct EpiPReLUStats {
   DEV float4 prefetch(int, int, int) const { return make_float4(0.f, 0.f, 0.f, 0.f); }
   DEV void row(int tile, int row, int colgroup, int c4, float4 v, float4, const Cols& k) const {
     const int64_t r = (int64_t)tile * CT_BM + row;
-    v = make_float4(prelu(v.x + k.b.x, k.a), prelu(v.y + k.b.y, k.a), prelu(v.z + k.b.z, k.a), prelu(v.w + k.b.w, k.a));
+    const float4 pre = make_float4(v.x + k.b.x, v.y + k.b.y, v.z + k.b.z, v.w + k.b.w);
+    v = make_float4(prelu(pre.x, k.a), prelu(pre.y, k.a), prelu(pre.z, k.a), prelu(pre.w, k.a));
     const float s = group_sum<32>((v.x + v.y) + (v.z + v.w));
     const float mu = s * (1.0f / 128.0f);
     const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
     const float q = group_sum<32>((dx * dx + dy * dy) + (dz * dz + dw * dw));
     if (r >= M) return;
-    *reinterpret_cast<float4*>(out + r * CT_H + colgroup * 128 + 4 * c4) = v;
+    *reinterpret_cast<float4*>(out + r * CT_H + colgroup * 128 + 4 * c4) = TAPE ? pre : v;
     if (c4 == 0) part[r * 4 + colgroup] = make_float2(s, q);
   }
 };
@@ -270,10 +286,13 @@ struct EpiResSkip {
 };
 
 // head (convtasnet.py:76-80): ym[row][j] = sigmoid(v + bias) * enc[row][j mod 512], j = 128 colgroup + 4 c4 ..
+// TAPE: the sigmoid masks go to mk [M][1024] as well (mk is not written otherwise)
+template <bool TAPE>
 struct EpiMask {
   static constexpr bool DIRECT = false;
   static constexpr bool HAS_FINISH = false;
   float* ym;
+  float* mk;
   const float* enc;
   const float* bias;
   int64_t M;
@@ -288,6 +307,7 @@ struct EpiMask {
     const float4 m = make_float4(1.0f / (1.0f + expf(-(v.x + k.b.x))), 1.0f / (1.0f + expf(-(v.y + k.b.y))),
                                  1.0f / (1.0f + expf(-(v.z + k.b.z))), 1.0f / (1.0f + expf(-(v.w + k.b.w))));
     *reinterpret_cast<float4*>(ym + r * (2 * CT_N) + j) = make_float4(e.x * m.x, e.y * m.y, e.z * m.z, e.w * m.w);
+    if constexpr (TAPE) *reinterpret_cast<float4*>(mk + r * (2 * CT_N) + j) = m;
   }
 };
 
@@ -324,6 +344,23 @@ __global__ __launch_bounds__(256) void ctasnet_taps_kernel(const float* __restri
   if (r0 + rr < M) *reinterpret_cast<float4*>(taps + (r0 + rr) * (4 * CT_L) + s * 2 * CT_L + k0) = acc;
 }
 
+// overlap-add and crop: out_s[b][t] = taps[b F + f][s][k] + taps[b F + f - 1][s][k + 16], t + 16 = 16 f + k
+// BIAS: + *bias, the deep decoder's output bias (deepconvtasnet.py:110, :116-118); bias is not read otherwise
+template <bool BIAS>
+__global__ __launch_bounds__(256) void ctasnet_overlap_add_kernel(const float* __restrict__ taps, const float* __restrict__ bias,
+                                                                  int B, int F, int64_t Lout, float* __restrict__ s1,
+                                                                  float* __restrict__ s2) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * (int64_t)B * Lout) return;
+  const int64_t bs = i / Lout, t = i - bs * Lout;
+  const int64_t b = bs >> 1;
+  const int s = (int)(bs & 1);
+  const int64_t j = t + CT_L, f = j / CT_L, k = j - f * CT_L;
+  const float* tp = taps + (b * F + f) * (4 * CT_L) + s * 2 * CT_L;
+  const float v = tp[k] + tp[k + CT_L - 4 * CT_L];   // previous frame's taps k + 16
+  (s ? s2 : s1)[b * Lout + t] = BIAS ? v + *bias : v;
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side: launch helpers for a handle type with fail(code, fmt, ...), device_id and num_cus
 // ------------------------------------------------------------------------------------------------
@@ -347,10 +384,11 @@ int set_lds(Ctx* c, Kern kern, size_t bytes, const char* what) {
 // The engine with its static tile schedule (no ticket queue): workgroup g takes tiles g, g + grid, ...  The grid is what
 // is co-resident (occupancy query once per instantiation and device, at most two workgroups per CU).
 // ldw: row stride of W, or 0 for a copy in the engine's fragment order (gemm_ws.h).
-template <int KIN, class Ctx, class AL, class EP>
+// WT: the engine in its transposed-weight form, out[m][j] = sum_k A[m][k] W[k][j] with W row-major [KIN][ldw].
+template <int KIN, bool WT = false, class Ctx, class AL, class EP>
 int launch_gemm(Ctx* c, hipStream_t st, const char* what, const float* W, const float* Walt, int64_t M, int colgroups,
                 const AL& al, const EP& ep, int ldw = KIN) {
-  auto kern = gemm_ws_kernel<KIN, 1, 1, 4, AL, EP>;
+  auto kern = gemm_ws_kernel<KIN, 1, 1, 4, AL, EP, WT>;
   const size_t lds = GemmShape<KIN, 1, 1, 4>::lds_bytes(EP::DIRECT);
   static std::atomic<int> resident_dev[64];
   int resident = resident_dev[c->device_id & 63].load(std::memory_order_acquire);
@@ -391,51 +429,78 @@ int launch_taps(Ctx* c, hipStream_t st, const float* ym, const float* D, int64_t
   return CTASNET_OK;
 }
 
+template <bool BIAS, class Ctx>
+int launch_overlap_add(Ctx* c, hipStream_t st, const float* taps, const float* bias, int B, int F, int64_t Lout, float* s1,
+                       float* s2) {
+  const int64_t n_out = 2 * (int64_t)B * Lout;
+  hipLaunchKernelGGL(ctasnet_overlap_add_kernel<BIAS>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, taps, bias, B, F,
+                     Lout, s1, s2);
+  CT_LAUNCH_CHECK(c, "ctasnet overlap-add");
+  return CTASNET_OK;
+}
+
 // The Separator (convtasnet.py:55-83) on the encoder output `enc` [M][512], whose row partials (P per row of n_part values
-// each) are in s.part: GlobalNorm statistics, bottleneck 1x1, 24 blocks, masks.  ym [M][1024] = enc * masks is written
-// over c and w (contiguous).  sw: the Separator's CT_SEP_W weights in state_dict order (separator.norm_1.gamma first).
+// each) are in s.part: GlobalNorm statistics, bottleneck 1x1, 24 blocks, masks.
+// sw: the Separator's CT_SEP_W weights in state_dict order (separator.norm_1.gamma first).
+// Without a tape every block reuses the same buffers and ym may lie over c and w (contiguous).  TAPE: block i works on
+// slice i of x, c (v1), w (u), stats1 and stats2, and x_{i+1} = x_i + res is formed in a copy, so x_i stays.
 struct SepBuffers {
-  float* x;        // [M][128]
+  float* x;        // [M][128]; TAPE: CT_BLOCKS + 1 of them
   float* skip;     // [M][128]
-  float* c;        // [M][512], directly followed by w [M][512]
-  float* w;
+  float* c;        // [M][512]; TAPE: CT_BLOCKS of them (v1)
+  float* w;        // [M][512]; TAPE: CT_BLOCKS of them (u)
   float2* part;    // [M][4]
-  float2* stats1;  // [B]
-  float2* stats2;  // [B]
+  float2* stats0;  // [B] GlobalNorm statistics (may be stats1 without a tape)
+  float2* stats1;  // [B]; TAPE: CT_BLOCKS of them
+  float2* stats2;  // [B]; TAPE: CT_BLOCKS of them
+  float* ym;       // [M][1024] = enc * masks
+  float* mk;       // TAPE: [M][1024] sigmoid masks
 };
 
-template <class Ctx>
+template <bool TAPE, class Ctx>
 int launch_separator(Ctx* c, hipStream_t st, const float* const* sw, const float* enc, int P, float n_part, int B, int F,
                      int64_t M, const SepBuffers& s) {
   const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
   // GlobalNorm statistics + bottleneck 1x1 (convtasnet.py:25-29, :67-68)
-  if (int rc = launch_stats(c, st, s.part, B, F, P, n_part, 5e-6f, s.stats1)) return rc;
+  if (int rc = launch_stats(c, st, s.part, B, F, P, n_part, 5e-6f, s.stats0)) return rc;
   if (int rc = launch_gemm<CT_N>(c, st, "ctasnet bottleneck gemm", sw[2], nullptr, M, 1,
-                                 ALoadNormRows{enc, s.stats1, sw[0], sw[1], M, F, CT_N},
+                                 ALoadNormRows<false>{enc, nullptr, s.stats0, sw[0], sw[1], M, F, CT_N},
                                  EpiBiasStore{s.x, sw[3], M, CT_B, CT_BM, 128}))
     return rc;
 
   for (int i = 0; i < CT_BLOCKS; ++i) {       // Conv1D_Block i (convtasnet.py:46-53), dilation 2^(i mod 8)
     const float* const* bw = sw + 4 + i * CT_BLOCK_W;
     const int dil = 1 << (i % CT_X);
+    const size_t slice = TAPE ? (size_t)i : 0;
+    float* xi = s.x + slice * M * CT_B;
+    float* ci = s.c + slice * M * CT_H;
+    float* wi = s.w + slice * M * CT_H;
+    float2* st1 = s.stats1 + slice * B;
+    float2* st2 = s.stats2 + slice * B;
     if (int rc = launch_gemm<CT_B>(c, st, "ctasnet block 1x1 gemm", bw[0], nullptr, M, CT_H / 128,
-                                   ALoadDense{s.x, M, CT_B, CT_BM}, EpiPReLUStats{s.c, s.part, bw[1], bw[2], M}))
+                                   ALoadDense{xi, M, CT_B, CT_BM}, EpiPReLUStats<TAPE>{ci, s.part, bw[1], bw[2], M}))
       return rc;
-    if (int rc = launch_stats(c, st, s.part, B, F, 4, 128.0f, 1e-10f, s.stats1)) return rc;
-    hipLaunchKernelGGL(ctasnet_dconv_kernel, dim3(row_wgs), dim3(256), 0, st, s.c, s.stats1, bw[3], bw[4], bw[5], bw[6], bw[7],
-                       dil, F, M, s.w, s.part);
+    if (int rc = launch_stats(c, st, s.part, B, F, 4, 128.0f, 1e-10f, st1)) return rc;
+    hipLaunchKernelGGL(ctasnet_dconv_kernel<TAPE>, dim3(row_wgs), dim3(256), 0, st, ci, bw[2], st1, bw[3], bw[4], bw[5], bw[6],
+                       bw[7], dil, F, M, wi, s.part);
     CT_LAUNCH_CHECK(c, "ctasnet dconv");
-    if (int rc = launch_stats(c, st, s.part, B, F, 2, 256.0f, 1e-10f, s.stats2)) return rc;
+    if (int rc = launch_stats(c, st, s.part, B, F, 2, 256.0f, 1e-10f, st2)) return rc;
+    float* xn = xi;                           // the residual is added in place ...
+    if constexpr (TAPE) {                     // ... into a copy, so x_i stays on the tape
+      xn = xi + (size_t)M * CT_B;
+      if (hipMemcpyAsync(xn, xi, (size_t)M * CT_B * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return c->fail(CTASNET_ERR_HIP, "ctasnet: residual copy failed");
+    }
     if (int rc = launch_gemm<CT_H>(c, st, "ctasnet block res|skip gemm", bw[10], bw[12], M, 2,
-                                   ALoadNormRows{s.w, s.stats2, bw[8], bw[9], M, F, CT_H},
-                                   EpiResSkip{s.x, s.skip, bw[11], bw[13], M, i == 0}))
+                                   ALoadNormRows<TAPE>{wi, bw[7], st2, bw[8], bw[9], M, F, CT_H},
+                                   EpiResSkip{xn, s.skip, bw[11], bw[13], M, i == 0}))
       return rc;
   }
 
   // masks (convtasnet.py:76-81)
   const float* const* hw = sw + 4 + CT_BLOCKS * CT_BLOCK_W;
   return launch_gemm<CT_B>(c, st, "ctasnet mask gemm", hw[1], nullptr, M, 2 * CT_N / 128,
-                           ALoadDensePReLU{s.skip, hw[0], M, CT_B, CT_BM}, EpiMask{s.c, enc, hw[2], M});
+                           ALoadDensePReLU{s.skip, hw[0], M, CT_B, CT_BM}, EpiMask<TAPE>{s.ym, s.mk, enc, hw[2], M});
 }
 
 }  // namespace

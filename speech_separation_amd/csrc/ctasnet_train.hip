@@ -1,13 +1,11 @@
 // ctasnet_train.hip -- Conv-TasNet training step (src/model/convtasnet.py forward + its autograd backward) for gfx950:
 // handle and the extern "C" boundary declared in include/ctasnet_train.h.
 //
-// Training forward: the launch sequence of ctasnet.hip (ctasnet_kernels.h) with every block writing into its own slice of
-// a tape.  Two pre-activations are kept instead of the post-PReLU tensors the inference path stores (v1 = conv1d(x) + b
-// instead of c = PReLU_1(v1), u = dconv(...) + b instead of w = PReLU_2(u)); the consumers apply the PReLU while they load,
-// with the same float operations, so the predictions are bitwise those of ctasnet_forward and the backward sees the sign
-// of the pre-activation whatever the slope.  Tape per block: x_i [M][128], v1 [M][512], u [M][512], two statistics pairs
-// per mixture; once: enc [M][512], GlobalNorm statistics, the final skip sum [M][128], ym [M][1024] and the sigmoid masks
-// [M][1024].
+// Training forward: the launch sequence of ctasnet.hip in its TAPE mode (ctasnet_kernels.h: one text for both), every
+// block writing into its own slice of a tape; the predictions are bitwise those of ctasnet_forward and the backward sees
+// the sign of each pre-activation whatever the slope.  Tape per block: x_i [M][128], v1 [M][512], u [M][512], two
+// statistics pairs per mixture; once: enc [M][512], GlobalNorm statistics, the final skip sum [M][128], ym [M][1024] and
+// the sigmoid masks [M][1024].
 //
 // Backward (reverse order): decoder taps gradient and d D; mask head (sigmoid, both d enc contributions of the head, d v,
 // seq.1 weight / bias, PReLU seq.0); 24 blocks (res|skip dgrad, norm_2, PReLU_2, depthwise conv, norm_1, PReLU_1, 1x1
@@ -20,186 +18,29 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/ctasnet_train.h"
-#include "common.h"
-// The headers below define non-template kernels that dptnav.hip owns (external linkage); this unit renames its copies so
-// that the two objects do not define the same symbols (same device code, only the names differ).
-#define gemm_pack_rows_kernel cttrain_unused_gemm_pack_rows_kernel
-#define slab_reduce_kernel cttrain_unused_slab_reduce_kernel
-#define slab_reduce_to2_kernel cttrain_unused_slab_reduce_to2_kernel
-#define dropout_mask_kernel cttrain_unused_dropout_mask_kernel
-#define sisnr_pairs_kernel cttrain_unused_sisnr_pairs_kernel
-#define pit_stats_kernel cttrain_unused_pit_stats_kernel
-#define pit_grad_kernel cttrain_unused_pit_grad_kernel
-#define sumsq_partials_kernel cttrain_sumsq_partials_kernel
-#define clip_scale_kernel cttrain_clip_scale_kernel
-#define adamw_kernel cttrain_adamw_kernel
-#include "gemm_ws.h"
 #include "backward.h"
 #include "train_tail.h"
-#undef gemm_pack_rows_kernel
-#undef slab_reduce_kernel
-#undef slab_reduce_to2_kernel
-#undef dropout_mask_kernel
-#undef sisnr_pairs_kernel
-#undef pit_stats_kernel
-#undef pit_grad_kernel
-#undef sumsq_partials_kernel
-#undef clip_scale_kernel
-#undef adamw_kernel
-#include "ctasnet_kernels.h"
+#include "ctasnet_handle.h"
+
+static_assert(CTTRAIN_OK == CTASNET_OK && CTTRAIN_ERR_INVALID == CTASNET_ERR_INVALID &&
+                  CTTRAIN_ERR_WORKSPACE == CTASNET_ERR_WORKSPACE && CTTRAIN_ERR_WEIGHTS == CTASNET_ERR_WEIGHTS &&
+                  CTTRAIN_ERR_HIP == CTASNET_ERR_HIP,
+              "the shared Conv-TasNet code returns CTASNET_* codes");
 
 namespace {
 
-constexpr int CT_NW = 5 + CT_BLOCKS * CT_BLOCK_W + 4;
 constexpr int CTT_G_ROW = 512;   // workgroups of the row kernels (grid-stride): fixed, so partials are summed in a fixed order
 constexpr int CTT_G_W = 128;     // workgroups of a weight-gradient launch (at most)
 constexpr int CTT_G_C = 256;     // workgroups of a column-sum launch
 constexpr int CTT_ROW_SLAB = 6 * CT_H;   // per-workgroup column partials of the dconv backward (3 taps, bias, gamma, beta)
 
 thread_local std::string g_create_error;
-
-// ------------------------------------------------------------------------------------------------
-// training forward: the inference kernels with pre-activations on the tape
-// ------------------------------------------------------------------------------------------------
-// (a) as EpiPReLUStats, but the tape gets v1 = v + bias (PReLU_1 is applied by the consumers); statistics of PReLU_1(v1)
-struct EpiPReLUStatsPre {
-  static constexpr bool DIRECT = false;
-  static constexpr bool HAS_FINISH = false;
-  float* out;
-  float2* part;
-  const float* bias;
-  const float* slope;
-  int64_t M;
-  struct Cols { float4 b; float a; };
-  DEV Cols cols(int colgroup, int c4) const {
-    return Cols{*reinterpret_cast<const float4*>(bias + colgroup * 128 + 4 * c4), *slope};
-  }
-  DEV float4 prefetch(int, int, int) const { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  DEV void row(int tile, int row, int colgroup, int c4, float4 v, float4, const Cols& k) const {
-    const int64_t r = (int64_t)tile * CT_BM + row;
-    const float4 pre = make_float4(v.x + k.b.x, v.y + k.b.y, v.z + k.b.z, v.w + k.b.w);
-    v = make_float4(prelu(pre.x, k.a), prelu(pre.y, k.a), prelu(pre.z, k.a), prelu(pre.w, k.a));
-    const float s = group_sum<32>((v.x + v.y) + (v.z + v.w));
-    const float mu = s * (1.0f / 128.0f);
-    const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
-    const float q = group_sum<32>((dx * dx + dy * dy) + (dz * dz + dw * dw));
-    if (r >= M) return;
-    *reinterpret_cast<float4*>(out + r * CT_H + colgroup * 128 + 4 * c4) = pre;
-    if (c4 == 0) part[r * 4 + colgroup] = make_float2(s, q);
-  }
-};
-
-// (b) as ctasnet_dconv_kernel, reading v1 (PReLU_1 on load) and storing u = the pre-activation of PReLU_2
-__global__ __launch_bounds__(256) void cttrain_dconv_kernel(const float* __restrict__ v1, const float* __restrict__ slope1,
-                                                            const float2* __restrict__ stats, const float* __restrict__ g1,
-                                                            const float* __restrict__ b1, const float* __restrict__ wd,
-                                                            const float* __restrict__ bd, const float* __restrict__ slope2,
-                                                            int dil, int F, int64_t M, float* __restrict__ u,
-                                                            float2* __restrict__ part) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int half = wave & 1, rsub = wave >> 1;
-  const int ch = half * 256 + 4 * lane;
-  const float4 ga = *reinterpret_cast<const float4*>(g1 + ch), be = *reinterpret_cast<const float4*>(b1 + ch);
-  const float4 bias = *reinterpret_cast<const float4*>(bd + ch);
-  float tap[4][CT_R];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int k = 0; k < CT_R; ++k) tap[j][k] = wd[(ch + j) * CT_R + k];
-  const float a1 = *slope1, a2 = *slope2;
-  for (int i = 0; i < CT_ROWS_PER_WG / 2; ++i) {
-    const int64_t r = (int64_t)blockIdx.x * CT_ROWS_PER_WG + 2 * i + rsub;
-    if (r >= M) break;                              // wave-uniform
-    const int64_t b = r / F, f = r - b * F;
-    const float2 st = stats[b];
-    float4 acc = bias;
-#pragma unroll
-    for (int k = 0; k < CT_R; ++k) {
-      const int64_t fk = f + (int64_t)(k - 1) * dil;
-      if (fk < 0 || fk >= F) continue;              // wave-uniform
-      float4 v = *reinterpret_cast<const float4*>(v1 + (b * F + fk) * CT_H + ch);
-      v = make_float4(prelu(v.x, a1), prelu(v.y, a1), prelu(v.z, a1), prelu(v.w, a1));
-      acc.x = fmaf(tap[0][k], (v.x - st.x) * st.y * ga.x + be.x, acc.x);
-      acc.y = fmaf(tap[1][k], (v.y - st.x) * st.y * ga.y + be.y, acc.y);
-      acc.z = fmaf(tap[2][k], (v.z - st.x) * st.y * ga.z + be.z, acc.z);
-      acc.w = fmaf(tap[3][k], (v.w - st.x) * st.y * ga.w + be.w, acc.w);
-    }
-    *reinterpret_cast<float4*>(u + r * CT_H + ch) = acc;
-    acc = make_float4(prelu(acc.x, a2), prelu(acc.y, a2), prelu(acc.z, a2), prelu(acc.w, a2));
-    const float2 p = wave_partial(acc);
-    if (lane == 0) part[r * 2 + half] = p;
-  }
-}
-
-// (c) A rows = norm_2(PReLU_2(u)) on the fly (ALoadNormRows with the PReLU in front)
-struct ALoadPReLUNormRows {
-  const float* A;
-  const float* slope;
-  const float2* stats;
-  const float* gamma;
-  const float* beta;
-  int64_t M;
-  int F;
-  int lda;
-  DEV float4 load4(int tile, int row, int k4) const {
-    const int64_t r = (int64_t)tile * CT_BM + row;
-    if (r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
-    const float2 st = stats[r / F];
-    const float a = *slope;
-    float4 v = *reinterpret_cast<const float4*>(A + r * lda + 4 * k4);
-    v = make_float4(prelu(v.x, a), prelu(v.y, a), prelu(v.z, a), prelu(v.w, a));
-    const float4 g = *reinterpret_cast<const float4*>(gamma + 4 * k4), bb = *reinterpret_cast<const float4*>(beta + 4 * k4);
-    return make_float4((v.x - st.x) * st.y * g.x + bb.x, (v.y - st.x) * st.y * g.y + bb.y,
-                       (v.z - st.x) * st.y * g.z + bb.z, (v.w - st.x) * st.y * g.w + bb.w);
-  }
-};
-
-// head: as EpiMask, and the sigmoid masks go to the tape as well
-struct EpiMaskTrain {
-  static constexpr bool DIRECT = false;
-  static constexpr bool HAS_FINISH = false;
-  float* ym;
-  float* mk;
-  const float* enc;
-  const float* bias;
-  int64_t M;
-  struct Cols { float4 b; };
-  DEV Cols cols(int colgroup, int c4) const { return Cols{*reinterpret_cast<const float4*>(bias + colgroup * 128 + 4 * c4)}; }
-  DEV float4 prefetch(int, int, int) const { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  DEV void row(int tile, int row, int colgroup, int c4, float4 v, float4, const Cols& k) const {
-    const int64_t r = (int64_t)tile * CT_BM + row;
-    if (r >= M) return;
-    const int j = colgroup * 128 + 4 * c4;
-    const float4 e = *reinterpret_cast<const float4*>(enc + r * CT_N + (j & (CT_N - 1)));
-    const float4 m = make_float4(1.0f / (1.0f + expf(-(v.x + k.b.x))), 1.0f / (1.0f + expf(-(v.y + k.b.y))),
-                                 1.0f / (1.0f + expf(-(v.z + k.b.z))), 1.0f / (1.0f + expf(-(v.w + k.b.w))));
-    *reinterpret_cast<float4*>(ym + r * (2 * CT_N) + j) = make_float4(e.x * m.x, e.y * m.y, e.z * m.z, e.w * m.w);
-    *reinterpret_cast<float4*>(mk + r * (2 * CT_N) + j) = m;
-  }
-};
-
-// overlap-add and crop (as ctasnet.hip): out_s[b][t] = taps[b F + f][s][k] + taps[b F + f - 1][s][k + 16], t + 16 = 16 f + k
-__global__ __launch_bounds__(256) void cttrain_overlap_add_kernel(const float* __restrict__ taps, int B, int F, int64_t Lout,
-                                                                  float* __restrict__ s1, float* __restrict__ s2) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * (int64_t)B * Lout) return;
-  const int64_t bs = i / Lout, t = i - bs * Lout;
-  const int64_t b = bs >> 1;
-  const int s = (int)(bs & 1);
-  const int64_t j = t + CT_L, f = j / CT_L, k = j - f * CT_L;
-  const float* tp = taps + (b * F + f) * (4 * CT_L) + s * 2 * CT_L;
-  const float v = tp[k] + tp[k + CT_L - 4 * CT_L];
-  (s ? s2 : s1)[b * Lout + t] = v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // backward kernels
@@ -593,65 +434,17 @@ struct Plan {
 
 }  // namespace
 
-struct cttrain_ctx {
-  std::string err;
-  std::vector<std::string> names;
-  std::vector<int64_t> numels;
-  std::vector<const float*> w;
+struct cttrain_ctx : CtHandle {
   std::vector<float*> g;
-  bool bound = false, gbound = false;
-  int device_id = 0;
-  int num_cus = 256;
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
+  bool gbound = false;
 };
 
 namespace {
 
-void build_names(cttrain_ctx* c) {
-  auto add = [&](const std::string& n, int64_t numel) { c->names.push_back(n); c->numels.push_back(numel); };
-  add("encoder.conv1d.weight", (int64_t)CT_N * 2 * CT_L);
-  add("separator.norm_1.gamma", CT_N);
-  add("separator.norm_1.beta", CT_N);
-  add("separator.conv1d.weight", (int64_t)CT_B * CT_N);
-  add("separator.conv1d.bias", CT_B);
-  for (int i = 0; i < CT_BLOCKS; ++i) {
-    const std::string p = "separator.separator." + std::to_string(i) + ".";
-    add(p + "conv1d.weight", (int64_t)CT_H * CT_B);
-    add(p + "conv1d.bias", CT_H);
-    add(p + "PReLU_1.weight", 1);
-    add(p + "norm_1.weight", CT_H);
-    add(p + "norm_1.bias", CT_H);
-    add(p + "dconv1d.weight", (int64_t)CT_H * CT_R);
-    add(p + "dconv1d.bias", CT_H);
-    add(p + "PReLU_2.weight", 1);
-    add(p + "norm_2.weight", CT_H);
-    add(p + "norm_2.bias", CT_H);
-    add(p + "conv.weight", (int64_t)CT_B * CT_H);
-    add(p + "conv.bias", CT_B);
-    add(p + "conv_sc.weight", (int64_t)CT_B * CT_H);
-    add(p + "conv_sc.bias", CT_B);
-  }
-  add("separator.seq.0.weight", 1);
-  add("separator.seq.1.weight", (int64_t)2 * CT_N * CT_B);
-  add("separator.seq.1.bias", 2 * CT_N);
-  add("decoder.deconv.weight", (int64_t)CT_N * 2 * CT_L);
-}
-
-int64_t frames_of(int64_t T) { return T < CT_L ? 0 : (T + CT_L) / CT_L + 1; }
 size_t align64f(size_t n) { return (n + 63) & ~(size_t)63; }
 
 int make_plan(cttrain_ctx* c, int B, int64_t T, Plan& p) {
-  if (B <= 0) return c->fail(CTTRAIN_ERR_INVALID, "B must be >= 1 (got %d)", B);
-  if (T < CT_L) return c->fail(CTTRAIN_ERR_INVALID, "T must be >= %d samples (got %lld): the output would be empty", CT_L,
-                               (long long)T);
+  if (int rc = check_batch(c, B, T)) return rc;
   p.F = frames_of(T);
   p.M = (int64_t)B * p.F;
   if (p.M * 2 * CT_N > (int64_t)INT32_MAX)
@@ -699,31 +492,6 @@ int ensure_lds(cttrain_ctx* c, PerDeviceOnce& once, Kern kern, size_t bytes, con
   return CTTRAIN_OK;
 }
 
-// the engine in its transposed-weight form: out[m][j] = sum_k A[m][k] W[k][j], W row-major [KIN][ldw]
-template <int KIN, class AL, class EP>
-int launch_gemm_t(cttrain_ctx* c, hipStream_t st, const char* what, const float* W, int ldw, int64_t M, int colgroups,
-                  const AL& al, const EP& ep) {
-  auto kern = gemm_ws_kernel<KIN, 1, 1, 4, AL, EP, true>;
-  const size_t lds = GemmShape<KIN, 1, 1, 4>::lds_bytes(EP::DIRECT);
-  static std::atomic<int> resident_dev[64];
-  int resident = resident_dev[c->device_id & 63].load(std::memory_order_acquire);
-  if (resident == 0) {
-    if (int rc = set_lds(c, kern, lds, what)) return rc;
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds);
-    if (e != hipSuccess || per_cu < 1) return c->fail(CTTRAIN_ERR_HIP, "%s: occupancy query: %s", what, hipGetErrorString(e));
-    resident = std::min(per_cu, 2) * c->num_cus;
-    resident_dev[c->device_id & 63].store(resident, std::memory_order_release);
-  }
-  const int64_t ntiles = (M + CT_BM - 1) / CT_BM;
-  int gx = resident / colgroups;
-  if (gx < 1) gx = 1;
-  if (ntiles < gx) gx = (int)ntiles;
-  hipLaunchKernelGGL(kern, dim3(gx, colgroups), dim3(256), lds, st, W, nullptr, ldw, (int)ntiles, nullptr, al, ep, NoRider{});
-  CT_LAUNCH_CHECK(c, what);
-  return CTTRAIN_OK;
-}
-
 int launch_reduce(cttrain_ctx* c, hipStream_t st, const float* slab, int nslabs, int64_t stride, int rows, int cols, float* out,
                   int ldo) {
   const int64_t n = (int64_t)rows * cols;
@@ -763,25 +531,11 @@ extern "C" {
 int cttrain_abi_version(void) { return CTTRAIN_ABI_VERSION; }
 
 int cttrain_create(cttrain_handle* out) {
-  if (!out) {
-    g_create_error = "out must not be NULL";
-    return CTTRAIN_ERR_INVALID;
-  }
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_create_error = "no HIP device visible: libdptnav's Conv-TasNet training step has no CPU path";
-    return CTTRAIN_ERR_INVALID;
-  }
-  cttrain_ctx* c = new cttrain_ctx();
-  int devid = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&devid) == hipSuccess) c->device_id = devid;
-  if (hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
-  build_names(c);
+  if (int rc = ct_create(out, "Conv-TasNet training step", g_create_error)) return rc;
+  cttrain_ctx* c = *out;
+  add_convtasnet_names(c);
   c->w.assign(c->names.size(), nullptr);
   c->g.assign(c->names.size(), nullptr);
-  *out = c;
   return CTTRAIN_OK;
 }
 
@@ -791,35 +545,17 @@ const char* cttrain_last_error(cttrain_handle h) { return h ? h->err.c_str() : g
 
 int cttrain_num_weights(cttrain_handle h) { return h ? (int)h->names.size() : 0; }
 
-const char* cttrain_weight_name(cttrain_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
-}
+const char* cttrain_weight_name(cttrain_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
 
-int64_t cttrain_weight_numel(cttrain_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1;
-}
+int64_t cttrain_weight_numel(cttrain_handle h, int i) { return h ? h->weight_numel(i) : -1; }
 
 int cttrain_bind_weights(cttrain_handle h, const float* const* dev_ptrs, int n) {
-  if (!h) return CTTRAIN_ERR_INVALID;
-  if (n != CT_NW || !dev_ptrs) return h->fail(CTTRAIN_ERR_WEIGHTS, "expected %d weight pointers, got %d", CT_NW, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(CTTRAIN_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 16)
-      return h->fail(CTTRAIN_ERR_WEIGHTS, "weight %d (%s) is not 16-byte aligned", i, h->names[i].c_str());
-  }
-  h->w.assign(dev_ptrs, dev_ptrs + n);
-  h->bound = true;
-  return CTTRAIN_OK;
+  return h ? bind_weights(h, dev_ptrs, n) : CTTRAIN_ERR_INVALID;
 }
 
 int cttrain_bind_grads(cttrain_handle h, float* const* dev_ptrs, int n) {
   if (!h) return CTTRAIN_ERR_INVALID;
-  if (n != CT_NW || !dev_ptrs) return h->fail(CTTRAIN_ERR_WEIGHTS, "expected %d gradient pointers, got %d", CT_NW, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(CTTRAIN_ERR_WEIGHTS, "gradient %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 4)
-      return h->fail(CTTRAIN_ERR_WEIGHTS, "gradient %d (%s) is not 4-byte aligned", i, h->names[i].c_str());
-  }
+  if (int rc = check_table_ptrs(h, reinterpret_cast<const void* const*>(dev_ptrs), n, "gradient", 4)) return rc;
   h->g.assign(dev_ptrs, dev_ptrs + n);
   h->gbound = true;
   return CTTRAIN_OK;
@@ -836,7 +572,7 @@ int64_t cttrain_flat_numel(cttrain_handle h) { return h ? cttrain_flat_offset(h,
 
 int64_t cttrain_frames(int64_t T) { return frames_of(T); }
 
-int64_t cttrain_out_len(int64_t T) { return T < CT_L ? 0 : CT_L * (T / CT_L); }
+int64_t cttrain_out_len(int64_t T) { return out_len_of(T); }
 
 size_t cttrain_workspace_bytes(cttrain_handle h, int B, int64_t T) {
   if (!h) return 0;
@@ -861,12 +597,6 @@ int64_t cttrain_tape_offset(cttrain_handle h, int B, int64_t T, int which, int b
   return -1;
 }
 
-static int check_ws(cttrain_ctx* c, const Plan& p, void* ws, size_t ws_bytes) {
-  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
-    return c->fail(CTTRAIN_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
-  return CTTRAIN_OK;
-}
-
 int cttrain_train_forward(cttrain_handle h, const float* mix, int B, int64_t T, float* s1_pred, float* s2_pred, void* ws,
                           size_t ws_bytes, void* stream) {
   if (!h) return CTTRAIN_ERR_INVALID;
@@ -875,7 +605,7 @@ int cttrain_train_forward(cttrain_handle h, const float* mix, int B, int64_t T, 
   if (!mix || !s1_pred || !s2_pred) return c->fail(CTTRAIN_ERR_INVALID, "mix / s1_pred / s2_pred must not be NULL");
   Plan p;
   if (int rc = make_plan(c, B, T, p)) return rc;
-  if (int rc = check_ws(c, p, ws, ws_bytes)) return rc;
+  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -883,61 +613,20 @@ int cttrain_train_forward(cttrain_handle h, const float* mix, int B, int64_t T, 
   const int F = (int)p.F;
   const int64_t M = p.M;
   const auto& W = c->w;
-  const float* const* sw = W.data() + 1;             // the Separator's weights
   float* enc = fp(p.off_enc);
   float2* part = f2(p.off_part);
-  float2* stats0 = f2(p.off_stats0);
-  float* skip = fp(p.off_skip);
+  float* ym = fp(p.off_ym);
+  float* taps = fp(p.off_taps);
+  const SepBuffers sb{fp(p.off_x), fp(p.off_skip), fp(p.off_v1), fp(p.off_u), part, f2(p.off_stats0), f2(p.off_st1),
+                      f2(p.off_st2), ym, fp(p.off_mk)};
   const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
 
-  // encoder, GlobalNorm statistics, bottleneck (convtasnet.py:12-15, :25-29, :67-68)
+  // as ctasnet_forward, on the tape: encoder (convtasnet.py:12-15), Separator (:55-83), decoder taps and overlap-add (:92-97)
   hipLaunchKernelGGL(ctasnet_encoder_kernel<false>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], nullptr, enc, part);
   CT_LAUNCH_CHECK(c, "cttrain encoder");
-  if (int rc = launch_stats(c, st, part, B, F, 2, 256.0f, 5e-6f, stats0)) return rc;
-  if (int rc = launch_gemm<CT_N>(c, st, "cttrain bottleneck gemm", sw[2], nullptr, M, 1,
-                                 ALoadNormRows{enc, stats0, sw[0], sw[1], M, F, CT_N},
-                                 EpiBiasStore{fp(p.off_x), sw[3], M, CT_B, CT_BM, 128}))
-    return rc;
-
-  for (int i = 0; i < CT_BLOCKS; ++i) {              // Conv1D_Block i (convtasnet.py:46-53), dilation 2^(i mod 8)
-    const float* const* bw = sw + 4 + i * CT_BLOCK_W;
-    const int dil = 1 << (i % CT_X);
-    float* xi = fp(p.off_x) + (size_t)i * M * CT_B;
-    float* v1 = fp(p.off_v1) + (size_t)i * M * CT_H;
-    float* u = fp(p.off_u) + (size_t)i * M * CT_H;
-    float2* st1 = f2(p.off_st1) + (size_t)i * B;
-    float2* st2 = f2(p.off_st2) + (size_t)i * B;
-    if (int rc = launch_gemm<CT_B>(c, st, "cttrain block 1x1 gemm", bw[0], nullptr, M, CT_H / 128,
-                                   ALoadDense{xi, M, CT_B, CT_BM}, EpiPReLUStatsPre{v1, part, bw[1], bw[2], M}))
-      return rc;
-    if (int rc = launch_stats(c, st, part, B, F, 4, 128.0f, 1e-10f, st1)) return rc;
-    hipLaunchKernelGGL(cttrain_dconv_kernel, dim3(row_wgs), dim3(256), 0, st, v1, bw[2], st1, bw[3], bw[4], bw[5], bw[6], bw[7],
-                       dil, F, M, u, part);
-    CT_LAUNCH_CHECK(c, "cttrain dconv");
-    if (int rc = launch_stats(c, st, part, B, F, 2, 256.0f, 1e-10f, st2)) return rc;
-    // x_{i+1} = x_i + res: the residual is added in place into a copy, so x_i stays on the tape
-    float* xn = xi + (size_t)M * CT_B;
-    if (hipMemcpyAsync(xn, xi, (size_t)M * CT_B * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return c->fail(CTTRAIN_ERR_HIP, "cttrain: residual copy failed");
-    if (int rc = launch_gemm<CT_H>(c, st, "cttrain block res|skip gemm", bw[10], bw[12], M, 2,
-                                   ALoadPReLUNormRows{u, bw[7], st2, bw[8], bw[9], M, F, CT_H},
-                                   EpiResSkip{xn, skip, bw[11], bw[13], M, i == 0}))
-      return rc;
-  }
-
-  // masks (convtasnet.py:76-81), decoder taps and overlap-add (:92-97)
-  const float* const* hw = sw + 4 + CT_BLOCKS * CT_BLOCK_W;
-  float* ym = fp(p.off_ym);
-  if (int rc = launch_gemm<CT_B>(c, st, "cttrain mask gemm", hw[1], nullptr, M, 2 * CT_N / 128,
-                                 ALoadDensePReLU{skip, hw[0], M, CT_B, CT_BM}, EpiMaskTrain{ym, fp(p.off_mk), enc, hw[2], M}))
-    return rc;
-  float* taps = fp(p.off_taps);
+  if (int rc = launch_separator<true>(c, st, W.data() + 1, enc, 2, 256.0f, B, F, M, sb)) return rc;
   if (int rc = launch_taps(c, st, ym, W[1 + CT_SEP_W], M, taps)) return rc;
-  const int64_t n_out = 2 * (int64_t)B * p.Lout;
-  hipLaunchKernelGGL(cttrain_overlap_add_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, taps, B, F, p.Lout,
-                     s1_pred, s2_pred);
-  CT_LAUNCH_CHECK(c, "cttrain overlap-add");
-  return CTTRAIN_OK;
+  return launch_overlap_add<false>(c, st, taps, nullptr, B, F, p.Lout, s1_pred, s2_pred);
 }
 
 int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T, const float* d_s1, const float* d_s2, void* ws,
@@ -949,7 +638,7 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
   if (!mix || !d_s1 || !d_s2) return c->fail(CTTRAIN_ERR_INVALID, "mix / d_s1 / d_s2 must not be NULL");
   Plan p;
   if (int rc = make_plan(c, B, T, p)) return rc;
-  if (int rc = check_ws(c, p, ws, ws_bytes)) return rc;
+  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -1003,8 +692,9 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
       if (int rc = launch_reduce(c, st, slab, ns, 256 * CT_B, 256, CT_B, G[HEAD + 1] + (size_t)256 * q * CT_B, CT_B)) return rc;
     }
     for (int q = 0; q < 2; ++q)
-      if (int rc = launch_gemm_t<CT_N>(c, st, "cttrain head dgrad", W[HEAD + 1] + (size_t)q * CT_N * CT_B, CT_B, M, 1,
-                                       ALoadColsT<false>{dv, M, 2 * CT_N, CT_N * q, CT_BM}, EpiStoreAdd{dskip, M, CT_B, q}))
+      if (int rc = launch_gemm<CT_N, true>(c, st, "cttrain head dgrad", W[HEAD + 1] + (size_t)q * CT_N * CT_B, nullptr, M, 1,
+                                           ALoadColsT<false>{dv, M, 2 * CT_N, CT_N * q, CT_BM}, EpiStoreAdd{dskip, M, CT_B, q},
+                                           CT_B))
         return rc;
     hipLaunchKernelGGL(cttrain_prelu_bwd_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, dskip, skip, W[HEAD], M * CT_B, aslab);
     CT_LAUNCH_CHECK(c, "cttrain head prelu backward");
@@ -1028,8 +718,8 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
     if (hipMemcpyAsync(wrs, bw[10], (size_t)CT_B * CT_H * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipMemcpyAsync(wrs + (size_t)CT_B * CT_H, bw[12], (size_t)CT_B * CT_H * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return c->fail(CTTRAIN_ERR_HIP, "cttrain: weight gather failed");
-    if (int rc = launch_gemm_t<2 * CT_B>(c, st, "cttrain res|skip dgrad", wrs, CT_H, M, CT_H / 128, ALoadCat{dx, dskip, M},
-                                         EpiStoreAdd{bufa, M, CT_H, 0}))
+    if (int rc = launch_gemm<2 * CT_B, true>(c, st, "cttrain res|skip dgrad", wrs, nullptr, M, CT_H / 128,
+                                             ALoadCat{dx, dskip, M}, EpiStoreAdd{bufa, M, CT_H, 0}, CT_H))
       return rc;
     for (int q = 0; q < CT_H / 128; ++q) {
       if (int rc = launch_wgrad<2 * CT_B, 128>(c, st, M, ALoadCat{dx, dskip, M},
@@ -1078,8 +768,8 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
       if (int rc = launch_reduce(c, st, slab, ns, 256 * CT_B, 256, CT_B, bg[0] + (size_t)256 * q * CT_B, CT_B)) return rc;
     }
     if (int rc = launch_colsum<CT_H>(c, st, bufb, M, CT_H, 0, cslab, bg[1])) return rc;
-    if (int rc = launch_gemm_t<CT_H>(c, st, "cttrain block 1x1 dgrad", bw[0], CT_B, M, 1, ALoadDense{bufb, M, CT_H, CT_BM},
-                                     EpiStoreAdd{dx, M, CT_B, 1}))
+    if (int rc = launch_gemm<CT_H, true>(c, st, "cttrain block 1x1 dgrad", bw[0], nullptr, M, 1,
+                                         ALoadDense{bufb, M, CT_H, CT_BM}, EpiStoreAdd{dx, M, CT_B, 1}, CT_B))
       return rc;
   }
 
@@ -1093,8 +783,8 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
       if (int rc = launch_reduce(c, st, slab, ns, CT_B * 128, CT_B, 128, G[SEP + 2] + 128 * q, CT_N)) return rc;
     }
     if (int rc = launch_colsum<CT_B>(c, st, dx, M, CT_B, 0, cslab, G[SEP + 3])) return rc;
-    if (int rc = launch_gemm_t<CT_B>(c, st, "cttrain bottleneck dgrad", W[SEP + 2], CT_N, M, CT_N / 128, ALoadDense{dx, M, CT_B, CT_BM},
-                                     EpiStoreAdd{bufa, M, CT_N, 0}))
+    if (int rc = launch_gemm<CT_B, true>(c, st, "cttrain bottleneck dgrad", W[SEP + 2], nullptr, M, CT_N / 128,
+                                         ALoadDense{dx, M, CT_B, CT_BM}, EpiStoreAdd{bufa, M, CT_N, 0}, CT_N))
       return rc;
     hipLaunchKernelGGL(cttrain_normstat_kernel<false>, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, enc, nullptr, stats0, W[SEP], F, M,
                        part, slab);
@@ -1125,8 +815,8 @@ int cttrain_grad_clip(cttrain_handle h, float* flat_grad, int64_t n_flat, float 
     return h->fail(CTTRAIN_ERR_WORKSPACE, "grad_clip: scratch too small / misaligned");
   hipStream_t st = (hipStream_t)stream;
   double* partials = (double*)scratch;
-  hipLaunchKernelGGL(cttrain_sumsq_partials_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, flat_grad, n_flat / 4, partials);
-  hipLaunchKernelGGL(cttrain_clip_scale_kernel, dim3(h->num_cus * 2), dim3(256), 0, st, flat_grad, n_flat / 4, partials, CLIP_PARTS,
+  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, flat_grad, n_flat / 4, partials);
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(h->num_cus * 2), dim3(256), 0, st, flat_grad, n_flat / 4, partials, CLIP_PARTS,
                      max_norm, norm_out);
   CT_LAUNCH_CHECK(h, "cttrain grad_clip");
   return CTTRAIN_OK;
@@ -1154,7 +844,7 @@ int cttrain_adamw_step(cttrain_handle h, const float* flat_grad, float* exp_avg,
       a.n[e] = (int)h->numels[lo + e];
       off += (int64_t)align64f((size_t)h->numels[lo + e]);
     }
-    hipLaunchKernelGGL(cttrain_adamw_kernel, dim3(cnt, ADAMW_YBLOCKS), dim3(256), 0, (hipStream_t)stream, a, flat_grad, exp_avg,
+    hipLaunchKernelGGL(adamw_kernel, dim3(cnt, ADAMW_YBLOCKS), dim3(256), 0, (hipStream_t)stream, a, flat_grad, exp_avg,
                        exp_avg_sq, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, decay,
                        step_size, inv_sqrt_bc2);
     CT_LAUNCH_CHECK(h, "cttrain adamw_step");
@@ -1165,11 +855,7 @@ int cttrain_adamw_step(cttrain_handle h, const float* flat_grad, float* exp_avg,
 double cttrain_flops_per_mixture(cttrain_handle, int64_t T) {
   // forward MACs (ctasnet_flops_per_mixture) x 3: the backward is one data-gradient and one weight-gradient product per
   // forward product
-  const double F = (double)frames_of(T);
-  const double per_block = (double)CT_B * CT_H + (double)CT_H * CT_R + 2.0 * CT_H * CT_B;
-  const double mac = (double)CT_N * 2 * CT_L + (double)CT_N * CT_B + CT_BLOCKS * per_block + (double)CT_B * 2 * CT_N +
-                     2.0 * CT_N * 2 * CT_L;
-  return 3.0 * 2.0 * mac * F;
+  return 3.0 * 2.0 * convtasnet_macs() * (double)frames_of(T);
 }
 
 }  // extern "C"

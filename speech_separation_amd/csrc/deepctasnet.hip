@@ -17,22 +17,17 @@
 // Conv-TasNet's mask epilogue, decoder taps and overlap-add layout unchanged.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/dctasnet.h"
-#include "common.h"
-// see ctasnet.hip: only dptnav.hip may define the engine's weight-packing kernel
-#define gemm_pack_rows_kernel dctasnet_unused_gemm_pack_rows_kernel
-#include "gemm_ws.h"
-#undef gemm_pack_rows_kernel
-#include "ctasnet_kernels.h"
+#include "ctasnet_handle.h"
+
+static_assert(DCTASNET_OK == CTASNET_OK && DCTASNET_ERR_INVALID == CTASNET_ERR_INVALID &&
+                  DCTASNET_ERR_WORKSPACE == CTASNET_ERR_WORKSPACE && DCTASNET_ERR_WEIGHTS == CTASNET_ERR_WEIGHTS &&
+                  DCTASNET_ERR_HIP == CTASNET_ERR_HIP,
+              "the shared Conv-TasNet code returns CTASNET_* codes");
 
 namespace {
 
@@ -238,20 +233,6 @@ __global__ __launch_bounds__(256) void dctasnet_video_frames_kernel(const float*
   }
 }
 
-// overlap-add and crop with the output bias (deepconvtasnet.py:110, :116-118): as ctasnet_overlap_add_kernel, + bias
-__global__ __launch_bounds__(256) void dctasnet_overlap_add_kernel(const float* __restrict__ taps, const float* __restrict__ bias,
-                                                                   int B, int F, int64_t Lout, float* __restrict__ s1,
-                                                                   float* __restrict__ s2) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= 2 * (int64_t)B * Lout) return;
-  const int64_t bs = i / Lout, t = i - bs * Lout;
-  const int64_t b = bs >> 1;
-  const int s = (int)(bs & 1);
-  const int64_t j = t + CT_L, f = j / CT_L, k = j - f * CT_L;
-  const float* tp = taps + (b * F + f) * (4 * CT_L) + s * 2 * CT_L;
-  (s ? s2 : s1)[b * Lout + t] = (tp[k] + tp[k + CT_L - 4 * CT_L]) + *bias;
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -262,30 +243,14 @@ struct Plan {
 
 }  // namespace
 
-struct dctasnet_ctx {
-  std::string err;
-  std::vector<std::string> names;
-  std::vector<int64_t> numels;
-  std::vector<const float*> w;
+struct dctasnet_ctx : CtHandle {
   bool av = false;
-  bool bound = false;
-  int device_id = 0;
-  int num_cus = 256;
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
 };
 
 namespace {
 
 void build_names(dctasnet_ctx* c) {
-  auto add = [&](const std::string& n, int64_t numel) { c->names.push_back(n); c->numels.push_back(numel); };
+  auto add = [&](const std::string& n, int64_t numel) { c->add(n, numel); };
   const int64_t dense = (int64_t)CT_N * CT_N * 3;
   add("encoder.sequential.0.weight", (int64_t)CT_N * 2 * CT_L);
   add("encoder.sequential.0.bias", CT_N);
@@ -295,30 +260,7 @@ void build_names(dctasnet_ctx* c) {
     add(p + std::to_string(i) + ".bias", CT_N);
     add(p + std::to_string(i + 1) + ".weight", 1);
   }
-  add("separator.norm_1.gamma", CT_N);
-  add("separator.norm_1.beta", CT_N);
-  add("separator.conv1d.weight", (int64_t)CT_B * CT_N);
-  add("separator.conv1d.bias", CT_B);
-  for (int i = 0; i < CT_BLOCKS; ++i) {
-    const std::string p = "separator.separator." + std::to_string(i) + ".";
-    add(p + "conv1d.weight", (int64_t)CT_H * CT_B);
-    add(p + "conv1d.bias", CT_H);
-    add(p + "PReLU_1.weight", 1);
-    add(p + "norm_1.weight", CT_H);
-    add(p + "norm_1.bias", CT_H);
-    add(p + "dconv1d.weight", (int64_t)CT_H * CT_R);
-    add(p + "dconv1d.bias", CT_H);
-    add(p + "PReLU_2.weight", 1);
-    add(p + "norm_2.weight", CT_H);
-    add(p + "norm_2.bias", CT_H);
-    add(p + "conv.weight", (int64_t)CT_B * CT_H);
-    add(p + "conv.bias", CT_B);
-    add(p + "conv_sc.weight", (int64_t)CT_B * CT_H);
-    add(p + "conv_sc.bias", CT_B);
-  }
-  add("separator.seq.0.weight", 1);
-  add("separator.seq.1.weight", (int64_t)2 * CT_N * CT_B);
-  add("separator.seq.1.bias", 2 * CT_N);
+  add_separator_names(c);
   for (int i = 0; i <= 6; i += 2) {
     const std::string p = "decoder.sequential.";
     add(p + std::to_string(i) + ".weight", dense);
@@ -336,12 +278,8 @@ void build_names(dctasnet_ctx* c) {
   }
 }
 
-int64_t frames_of(int64_t T) { return T < CT_L ? 0 : (T + CT_L) / CT_L + 1; }
-
 int make_plan(dctasnet_ctx* c, int B, int64_t T, int Tv, Plan& p) {
-  if (B <= 0) return c->fail(DCTASNET_ERR_INVALID, "B must be >= 1 (got %d)", B);
-  if (T < CT_L) return c->fail(DCTASNET_ERR_INVALID, "T must be >= %d samples (got %lld): the output would be empty", CT_L,
-                               (long long)T);
+  if (int rc = check_batch(c, B, T)) return rc;
   if (c->av && Tv < 1) return c->fail(DCTASNET_ERR_INVALID, "Tv must be >= 1 for the audio-visual model (got %d)", Tv);
   p.F = frames_of(T);
   p.M = (int64_t)B * p.F;
@@ -389,25 +327,11 @@ extern "C" {
 int dctasnet_abi_version(void) { return DCTASNET_ABI_VERSION; }
 
 int dctasnet_create(dctasnet_handle* out, int av) {
-  if (!out) {
-    g_create_error = "out must not be NULL";
-    return DCTASNET_ERR_INVALID;
-  }
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_create_error = "no HIP device visible: libdptnav's deep Conv-TasNet has no CPU path";
-    return DCTASNET_ERR_INVALID;
-  }
-  dctasnet_ctx* c = new dctasnet_ctx();
+  if (int rc = ct_create(out, "deep Conv-TasNet", g_create_error)) return rc;
+  dctasnet_ctx* c = *out;
   c->av = av != 0;
-  int devid = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&devid) == hipSuccess) c->device_id = devid;
-  if (hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
   build_names(c);
   c->w.assign(c->names.size(), nullptr);
-  *out = c;
   return DCTASNET_OK;
 }
 
@@ -417,31 +341,17 @@ const char* dctasnet_last_error(dctasnet_handle h) { return h ? h->err.c_str() :
 
 int dctasnet_num_weights(dctasnet_handle h) { return h ? (int)h->names.size() : 0; }
 
-const char* dctasnet_weight_name(dctasnet_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
-}
+const char* dctasnet_weight_name(dctasnet_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
 
-int64_t dctasnet_weight_numel(dctasnet_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1;
-}
+int64_t dctasnet_weight_numel(dctasnet_handle h, int i) { return h ? h->weight_numel(i) : -1; }
 
 int dctasnet_bind_weights(dctasnet_handle h, const float* const* dev_ptrs, int n) {
-  if (!h) return DCTASNET_ERR_INVALID;
-  const int nw = (int)h->names.size();
-  if (n != nw || !dev_ptrs) return h->fail(DCTASNET_ERR_WEIGHTS, "expected %d weight pointers, got %d", nw, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(DCTASNET_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 16)
-      return h->fail(DCTASNET_ERR_WEIGHTS, "weight %d (%s) is not 16-byte aligned", i, h->names[i].c_str());
-  }
-  h->w.assign(dev_ptrs, dev_ptrs + n);
-  h->bound = true;
-  return DCTASNET_OK;
+  return h ? bind_weights(h, dev_ptrs, n) : DCTASNET_ERR_INVALID;
 }
 
 int64_t dctasnet_frames(int64_t T) { return frames_of(T); }
 
-int64_t dctasnet_out_len(int64_t T) { return T < CT_L ? 0 : CT_L * (T / CT_L); }
+int64_t dctasnet_out_len(int64_t T) { return out_len_of(T); }
 
 size_t dctasnet_workspace_bytes(dctasnet_handle h, int B, int64_t T, int Tv) {
   if (!h) return 0;
@@ -460,8 +370,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
   if (!c->av && (e1 || e2)) return c->fail(DCTASNET_ERR_INVALID, "the audio-only model takes no embeddings (pass NULL)");
   Plan p;
   if (int rc = make_plan(c, B, T, Tv, p)) return rc;
-  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
-    return c->fail(DCTASNET_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
+  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   float* wpk = reinterpret_cast<float*>(base + p.off_wpk);
@@ -472,7 +381,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
   float2* part = reinterpret_cast<float2*>(base + p.off_part);
   float2* stats1 = reinterpret_cast<float2*>(base + p.off_stats);
   const SepBuffers sb{reinterpret_cast<float*>(base + p.off_x), reinterpret_cast<float*>(base + p.off_skip), cbuf,
-                      cbuf + p.M * CT_N, part, stats1, stats1 + B};
+                      cbuf + p.M * CT_N, part, stats1, stats1, stats1 + B, cbuf, nullptr};
   const int F = (int)p.F;
   const int64_t M = p.M;
   const auto& W = c->w;
@@ -513,7 +422,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
   }
 
   // Separator: masks times the (fused) encoder output -> ym [M][1024] in c
-  if (int rc = launch_separator(c, st, W.data() + DC_SEP0, enc, 4, 128.0f, B, F, M, sb)) return rc;
+  if (int rc = launch_separator<false>(c, st, W.data() + DC_SEP0, enc, 4, 128.0f, B, F, M, sb)) return rc;
 
   // deep decoder (deepconvtasnet.py:96-120) on 2M rows (b, f, speaker): 4 x [dense ConvTranspose d, PReLU], d = 8, 4, 2, 1,
   // ping-pong c <-> dec, ending in c; then ConvTranspose1d(512, 1, 32, 16) + bias as taps + overlap-add
@@ -525,19 +434,13 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
       return rc;
   }
   if (int rc = launch_taps(c, st, cbuf, W[DC_DEC0 + 12], M, taps)) return rc;
-  const int64_t n_out = 2 * (int64_t)B * p.Lout;
-  hipLaunchKernelGGL(dctasnet_overlap_add_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, taps,
-                     W[DC_DEC0 + 13], B, F, p.Lout, s1_pred, s2_pred);
-  CT_LAUNCH_CHECK(c, "dctasnet overlap-add");
-  return DCTASNET_OK;
+  return launch_overlap_add<true>(c, st, taps, W[DC_DEC0 + 13], B, F, p.Lout, s1_pred, s2_pred);
 }
 
 double dctasnet_flops_per_mixture(dctasnet_handle, int64_t T) {
   const double F = (double)frames_of(T);
   const double dense = 3.0 * CT_N * CT_N;
-  const double per_block = (double)CT_B * CT_H + (double)CT_H * CT_R + 2.0 * CT_H * CT_B;
-  const double sep = (double)CT_N * CT_B + CT_BLOCKS * per_block + (double)CT_B * 2 * CT_N;
-  const double mac = (double)CT_N * 2 * CT_L + 4.0 * dense + sep + 2.0 * 4.0 * dense + 2.0 * CT_N * 2 * CT_L;
+  const double mac = (double)CT_N * 2 * CT_L + 4.0 * dense + separator_macs() + 2.0 * 4.0 * dense + 2.0 * CT_N * 2 * CT_L;
   return 2.0 * mac * F;
 }
 

@@ -1090,7 +1090,7 @@ struct GemmPackArgs {
   const float* src[GEMM_PACK_MAX];   // nullptr: that slot stays untouched (a path without a reverse direction)
   int rows, K;
 };
-__global__ __launch_bounds__(256) void gemm_pack_rows_kernel(GemmPackArgs a, float* __restrict__ dst) {
+static __global__ __launch_bounds__(256) void gemm_pack_rows_kernel(GemmPackArgs a, float* __restrict__ dst) {
   const float* W = a.src[blockIdx.y];
   if (W == nullptr) return;
   const int km = a.K / 8, n4 = a.rows * a.K / 4;

@@ -22,7 +22,7 @@ DEV double block_sum(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ __launch_bounds__(256) void sisnr_pairs_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+static __global__ __launch_bounds__(256) void sisnr_pairs_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                            const float* __restrict__ s1, const float* __restrict__ s2,
                                                            const float* __restrict__ mix, int64_t T,
                                                            float* __restrict__ out /* [B][6][2] = (metric dB, loss) */) {

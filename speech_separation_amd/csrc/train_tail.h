@@ -17,7 +17,7 @@ constexpr int CLIP_PARTS = 256;      // partial sums of squares (one per workgro
 
 // One workgroup per (item, pair); pairs = (p1,s1) (p1,s2) (p2,s1) (p2,s2).  Two passes over the 2 x T samples (the second
 // one hits L2): the noise energy |p~ - a g~|^2 is summed directly, not as a difference of energies.
-__global__ __launch_bounds__(256) void pit_stats_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+static __global__ __launch_bounds__(256) void pit_stats_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                          const float* __restrict__ s1, const float* __restrict__ s2,
                                                          int64_t T, double* __restrict__ stats) {
   __shared__ double red[4];
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void pit_stats_kernel(const float* __restrict_
 // terms (same fixed-order sum everywhere), then writes its 1024 samples of d loss / d prediction:
 //   loss = w sum_items -20 log10(|a g~|^2 / |e|^2),  w = grad_scale / (2 B)
 //   d / d p = w (-20 / ln 10) (2 g~ / D - 2 e / |e|^2)          (g~ and e are zero-mean: the mean subtraction drops out)
-__global__ __launch_bounds__(256) void pit_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+static __global__ __launch_bounds__(256) void pit_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const float* __restrict__ s1, const float* __restrict__ s2, int B,
                                                         int64_t T, const double* __restrict__ stats, float grad_scale,
                                                         float* __restrict__ d1, float* __restrict__ d2,
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void pit_grad_kernel(const float* __restrict__
 }
 
 // ---- global-norm clip over the flat gradient buffer (padding between slots is zero) --------------------------------
-__global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __restrict__ g, int64_t n4,
+static __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __restrict__ g, int64_t n4,
                                                               double* __restrict__ partials) {
   __shared__ double red[4];
   double acc = 0;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void sumsq_partials_kernel(const float* __rest
 }
 // clip_grad_norm_: coef = max_norm / (norm + 1e-6) clamped to 1, gradients scaled in place (torch multiplies even when
 // coef == 1).  max_norm <= 0: only the norm is reported.
-__global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, int64_t n4, const double* __restrict__ partials,
+static __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, int64_t n4, const double* __restrict__ partials,
                                                           int nparts, float max_norm, float* __restrict__ norm_out) {
   __shared__ double red[4];
   double acc = 0;
@@ -131,7 +131,7 @@ struct AdamwArgs {
   int64_t off[ADAMW_MAX];
   int n[ADAMW_MAX];
 };
-__global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a, const float* __restrict__ grad, float* __restrict__ m,
+static __global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a, const float* __restrict__ grad, float* __restrict__ m,
                                                      float* __restrict__ v, float beta1, float one_minus_beta1, float beta2,
                                                      float one_minus_beta2 /* both 1 - beta in double on the host, as torch */,
                                                      float eps, float decay /* 1 - lr * weight_decay */,

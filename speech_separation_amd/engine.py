@@ -466,35 +466,40 @@ def params_to_device(sd: Mapping[str, "object"], device) -> Dict[str, torch.Tens
     return out
 
 
-class ConvTasNetEngine:
-    """Conv-TasNet forward (include/ctasnet.h): one handle <-> one device <-> the caller's current stream.  Same conventions
-    as DptnEngine: borrowed weights (bind / bound_to), a cached workspace taken through the optional `alloc` hook."""
+class _ConvTasNetEngineBase:
+    """What the Conv-TasNet engines share: one handle of the `<prefix>_*` C ABI <-> one device <-> the caller's current
+    stream.  Same conventions as DptnEngine: borrowed weights (bind / bound_to), a cached workspace taken through the
+    optional `alloc` hook."""
 
-    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
-        from .spec import convtasnet_state_dict_spec
+    def __init__(self, prefix: str, what: str, spec, device, alloc, *create_args):
+        """prefix: "ctasnet" / "dctasnet" / "cttrain"; what: the model's name in the weight-table message; spec: its
+        state_dict spec; create_args: what `<prefix>_create` takes after the handle."""
+        self._prefix = prefix
         self.device = torch.device(device)
         self._alloc_hook = alloc
         if self.device.type != "cuda":
-            raise RuntimeError("ConvTasNetEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
+            raise RuntimeError(f"{type(self).__name__} needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = _DeviceBoundLib(_lib.load(), self.device)
         h = C.c_void_p()
-        rc = self.lib.ctasnet_create(C.byref(h))
+        rc = self._fn("create")(C.byref(h), *create_args)
         if rc != 0:
-            raise RuntimeError(f"ctasnet_create failed ({rc}): {self.lib.ctasnet_last_error(None).decode()}")
+            raise RuntimeError(f"{prefix}_create failed ({rc}): {self._fn('last_error')(None).decode()}")
         self._h = h
         self._ws: Optional[torch.Tensor] = None
         self._bound: Optional[list] = None
-        spec = convtasnet_state_dict_spec()
-        names = [self.lib.ctasnet_weight_name(h, i).decode() for i in range(self.lib.ctasnet_num_weights(h))]
+        names = [self._fn("weight_name")(h, i).decode() for i in range(self._fn("num_weights")(h))]
         if names != [k for k, _ in spec]:
-            raise RuntimeError("libdptnav's Conv-TasNet weight table disagrees with speech_separation_amd.spec")
+            raise RuntimeError(f"libdptnav's {what} weight table disagrees with speech_separation_amd.spec")
         self.slots = spec
+
+    def _fn(self, name: str):
+        return getattr(self.lib, f"{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.ctasnet_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -504,258 +509,7 @@ class ConvTasNetEngine:
             pass
 
     def _raise(self, rc: int, what: str):
-        raise RuntimeError(f"{what} failed ({rc}): {self.lib.ctasnet_last_error(self._h).decode()}")
-
-    _alloc = DptnEngine._alloc
-    _empty = DptnEngine._empty
-
-    def bind(self, params: Mapping[str, torch.Tensor]):
-        """Borrow the parameter storages (no copies): call again if they are re-allocated."""
-        keep, ptrs = [], (C.c_void_p * len(self.slots))()
-        for i, (key, shape) in enumerate(self.slots):
-            if key not in params:
-                raise KeyError(f"missing parameter {key}")
-            t = params[key].detach()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{key}: expected {tuple(shape)}, got {tuple(t.shape)}")
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
-            keep.append(t)
-            ptrs[i] = t.data_ptr()
-        rc = self.lib.ctasnet_bind_weights(self._h, ptrs, len(self.slots))
-        if rc:
-            self._raise(rc, "ctasnet_bind_weights")
-        self._bound = keep
-        self._bound_ptrs = tuple(t.data_ptr() for t in keep)
-
-    def bound_to(self, params: Mapping[str, torch.Tensor]) -> bool:
-        if self._bound is None:
-            return False
-        return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
-
-    def frames(self, T: int) -> int:
-        return int(self.lib.ctasnet_frames(T))
-
-    def out_len(self, T: int) -> int:
-        return int(self.lib.ctasnet_out_len(T))
-
-    def workspace_bytes(self, B: int, T: int) -> int:
-        n = int(self.lib.ctasnet_workspace_bytes(self._h, B, T))
-        if n == 0:
-            raise RuntimeError(f"unsupported shape: {self.lib.ctasnet_last_error(self._h).decode()}")
-        return n
-
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._alloc(need)
-        return self._ws
-
-    def flops_per_mixture(self, T: int) -> float:
-        return float(self.lib.ctasnet_flops_per_mixture(self._h, T))
-
-    def min_bytes_per_mixture(self, T: int) -> float:
-        return float(self.lib.ctasnet_min_bytes_per_mixture(self._h, T))
-
-    def forward(self, mix: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-                ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """mix [B][T] -> (s1_pred, s2_pred), each [B][16 * (T // 16)], enqueued on the current stream."""
-        if mix.dim() != 2:
-            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
-        B, T = mix.shape
-        mix = _check(mix, "mix", (B, T), self.device)
-        if self._bound is None:
-            raise RuntimeError("ConvTasNetEngine.forward: weights not bound (call bind first)")
-        ws = self._workspace(B, T)
-        L = self.out_len(T)
-        if out is None:
-            s1, s2 = self._empty(B, L), self._empty(B, L)
-        else:
-            s1 = _check(out[0], "out[0]", (B, L), self.device)
-            s2 = _check(out[1], "out[1]", (B, L), self.device)
-            if not (out[0].is_contiguous() and out[1].is_contiguous()):
-                raise ValueError("out tensors must be contiguous")
-        rc = self.lib.ctasnet_forward(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      torch.cuda.current_stream(self.device).cuda_stream)
-        if rc:
-            self._raise(rc, "ctasnet_forward")
-        return s1, s2
-
-
-class DeepConvTasNetEngine:
-    """DeepConvTasNet / DeepAVConvTasNet forward (include/dctasnet.h): one handle <-> one device <-> the caller's current
-    stream.  Same conventions as ConvTasNetEngine: borrowed weights (bind / bound_to), a cached workspace taken through the
-    optional `alloc` hook.  The library repacks the dense convs' weights in every forward, so nothing bound goes stale."""
-
-    def __init__(self, device: torch.device | str = "cuda:0", av: bool = False, alloc=None):
-        from .spec import deepconvtasnet_state_dict_spec
-        self.device = torch.device(device)
-        self.av = bool(av)
-        self._alloc_hook = alloc
-        if self.device.type != "cuda":
-            raise RuntimeError("DeepConvTasNetEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.lib = _DeviceBoundLib(_lib.load(), self.device)
-        h = C.c_void_p()
-        rc = self.lib.dctasnet_create(C.byref(h), int(self.av))
-        if rc != 0:
-            raise RuntimeError(f"dctasnet_create failed ({rc}): {self.lib.dctasnet_last_error(None).decode()}")
-        self._h = h
-        self._ws: Optional[torch.Tensor] = None
-        self._bound: Optional[list] = None
-        spec = deepconvtasnet_state_dict_spec(self.av)
-        names = [self.lib.dctasnet_weight_name(h, i).decode() for i in range(self.lib.dctasnet_num_weights(h))]
-        if names != [k for k, _ in spec]:
-            raise RuntimeError("libdptnav's deep Conv-TasNet weight table disagrees with speech_separation_amd.spec")
-        self.slots = spec
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.dctasnet_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _raise(self, rc: int, what: str):
-        raise RuntimeError(f"{what} failed ({rc}): {self.lib.dctasnet_last_error(self._h).decode()}")
-
-    _alloc = DptnEngine._alloc
-    _empty = DptnEngine._empty
-
-    def bind(self, params: Mapping[str, torch.Tensor]):
-        """Borrow the parameter storages (no copies): call again if they are re-allocated."""
-        keep, ptrs = [], (C.c_void_p * len(self.slots))()
-        for i, (key, shape) in enumerate(self.slots):
-            if key not in params:
-                raise KeyError(f"missing parameter {key}")
-            t = params[key].detach()
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{key}: expected {tuple(shape)}, got {tuple(t.shape)}")
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
-            keep.append(t)
-            ptrs[i] = t.data_ptr()
-        rc = self.lib.dctasnet_bind_weights(self._h, ptrs, len(self.slots))
-        if rc:
-            self._raise(rc, "dctasnet_bind_weights")
-        self._bound = keep
-        self._bound_ptrs = tuple(t.data_ptr() for t in keep)
-
-    def bound_to(self, params: Mapping[str, torch.Tensor]) -> bool:
-        if self._bound is None:
-            return False
-        return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
-
-    def frames(self, T: int) -> int:
-        return int(self.lib.dctasnet_frames(T))
-
-    def out_len(self, T: int) -> int:
-        return int(self.lib.dctasnet_out_len(T))
-
-    def workspace_bytes(self, B: int, T: int, Tv: int = 0) -> int:
-        n = int(self.lib.dctasnet_workspace_bytes(self._h, B, T, Tv))
-        if n == 0:
-            raise RuntimeError(f"unsupported shape: {self.lib.dctasnet_last_error(self._h).decode()}")
-        return n
-
-    def _workspace(self, B: int, T: int, Tv: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, T, Tv)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._alloc(need)
-        return self._ws
-
-    def flops_per_mixture(self, T: int) -> float:
-        return float(self.lib.dctasnet_flops_per_mixture(self._h, T))
-
-    def min_bytes_per_mixture(self, T: int) -> float:
-        return float(self.lib.dctasnet_min_bytes_per_mixture(self._h, T))
-
-    def weight_pack_bytes(self) -> int:
-        return int(self.lib.dctasnet_weight_pack_bytes(self._h))
-
-    def forward(self, mix: torch.Tensor, s1_embedding: Optional[torch.Tensor] = None,
-                s2_embedding: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """mix [B][T] (+ s1/s2_embedding [B][512][Tv] for the audio-visual model) -> (s1_pred, s2_pred), each
-        [B][16 * (T // 16)], enqueued on the current stream."""
-        if mix.dim() != 2:
-            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
-        B, T = mix.shape
-        mix = _check(mix, "mix", (B, T), self.device)
-        Tv, e1, e2 = 0, None, None
-        if self.av:
-            if s1_embedding is None or s2_embedding is None:
-                raise ValueError("DeepAVConvTasNet needs s1_embedding and s2_embedding")
-            if s1_embedding.dim() != 3:
-                raise ValueError(f"s1_embedding: expected (B,512,Tv), got {tuple(s1_embedding.shape)}")
-            Tv = int(s1_embedding.shape[-1])
-            e1 = _check(s1_embedding, "s1_embedding", (B, 512, Tv), self.device)
-            e2 = _check(s2_embedding, "s2_embedding", (B, 512, Tv), self.device)
-        if self._bound is None:
-            raise RuntimeError("DeepConvTasNetEngine.forward: weights not bound (call bind first)")
-        ws = self._workspace(B, T, Tv)
-        L = self.out_len(T)
-        s1, s2 = self._empty(B, L), self._empty(B, L)
-        rc = self.lib.dctasnet_forward(self._h, mix.data_ptr(), _ptr(e1), _ptr(e2), B, T, Tv, s1.data_ptr(), s2.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
-        if rc:
-            self._raise(rc, "dctasnet_forward")
-        return s1, s2
-
-
-class ConvTasNetTrainEngine:
-    """Conv-TasNet training step (include/ctasnet_train.h): one handle <-> one device <-> the caller's current stream.
-    Borrowed weights (bind / bound_to) as ConvTasNetEngine; gradient buffers the library writes, all views of ONE flat
-    tensor in the layout of cttrain_flat_offset (bind_grads), and the clip / AdamW step over that layout, so that
-    optim.clip_grad_norm_, optim.FusedAdamW and train.allreduce_gradients take their fused paths.  The workspace holds the
-    tape of the last train_forward; train_backward refuses a tape that a later train_forward has overwritten."""
-
-    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
-        from .spec import convtasnet_state_dict_spec
-        self.device = torch.device(device)
-        self._alloc_hook = alloc
-        if self.device.type != "cuda":
-            raise RuntimeError("ConvTasNetTrainEngine needs a GPU device (PyTorch-ROCm 'cuda:N'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.lib = _DeviceBoundLib(_lib.load(), self.device)
-        h = C.c_void_p()
-        rc = self.lib.cttrain_create(C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"cttrain_create failed ({rc}): {self.lib.cttrain_last_error(None).decode()}")
-        self._h = h
-        self._ws: Optional[torch.Tensor] = None
-        self._bound: Optional[list] = None
-        self._grads: Optional[Dict[str, torch.Tensor]] = None
-        self._grads_flat: Optional[torch.Tensor] = None
-        self._clip_ws: Optional[torch.Tensor] = None
-        self._tape_id = 0
-        spec = convtasnet_state_dict_spec()
-        names = [self.lib.cttrain_weight_name(h, i).decode() for i in range(self.lib.cttrain_num_weights(h))]
-        if names != [k for k, _ in spec]:
-            raise RuntimeError("libdptnav's Conv-TasNet training weight table disagrees with speech_separation_amd.spec")
-        self.slots = spec
-        self._grad_offsets = self.flat_offsets()
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.cttrain_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _raise(self, rc: int, what: str):
-        raise RuntimeError(f"{what} failed ({rc}): {self.lib.cttrain_last_error(self._h).decode()}")
+        raise RuntimeError(f"{what} failed ({rc}): {self._fn('last_error')(self._h).decode()}")
 
     _alloc = DptnEngine._alloc
     _empty = DptnEngine._empty
@@ -776,9 +530,9 @@ class ConvTasNetTrainEngine:
                 raise ValueError(f"{key}: must be contiguous float32 on {self.device}")
             keep.append(t)
             ptrs[i] = t.data_ptr()
-        rc = self.lib.cttrain_bind_weights(self._h, ptrs, len(self.slots))
+        rc = self._fn("bind_weights")(self._h, ptrs, len(self.slots))
         if rc:
-            self._raise(rc, "cttrain_bind_weights")
+            self._raise(rc, f"{self._prefix}_bind_weights")
         self._bound = keep
         self._bound_ptrs = tuple(t.data_ptr() for t in keep)
 
@@ -786,6 +540,128 @@ class ConvTasNetTrainEngine:
         if self._bound is None:
             return False
         return self._bound_ptrs == tuple(params[k].data_ptr() for k, _ in self.slots)
+
+    def frames(self, T: int) -> int:
+        return int(self._fn("frames")(T))
+
+    def out_len(self, T: int) -> int:
+        return int(self._fn("out_len")(T))
+
+    def workspace_bytes(self, B: int, T: int, *more) -> int:
+        n = int(self._fn("workspace_bytes")(self._h, B, T, *more))
+        if n == 0:
+            raise RuntimeError(f"unsupported shape: {self._fn('last_error')(self._h).decode()}")
+        return n
+
+    def _workspace(self, *shape) -> torch.Tensor:
+        need = self.workspace_bytes(*shape)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = self._alloc(need)
+        return self._ws
+
+    def _mix_2d(self, mix: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+        """mix [B][T] checked -> (contiguous mix, B, T)"""
+        if mix.dim() != 2:
+            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
+        B, T = mix.shape
+        return _check(mix, "mix", (B, T), self.device), B, T
+
+    def _need_bound(self, entry: str):
+        if self._bound is None:
+            raise RuntimeError(f"{type(self).__name__}.{entry}: weights not bound (call bind first)")
+
+    def flops_per_mixture(self, T: int) -> float:
+        return float(self._fn("flops_per_mixture")(self._h, T))
+
+    def min_bytes_per_mixture(self, T: int) -> float:
+        """The inference ABIs only: include/ctasnet_train.h has no byte model."""
+        return float(self._fn("min_bytes_per_mixture")(self._h, T))
+
+
+class ConvTasNetEngine(_ConvTasNetEngineBase):
+    """Conv-TasNet forward (include/ctasnet.h)."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import convtasnet_state_dict_spec
+        super().__init__("ctasnet", "Conv-TasNet", convtasnet_state_dict_spec(), device, alloc)
+
+    def forward(self, mix: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mix [B][T] -> (s1_pred, s2_pred), each [B][16 * (T // 16)], enqueued on the current stream."""
+        mix, B, T = self._mix_2d(mix)
+        self._need_bound("forward")
+        ws = self._workspace(B, T)
+        L = self.out_len(T)
+        if out is None:
+            s1, s2 = self._empty(B, L), self._empty(B, L)
+        else:
+            s1 = _check(out[0], "out[0]", (B, L), self.device)
+            s2 = _check(out[1], "out[1]", (B, L), self.device)
+            if not (out[0].is_contiguous() and out[1].is_contiguous()):
+                raise ValueError("out tensors must be contiguous")
+        rc = self.lib.ctasnet_forward(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      self._stream())
+        if rc:
+            self._raise(rc, "ctasnet_forward")
+        return s1, s2
+
+
+class DeepConvTasNetEngine(_ConvTasNetEngineBase):
+    """DeepConvTasNet / DeepAVConvTasNet forward (include/dctasnet.h).  The library repacks the dense convs' weights in
+    every forward, so nothing bound goes stale."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", av: bool = False, alloc=None):
+        from .spec import deepconvtasnet_state_dict_spec
+        self.av = bool(av)
+        super().__init__("dctasnet", "deep Conv-TasNet", deepconvtasnet_state_dict_spec(self.av), device, alloc, int(self.av))
+
+    def workspace_bytes(self, B: int, T: int, Tv: int = 0) -> int:
+        return super().workspace_bytes(B, T, Tv)
+
+    def weight_pack_bytes(self) -> int:
+        return int(self.lib.dctasnet_weight_pack_bytes(self._h))
+
+    def forward(self, mix: torch.Tensor, s1_embedding: Optional[torch.Tensor] = None,
+                s2_embedding: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mix [B][T] (+ s1/s2_embedding [B][512][Tv] for the audio-visual model) -> (s1_pred, s2_pred), each
+        [B][16 * (T // 16)], enqueued on the current stream."""
+        mix, B, T = self._mix_2d(mix)
+        Tv, e1, e2 = 0, None, None
+        if self.av:
+            if s1_embedding is None or s2_embedding is None:
+                raise ValueError("DeepAVConvTasNet needs s1_embedding and s2_embedding")
+            if s1_embedding.dim() != 3:
+                raise ValueError(f"s1_embedding: expected (B,512,Tv), got {tuple(s1_embedding.shape)}")
+            Tv = int(s1_embedding.shape[-1])
+            e1 = _check(s1_embedding, "s1_embedding", (B, 512, Tv), self.device)
+            e2 = _check(s2_embedding, "s2_embedding", (B, 512, Tv), self.device)
+        self._need_bound("forward")
+        ws = self._workspace(B, T, Tv)
+        L = self.out_len(T)
+        s1, s2 = self._empty(B, L), self._empty(B, L)
+        rc = self.lib.dctasnet_forward(self._h, mix.data_ptr(), _ptr(e1), _ptr(e2), B, T, Tv, s1.data_ptr(), s2.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), self._stream())
+        if rc:
+            self._raise(rc, "dctasnet_forward")
+        return s1, s2
+
+
+class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
+    """Conv-TasNet training step (include/ctasnet_train.h).  Borrowed weights as ConvTasNetEngine; gradient buffers the
+    library writes, all views of ONE flat tensor in the layout of cttrain_flat_offset (bind_grads), and the clip / AdamW
+    step over that layout, so that optim.clip_grad_norm_, optim.FusedAdamW and train.allreduce_gradients take their fused
+    paths.  The workspace holds the tape of the last train_forward; train_backward refuses a tape that a later
+    train_forward has overwritten."""
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import convtasnet_state_dict_spec
+        super().__init__("cttrain", "Conv-TasNet training", convtasnet_state_dict_spec(), device, alloc)
+        self._grads: Optional[Dict[str, torch.Tensor]] = None
+        self._grads_flat: Optional[torch.Tensor] = None
+        self._clip_ws: Optional[torch.Tensor] = None
+        self._tape_id = 0
+        self._grad_offsets = self.flat_offsets()
 
     def flat_offsets(self) -> Dict[str, int]:
         """{state_dict key: offset in floats} of the flat gradient / optimizer-state layout (cttrain_flat_offset)."""
@@ -813,36 +689,10 @@ class ConvTasNetTrainEngine:
         self._grads, self._grads_flat = grads, flat
         return grads
 
-    def frames(self, T: int) -> int:
-        return int(self.lib.cttrain_frames(T))
-
-    def out_len(self, T: int) -> int:
-        return int(self.lib.cttrain_out_len(T))
-
-    def workspace_bytes(self, B: int, T: int) -> int:
-        n = int(self.lib.cttrain_workspace_bytes(self._h, B, T))
-        if n == 0:
-            raise RuntimeError(f"unsupported shape: {self.lib.cttrain_last_error(self._h).decode()}")
-        return n
-
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = self._alloc(need)
-        return self._ws
-
-    def flops_per_mixture(self, T: int) -> float:
-        return float(self.lib.cttrain_flops_per_mixture(self._h, T))
-
     def train_forward(self, mix: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, tuple]:
         """mix [B][T] -> (s1_pred, s2_pred, tape); the tape lives in the engine's workspace until the next train_forward."""
-        if mix.dim() != 2:
-            raise ValueError(f"mix: expected (B,T), got {tuple(mix.shape)}")
-        B, T = mix.shape
-        mix = _check(mix, "mix", (B, T), self.device)
-        if self._bound is None:
-            raise RuntimeError("ConvTasNetTrainEngine.train_forward: weights not bound (call bind first)")
+        mix, B, T = self._mix_2d(mix)
+        self._need_bound("train_forward")
         ws = self._workspace(B, T)
         L = self.out_len(T)
         s1, s2 = self._empty(B, L), self._empty(B, L)

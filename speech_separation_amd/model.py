@@ -268,6 +268,45 @@ class DPRNNAVEncDec(_DPTNBase):
         return self._run(mix, s1_embedding, s2_embedding)
 
 
+def _register_spec_parameters(module: nn.Module, spec):
+    """One uninitialised nn.Parameter per (key, shape) of a state_dict spec, in its order, under `_Node` containers named
+    by the key's path (so state_dict() has the spec's keys and order)."""
+    for key, shape in spec:
+        parts = key.split(".")
+        node = module
+        for name in parts[:-1]:
+            if name not in node._modules:
+                node.add_module(name, _Node())
+            node = node._modules[name]
+        node.register_parameter(parts[-1], nn.Parameter(torch.empty(*shape)))
+
+
+def _bound_engine(module: nn.Module, attr: str, make, device: torch.device):
+    """The engine `module` keeps in `attr` for `device` -- made by make(device) at first use and after a device change --
+    bound to the module's parameters as they are now."""
+    if device.type != "cuda":
+        raise RuntimeError(f"{type(module).__name__} computes only on an AMD GPU through libdptnav (got a {device} tensor); "
+                           f"there is no CPU/PyTorch fallback")
+    eng = getattr(module, attr)
+    if eng is None or eng.device != device:
+        eng = make(device)
+        setattr(module, attr, eng)
+    params = dict(module.named_parameters())
+    for k, p in params.items():
+        if p.device != device:
+            raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
+    if not eng.bound_to(params):
+        eng.bind(params)
+    return eng
+
+
+def _str_with_parameter_counts(module: nn.Module) -> str:
+    all_parameters = sum(p.numel() for p in module.parameters())
+    trainable_parameters = sum(p.numel() for p in module.parameters() if p.requires_grad)
+    return (nn.Module.__str__(module) + f"\nAll parameters: {all_parameters}"
+            + f"\nTrainable parameters: {trainable_parameters}")
+
+
 class ConvTasNet(nn.Module):
     """Conv-TasNet (BASELINE configs[0], src/configs/model/convtasnet.yaml) -- same constructor as the reference class of
     that name (src/model/convtasnet.py:101-116): N and L are accepted and ignored, as there.  Inference only: the forward
@@ -277,15 +316,7 @@ class ConvTasNet(nn.Module):
         super().__init__()
         self.N = N
         self.L = L
-        for key, shape in convtasnet_state_dict_spec():
-            parts = key.split(".")
-            node: nn.Module = self
-            for name in parts[:-1]:
-                if name not in node._modules:
-                    node.add_module(name, _Node())
-                node = node._modules[name]
-            p = nn.Parameter(torch.empty(*shape))
-            node.register_parameter(parts[-1], p)
+        _register_spec_parameters(self, convtasnet_state_dict_spec())
         self.reset_parameters()
         self._engine: Optional[ConvTasNetEngine] = None
 
@@ -307,20 +338,7 @@ class ConvTasNet(nn.Module):
                     p.uniform_(-b, b)
 
     def _get_engine(self, device: torch.device) -> ConvTasNetEngine:
-        if device.type != "cuda":
-            raise RuntimeError(f"ConvTasNet computes only on an AMD GPU through libdptnav (got a {device} tensor); there is "
-                               f"no CPU/PyTorch fallback")
-        eng = self._engine
-        if eng is None or eng.device != device:
-            eng = ConvTasNetEngine(device)
-            self._engine = eng
-        params = dict(self.named_parameters())
-        for k, p in params.items():
-            if p.device != device:
-                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
-        if not eng.bound_to(params):
-            eng.bind(params)
-        return eng
+        return _bound_engine(self, "_engine", ConvTasNetEngine, device)
 
     def forward(self, mix, **batch):
         eng = self._get_engine(mix.device)
@@ -329,11 +347,7 @@ class ConvTasNet(nn.Module):
         s1, s2 = eng.forward(mix)
         return {"s1_pred": s1, "s2_pred": s2}
 
-    def __str__(self):
-        all_parameters = sum(p.numel() for p in self.parameters())
-        trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
-        return (super().__str__() + f"\nAll parameters: {all_parameters}"
-                + f"\nTrainable parameters: {trainable_parameters}")
+    __str__ = _str_with_parameter_counts
 
 
 class _ConvTasNetTrainFn(torch.autograd.Function):
@@ -384,40 +398,14 @@ class TrainableConvTasNet(ConvTasNet):
         for p in self.parameters():
             p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
 
-    def _bind(self, eng, device: torch.device):
-        params = dict(self.named_parameters())
-        for k, p in params.items():
-            if p.device != device:
-                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
-        if not eng.bound_to(params):
-            eng.bind(params)
-        return eng
-
-    @staticmethod
-    def _need_gpu(device: torch.device):
-        if device.type != "cuda":
-            raise RuntimeError(f"TrainableConvTasNet computes only on an AMD GPU through libdptnav (got a {device} tensor); "
-                               f"there is no CPU/PyTorch fallback")
-
     def _get_engine(self, device: torch.device) -> ConvTasNetTrainEngine:
-        self._need_gpu(device)
-        eng = self._engine
-        if eng is None or eng.device != device:
-            eng = ConvTasNetTrainEngine(device)
-            self._engine = eng
-        return self._bind(eng, device)
+        return _bound_engine(self, "_engine", ConvTasNetTrainEngine, device)
 
     def _get_infer_engine(self, device: torch.device) -> ConvTasNetEngine:
-        self._need_gpu(device)
-        eng = self._infer_engine
-        if eng is None or eng.device != device:
-            eng = ConvTasNetEngine(device)
-            self._infer_engine = eng
-        return self._bind(eng, device)
+        return _bound_engine(self, "_infer_engine", ConvTasNetEngine, device)
 
     def forward(self, mix, **batch):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self._need_gpu(mix.device)
             s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
             return {"s1_pred": s1, "s2_pred": s2}
         s1, s2 = self._get_infer_engine(mix.device).forward(mix)
@@ -435,14 +423,7 @@ class DeepConvTasNet(nn.Module):
         super().__init__()
         self.N = N
         self.L = L
-        for key, shape in deepconvtasnet_state_dict_spec(self._AV):
-            parts = key.split(".")
-            node: nn.Module = self
-            for name in parts[:-1]:
-                if name not in node._modules:
-                    node.add_module(name, _Node())
-                node = node._modules[name]
-            node.register_parameter(parts[-1], nn.Parameter(torch.empty(*shape)))
+        _register_spec_parameters(self, deepconvtasnet_state_dict_spec(self._AV))
         self.reset_parameters()
         self._engine: Optional[DeepConvTasNetEngine] = None
 
@@ -465,20 +446,7 @@ class DeepConvTasNet(nn.Module):
                     p.uniform_(-b, b)
 
     def _get_engine(self, device: torch.device) -> DeepConvTasNetEngine:
-        if device.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} computes only on an AMD GPU through libdptnav (got a {device} tensor); "
-                               f"there is no CPU/PyTorch fallback")
-        eng = self._engine
-        if eng is None or eng.device != device:
-            eng = DeepConvTasNetEngine(device, av=self._AV)
-            self._engine = eng
-        params = dict(self.named_parameters())
-        for k, p in params.items():
-            if p.device != device:
-                raise RuntimeError(f"parameter {k} is on {p.device} but the input is on {device}: call model.to(device)")
-        if not eng.bound_to(params):
-            eng.bind(params)
-        return eng
+        return _bound_engine(self, "_engine", lambda dev: DeepConvTasNetEngine(dev, av=self._AV), device)
 
     def _run(self, mix, s1_embedding=None, s2_embedding=None):
         eng = self._get_engine(mix.device)
@@ -490,11 +458,7 @@ class DeepConvTasNet(nn.Module):
     def forward(self, mix, **batch):
         return self._run(mix)
 
-    def __str__(self):
-        all_parameters = sum(p.numel() for p in self.parameters())
-        trainable_parameters = sum(p.numel() for p in self.parameters() if p.requires_grad)
-        return (super().__str__() + f"\nAll parameters: {all_parameters}"
-                + f"\nTrainable parameters: {trainable_parameters}")
+    __str__ = _str_with_parameter_counts
 
 
 class DeepAVConvTasNet(DeepConvTasNet):

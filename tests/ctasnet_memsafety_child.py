@@ -47,10 +47,12 @@ def run(dev, alloc, place):
     return res
 
 
-def main(mode):
+def main(mode, label="convtasnet", run=run):
+    """`run(dev, alloc, place) -> {name: array}` under `mode`, then plainly; 0 if every array is finite and bit-identical.
+    tests/deepctasnet_memsafety_child.py and tests/ctasnet_train_memsafety_child.py pass their own label and run."""
     dev = torch.device("cuda:0")
     arena = None
-    say(f"== {mode} convtasnet: run under test")
+    say(f"== {mode} {label}: run under test")
     if mode == "poison":
         got = run(dev, lambda n: torch.full((n,), 0xFF, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
     elif mode in ("guard_end", "guard_start"):
@@ -64,14 +66,14 @@ def main(mode):
         say(f"guard arena: {len(arena.handles)} allocations, {arena.total / 2**20:.1f} MiB")
         arena.close()
     torch.cuda.empty_cache()
-    say(f"== {mode} convtasnet: plain run")
+    say(f"== {mode} {label}: plain run")
     want = run(dev, lambda n: torch.zeros(n, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
     bad = [k for k in want if not (np.all(np.isfinite(got[k])) and np.array_equal(got[k], want[k]))]
     for k in bad:
         say(f"MISMATCH {k}")
     if bad:
         return 1
-    say(f"OK {mode} convtasnet")
+    say(f"OK {mode} {label}")
     return 0
 
 

@@ -20,18 +20,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from oracle.convtasnet_stock import synthetic_convtasnet_weights  # noqa: E402
 from speech_separation_amd.engine import ConvTasNetTrainEngine  # noqa: E402
 from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
+from tests.ctasnet_memsafety_child import main  # noqa: E402  (the mode harness)
 
 SHAPES = [(3, 4001), (1, 400), (2, 17)]
-
-
-def say(msg):
-    print(msg, flush=True)
 
 
 def run(dev, alloc, place):
@@ -54,35 +50,7 @@ def run(dev, alloc, place):
     return res
 
 
-def main(mode):
-    dev = torch.device("cuda:0")
-    arena = None
-    say(f"== {mode} cttrain: run under test")
-    if mode == "poison":
-        got = run(dev, lambda n: torch.full((n,), 0xFF, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
-    elif mode in ("guard_end", "guard_start"):
-        from tests.guardmem import GuardArena
-        arena = GuardArena(0, flush="end" if mode == "guard_end" else "start", fill=0xFF)
-        got = run(dev, lambda n: arena.bytes(n, 256), lambda t: arena.like(t.contiguous()))
-    else:
-        raise SystemExit(f"unknown mode {mode}")
-    torch.cuda.synchronize()
-    if arena is not None:
-        say(f"guard arena: {len(arena.handles)} allocations, {arena.total / 2**20:.1f} MiB")
-        arena.close()
-    torch.cuda.empty_cache()
-    say(f"== {mode} cttrain: plain run")
-    want = run(dev, lambda n: torch.zeros(n, dtype=torch.uint8, device=dev), lambda t: t.to(dev))
-    bad = [k for k in want if not (np.all(np.isfinite(got[k])) and np.array_equal(got[k], want[k]))]
-    for k in bad:
-        say(f"MISMATCH {k}")
-    if bad:
-        return 1
-    say(f"OK {mode} cttrain")
-    return 0
-
-
 if __name__ == "__main__":
-    rc = main(sys.argv[1])
+    rc = main(sys.argv[1], "cttrain", run)
     sys.stdout.flush()
     os._exit(rc)      # no interpreter teardown with guard mappings still referenced by tensors
