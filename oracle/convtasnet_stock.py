@@ -34,12 +34,33 @@ def convtasnet_spec() -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
-def synthetic_convtasnet_weights(seed: int = 0) -> Dict[str, np.ndarray]:
+SLOPE_RANGE = (-0.3, 1.2)
+# distinct slopes: three pinned values in different blocks, on both PReLUs of a block (a ReLU, the identity, a negative one)
+SLOPE_SPECIALS = {"separator.separator.5.PReLU_1.weight": 0.0, "separator.separator.14.PReLU_2.weight": 1.0,
+                  "separator.separator.20.PReLU_2.weight": -0.25}
+
+
+def distinct_slopes(keys: List[str], seed: int) -> Dict[str, np.float32]:
+    """One slope per PReLU key, pairwise different as float32: uniform in SLOPE_RANGE from a generator of its own (the other
+    tensors' draws do not move), SLOPE_SPECIALS pinned.  A real checkpoint has different slopes everywhere; with one common
+    value no test can tell which slope a kernel read."""
+    rng = np.random.default_rng([seed, 0x510E5])
+    vals = rng.uniform(*SLOPE_RANGE, size=len(keys)).astype(np.float32)
+    out = {k: np.float32(SLOPE_SPECIALS.get(k, v)) for k, v in zip(keys, vals)}
+    assert len(set(out.values())) == len(keys), "slopes collide"
+    return out
+
+
+def synthetic_convtasnet_weights(seed: int = 0, slopes: str = "0.25") -> Dict[str, np.ndarray]:
+    """slopes: "0.25" (every PReLU, the fixtures' weights_digest) or "distinct" (distinct_slopes)."""
+    assert slopes in ("0.25", "distinct"), slopes
     rng = np.random.default_rng(seed)
+    prelus = [k for k, _ in convtasnet_spec() if k.endswith(("PReLU_1.weight", "PReLU_2.weight", "seq.0.weight"))]
+    drawn = distinct_slopes(prelus, seed) if slopes == "distinct" else {}
     sd = {}
     for k, shape in convtasnet_spec():
-        if k.endswith(("PReLU_1.weight", "PReLU_2.weight", "seq.0.weight")):
-            w = np.full(shape, 0.25)
+        if k in prelus:
+            w = np.full(shape, drawn.get(k, 0.25))
         elif k.endswith(("gamma", "norm_1.weight", "norm_2.weight")):
             w = 1.0 + 0.1 * rng.standard_normal(shape)
         elif k.endswith(("beta", "norm_1.bias", "norm_2.bias")):

@@ -40,13 +40,11 @@ def test_header_is_plain_c99():
     assert r.returncode == 0, r.stderr
 
 
-def test_restatement_reproduces_reference_gradients():
-    """loss.backward() through the restatement (fp32 and fp64, CPU) against the reference's own: the loss, the norms and
-    the sampled entries, each within the reference's own fp32 / fp64 gap (x4, plus a floor at fp32 resolution)."""
+def _restatement_reproduces_reference_gradients(golden, slopes):
     from tests import convtasnet_train_ref as R
     from tests.sisnr_ref import pit_sisnr_loss
-    z = np.load(GOLDEN)
-    sd = CT.synthetic_convtasnet_weights(int(z["seeds"][0]))
+    z = np.load(golden)
+    sd = CT.synthetic_convtasnet_weights(int(z["seeds"][0]), slopes=slopes)
     from tools.gen_golden import weights_digest
     assert weights_digest(sd) == str(z["digest"])
     keys = [str(k) for k in z["keys"]]
@@ -74,6 +72,34 @@ def test_restatement_reproduces_reference_gradients():
         if dt == torch.float64:
             norms = np.array([float((p[k].grad if p[k].grad is not None else torch.zeros_like(p[k])).norm()) for k in keys])
             np.testing.assert_allclose(norms, z["norm64"], rtol=1e-9, atol=1e-12)
+
+
+def test_restatement_reproduces_reference_gradients():
+    """loss.backward() through the restatement (fp32 and fp64, CPU) against the reference's own: the loss, the norms and
+    the sampled entries, each within the reference's own fp32 / fp64 gap (x4, plus a floor at fp32 resolution)."""
+    _restatement_reproduces_reference_gradients(GOLDEN, "0.25")
+
+
+def test_restatement_reproduces_reference_gradients_distinct_slopes():
+    """The same with 49 distinct PReLU slopes (tests/golden/convtasnet_grad_slopes.npz): the restatement is the yardstick of
+    the GPU gradient checks, and with one common slope nothing shows that it gives each PReLU the reference's slope."""
+    _restatement_reproduces_reference_gradients(GOLDEN.replace("convtasnet_grad", "convtasnet_grad_slopes"), "distinct")
+
+
+def test_restatement_taps_are_its_own_intermediates():
+    """forward(taps=...) returns the outputs it returns without taps, and the taps have the tape's shapes; PReLU of the taps
+    with the state dict's slopes feeds what follows (checked on the last one: the masks' input)."""
+    from tests import convtasnet_train_ref as R
+    sd = {k: torch.from_numpy(v) for k, v in CT.synthetic_convtasnet_weights(0, slopes="distinct").items()}
+    mix = torch.from_numpy(synthetic_inputs(DPTN_AUDIO, B=2, T=401, seed=1)["mix"])
+    taps = {}
+    with torch.no_grad():
+        a, b = R.forward(sd, mix), R.forward(sd, mix, taps=taps)
+    Fr = (401 + 16) // 16 + 1
+    assert torch.equal(a["s1_pred"], b["s1_pred"]) and torch.equal(a["s2_pred"], b["s2_pred"])
+    assert len(taps["v1"]) == len(taps["u"]) == 24
+    assert all(t.shape == (2, 512, Fr) for t in taps["v1"] + taps["u"]) and taps["skip"].shape == (2, 128, Fr)
+    assert all(float(t.abs().max()) > 0 for t in taps["v1"] + taps["u"] + [taps["skip"]])
 
 
 def test_module_surface():

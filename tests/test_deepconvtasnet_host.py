@@ -122,13 +122,11 @@ def test_cpu_tensors_are_refused():
         DeepConvTasNetEngine("cpu")
 
 
-@pytest.mark.parametrize("name,av,ntensors,nparams", CASES)
-def test_restatement_reproduces_the_reference(name, av, ntensors, nparams):
-    """tests/deepconvtasnet_ref.py in fp32 against the reference's own outputs (same weights, same inputs)."""
-    z = np.load(os.path.join(GOLDEN, f"{name}.npz"))
+def _restatement_reproduces_the_reference(fixture, av, slopes):
+    z = np.load(os.path.join(GOLDEN, f"{fixture}.npz"))
     wseed, iseed = (int(v) for v in z["seeds"])
     B, T, Tv = (int(v) for v in z["shape"])
-    sd = DR.synthetic_deepconvtasnet_weights(av, seed=wseed)
+    sd = DR.synthetic_deepconvtasnet_weights(av, seed=wseed, slopes=slopes)
     assert weights_digest(sd) == str(z["digest"])
     inp = synthetic_inputs(DPTN_AV, B=B, T=T, Tv=Tv, seed=iseed)
     emb = (inp["s1_embedding"], inp["s2_embedding"]) if av else (None, None)
@@ -139,6 +137,19 @@ def test_restatement_reproduces_the_reference(name, av, ntensors, nparams):
         assert out32[k].shape == z[k].shape == (B, 16 * (T // 16))
         assert O.agreement_db(out32[k], z[k]) >= 120.0, (k, O.agreement_db(out32[k], z[k]))
         assert O.agreement_db(out64[k], z[k]) >= 90.0, (k, O.agreement_db(out64[k], z[k]))
+
+
+@pytest.mark.parametrize("name,av,ntensors,nparams", CASES)
+def test_restatement_reproduces_the_reference(name, av, ntensors, nparams):
+    """tests/deepconvtasnet_ref.py in fp32 against the reference's own outputs (same weights, same inputs)."""
+    _restatement_reproduces_the_reference(name, av, "0.25")
+
+
+@pytest.mark.parametrize("name,av,ntensors,nparams", CASES)
+def test_restatement_reproduces_the_reference_distinct_slopes(name, av, ntensors, nparams):
+    """The same with 57 distinct PReLU slopes (deep encoder, Separator, deep decoder; tests/golden/*_slopes.npz): shows that the
+    restatement gives each PReLU the slope the reference gives it, which one common slope cannot."""
+    _restatement_reproduces_the_reference(name + "_slopes", av, "distinct")
 
 
 def test_engine_reaches_no_ticket_wait_in_deepctasnet():

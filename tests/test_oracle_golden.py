@@ -139,6 +139,64 @@ def test_convtasnet_stock_composition_matches_reference():
         assert out[k].shape == (2, 4000) and O.agreement_db(out[k].numpy(), z[k]) > 100
 
 
+def test_convtasnet_stock_composition_matches_reference_distinct_slopes():
+    """The same with 49 distinct PReLU slopes (tests/golden/convtasnet_slopes.npz): with one common slope the pin above cannot
+    tell whether the oracle gives each PReLU the slope the reference gives it."""
+    import os
+    import torch
+    from oracle import convtasnet_stock as CT
+    from tests.conftest import GOLDEN
+    from speech_separation_amd.spec import DPTN_AUDIO
+    z = np.load(os.path.join(GOLDEN, "convtasnet_slopes.npz"))
+    sd = CT.synthetic_convtasnet_weights(seed=0, slopes="distinct")
+    assert weights_digest(sd) == str(z["digest"])
+    mix = synthetic_inputs(DPTN_AUDIO, B=2, T=4000, seed=21)["mix"]
+    out = CT.forward({k: torch.from_numpy(v) for k, v in sd.items()}, torch.from_numpy(mix))
+    for k in ("s1_pred", "s2_pred"):
+        assert out[k].shape == (2, 4000) and O.agreement_db(out[k].numpy(), z[k]) > 100
+    # the pin has teeth: PReLU_1 and PReLU_2 swapped inside each block is far away (identical with one common slope)
+    swapped = dict(sd)
+    for i in range(CT.P * CT.X):
+        a, b = f"separator.separator.{i}.PReLU_1.weight", f"separator.separator.{i}.PReLU_2.weight"
+        swapped[a], swapped[b] = sd[b], sd[a]
+    out = CT.forward({k: torch.from_numpy(v) for k, v in swapped.items()}, torch.from_numpy(mix))
+    assert O.agreement_db(out["s1_pred"].numpy(), z["s1_pred"]) < 40
+
+
+def test_distinct_slopes_are_distinct_and_the_default_is_unchanged():
+    """slopes="distinct": pairwise different over all PReLUs of each model, inside SLOPE_RANGE with values below 0 and above
+    1, the three specials in different blocks and on both PReLUs of a block; every other tensor equals the default
+    generator's, and the default (every slope 0.25) still hashes to the digests stored in the fixtures."""
+    import os
+    from oracle import convtasnet_stock as CT
+    from tests import deepconvtasnet_ref as DR
+    from tests.conftest import GOLDEN
+    cases = [("convtasnet", CT.synthetic_convtasnet_weights, (), 49),
+             ("deepconvtasnet", DR.synthetic_deepconvtasnet_weights, (False,), 57),
+             ("deepavconvtasnet", DR.synthetic_deepconvtasnet_weights, (True,), 57)]
+    for name, gen, args, count in cases:
+        plain, sd = gen(*args, 0), gen(*args, 0, slopes="distinct")
+        assert weights_digest(plain) == str(np.load(os.path.join(GOLDEN, f"{name}.npz"))["digest"]), name
+        assert weights_digest(sd) == str(np.load(os.path.join(GOLDEN, f"{name}_slopes.npz"))["digest"]), name
+        assert list(sd) == list(plain)
+        prelus = [k for k in sd if plain[k].shape == (1,) and float(plain[k][0]) == 0.25 and not k.endswith("bias")]
+        assert len(prelus) == count, (name, len(prelus))
+        for k in sd:
+            assert sd[k].dtype == np.float32 and sd[k].shape == plain[k].shape
+            assert (k in prelus) or np.array_equal(sd[k], plain[k]), k
+        vals = [float(sd[k][0]) for k in prelus]
+        assert len(set(vals)) == count, name                                   # pairwise different
+        assert all(CT.SLOPE_RANGE[0] <= v <= CT.SLOPE_RANGE[1] for v in vals)
+        assert sum(v < 0 for v in vals) >= 3 and sum(v > 1 for v in vals) >= 3
+        for k, v in CT.SLOPE_SPECIALS.items():
+            assert float(sd[k][0]) == v, k
+    sp = CT.SLOPE_SPECIALS
+    assert sorted(sp.values()) == [-0.25, 0.0, 1.0]
+    assert len({k.split(".")[2] for k in sp}) == 3 and {k.split(".")[3] for k in sp} == {"PReLU_1", "PReLU_2"}
+    other = CT.synthetic_convtasnet_weights(1, slopes="distinct")            # the slopes follow the seed
+    assert other["separator.seq.0.weight"] != CT.synthetic_convtasnet_weights(0, slopes="distinct")["separator.seq.0.weight"]
+
+
 def reference_gradient_report(z, grads, floor_db=60.0, margin_db=3.0):
     """Compare {state_dict key: gradient array} with a tests/golden/grad_*.npz record of the REFERENCE's loss.backward()
     (tools/gen_golden.py::reference_gradients; truth = the reference run in fp64, small tensors stored whole, big ones as

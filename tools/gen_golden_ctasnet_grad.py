@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/convtasnet_grad.npz by RUNNING the reference's ConvTasNet (src/model/convtasnet.py) and its
-SiSNRWavLoss (src/loss/ss_losses.py) on the CPU in fp32 and in fp64, then loss.backward(), imported through the stub
+"""Generate tests/golden/convtasnet_grad.npz (every PReLU slope 0.25) and convtasnet_grad_slopes.npz (49 distinct slopes) by
+RUNNING the reference's ConvTasNet (src/model/convtasnet.py) and its SiSNRWavLoss (src/loss/ss_losses.py) on the CPU in fp32 and in fp64, then loss.backward(), imported through the stub
 packages of tools/gen_golden.py.  Runs only where the reference is present; the fixture is what the tests read.
 
 Weights and inputs are not stored: both sides regenerate them (oracle.convtasnet_stock.synthetic_convtasnet_weights,
@@ -8,7 +8,7 @@ speech_separation_amd.spec.synthetic_inputs; numpy PCG64, mix = s1 + s2), and a 
 Full gradients would be 20 MB; per tensor the file keeps the fp64 gradient norm and the fp64 and fp32 values at SAMPLES
 seeded indices (every entry of tensors with at most SAMPLES elements), which keeps it near 0.3 MB.
 
-Usage:  python tools/gen_golden_ctasnet_grad.py
+Usage:  python tools/gen_golden_ctasnet_grad.py [name ...]  (both, or only the named fixtures)
 """
 from __future__ import annotations
 
@@ -51,8 +51,15 @@ def main():
     import_reference()
     ConvTasNet = importlib.import_module("src.model.convtasnet").ConvTasNet
     SiSNRWavLoss = importlib.import_module("src.loss.ss_losses").SiSNRWavLoss
+    only = set(sys.argv[1:])
+    for name, slopes in (("convtasnet_grad", "0.25"), ("convtasnet_grad_slopes", "distinct")):
+        if not only or name in only:
+            generate(name, slopes, ConvTasNet, SiSNRWavLoss)
+
+
+def generate(fixture, slopes, ConvTasNet, SiSNRWavLoss):
     spec = convtasnet_state_dict_spec()
-    sd = synthetic_convtasnet_weights(WEIGHT_SEED)
+    sd = synthetic_convtasnet_weights(WEIGHT_SEED, slopes=slopes)
     mix, s1, s2 = batch()
     idx = sample_indices(spec)
     res = {}
@@ -69,7 +76,7 @@ def main():
         res[name] = (float(loss.detach()), g)
     keys = [k for k, _ in spec]
     np.savez_compressed(
-        os.path.join(OUT, "convtasnet_grad.npz"), digest=np.array(weights_digest(sd)),
+        os.path.join(OUT, f"{fixture}.npz"), digest=np.array(weights_digest(sd)),
         seeds=np.array([WEIGHT_SEED, INPUT_SEED, INDEX_SEED]), shape=np.array([B, T]), keys=np.array(keys),
         loss32=np.array(res["32"][0]), loss64=np.array(res["64"][0]),
         norm64=np.array([np.linalg.norm(res["64"][1][k]) for k in keys]),
@@ -77,7 +84,7 @@ def main():
         index=np.concatenate([idx[k] for k in keys]).astype(np.int32),
         value64=np.concatenate([res["64"][1][k][idx[k]] for k in keys]),
         value32=np.concatenate([res["32"][1][k][idx[k]] for k in keys]).astype(np.float32))
-    print("loss fp32", res["32"][0], "fp64", res["64"][0], "keys", len(keys))
+    print(fixture, "loss fp32", res["32"][0], "fp64", res["64"][0], "keys", len(keys))
 
 
 if __name__ == "__main__":
