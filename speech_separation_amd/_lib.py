@@ -142,6 +142,34 @@ CTTRAIN_SYMBOLS = {
     "cttrain_flops_per_mixture": (C.c_double, [_vp, _i64]),
 }
 
+DCTTRAIN_ABI_VERSION = 1
+
+#: name -> (restype, argtypes): every symbol include/dctasnet_train.h declares (deep Conv-TasNet training step, same shared object)
+DCTTRAIN_SYMBOLS = {
+    "dcttrain_abi_version": (_i, []),
+    "dcttrain_create": (_i, [C.POINTER(_vp), _i]),
+    "dcttrain_destroy": (None, [_vp]),
+    "dcttrain_last_error": (C.c_char_p, [_vp]),
+    "dcttrain_num_weights": (_i, [_vp]),
+    "dcttrain_weight_name": (C.c_char_p, [_vp, _i]),
+    "dcttrain_weight_numel": (_i64, [_vp, _i]),
+    "dcttrain_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "dcttrain_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
+    "dcttrain_flat_offset": (_i64, [_vp, _i]),
+    "dcttrain_flat_numel": (_i64, [_vp]),
+    "dcttrain_frames": (_i64, [_i64]),
+    "dcttrain_out_len": (_i64, [_i64]),
+    "dcttrain_workspace_bytes": (_sz, [_vp, _i, _i64]),
+    "dcttrain_train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+    "dcttrain_train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+    "dcttrain_tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
+    "dcttrain_clip_scratch_bytes": (_sz, [_vp]),
+    "dcttrain_grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
+    "dcttrain_adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                                _vp]),
+    "dcttrain_flops_per_mixture": (C.c_double, [_vp, _i64]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -160,7 +188,7 @@ def load() -> C.CDLL:
             f"g.build()'` at the repo root).  speech_separation_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
-                      + list(CTTRAIN_SYMBOLS.items())):
+                      + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -175,5 +203,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"dctasnet ABI {lib.dctasnet_abi_version()} != binding {DCTASNET_ABI_VERSION}: rebuild")
     if lib.cttrain_abi_version() != CTTRAIN_ABI_VERSION:
         raise RuntimeError(f"cttrain ABI {lib.cttrain_abi_version()} != binding {CTTRAIN_ABI_VERSION}: rebuild")
+    if lib.dcttrain_abi_version() != DCTTRAIN_ABI_VERSION:
+        raise RuntimeError(f"dcttrain ABI {lib.dcttrain_abi_version()} != binding {DCTTRAIN_ABI_VERSION}: rebuild")
     _lib = lib
     return lib

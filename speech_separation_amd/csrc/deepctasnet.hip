@@ -22,7 +22,7 @@
 #include <string>
 
 #include "../../include/dctasnet.h"
-#include "ctasnet_handle.h"
+#include "deepctasnet_kernels.h"
 
 static_assert(DCTASNET_OK == CTASNET_OK && DCTASNET_ERR_INVALID == CTASNET_ERR_INVALID &&
                   DCTASNET_ERR_WORKSPACE == CTASNET_ERR_WORKSPACE && DCTASNET_ERR_WEIGHTS == CTASNET_ERR_WEIGHTS &&
@@ -30,121 +30,7 @@ static_assert(DCTASNET_OK == CTASNET_OK && DCTASNET_ERR_INVALID == CTASNET_ERR_I
               "the shared Conv-TasNet code returns CTASNET_* codes");
 
 namespace {
-
-constexpr int DC_ENC_W = 14;                                   // encoder.sequential.{0..8}
-constexpr int DC_DEC_W = 14;                                   // decoder.sequential.{0..8}
-constexpr int DC_NW_AUDIO = DC_ENC_W + CT_SEP_W + DC_DEC_W + 1;   // + decoder.deconv.weight (unused)
-constexpr int DC_NW_AV = DC_NW_AUDIO + 4;                      // + visual_compression.{weight,bias}, video_ln.{weight,bias}
-constexpr int DC_SEP0 = DC_ENC_W, DC_DEC0 = DC_ENC_W + CT_SEP_W, DC_AV0 = DC_NW_AUDIO;
-constexpr int DC_LAYERS = 8;                                   // dense k = 3 convs: 4 encoder + 4 decoder
-constexpr int64_t DC_TAP_FLOATS = (int64_t)CT_N * CT_N;        // one tap of one layer, fragment order
-constexpr int DC_HV = 256;                                     // hidden_video / 2
-constexpr int DC_VT = 8;                                       // video frames per workgroup of the linear kernel
-
 thread_local std::string g_create_error;
-
-// ------------------------------------------------------------------------------------------------
-// weights -> fragment order (gemm_ws.h, ldw == 0): dst[(layer*3 + k)][cb 16][m 64][lane 64][4] = W_k[32 cb + (lane & 31)]
-// [8 m + 4 (lane >> 5) ..+3], W_k[o][i] the tap-k matrix.  Conv1d weight (o, i, k): the 12 floats of (o, i..i+3, 0..2) are
-// contiguous.  ConvTranspose1d weight (i, o, k): W_k[o][i] = weight[i][o][k]; lanes with consecutive o read consecutive
-// 12-byte groups.
-// ------------------------------------------------------------------------------------------------
-struct PackSrc { const float* w[DC_LAYERS]; };
-
-__global__ __launch_bounds__(256) void dctasnet_pack_kernel(PackSrc src, float* __restrict__ dst) {
-  const int layer = blockIdx.y;
-  const int f = blockIdx.x * 256 + threadIdx.x;                // < 512 * 512 / 4
-  const int lane = f & 63, m = (f >> 6) & 63, cb = f >> 12;
-  const int o = 32 * cb + (lane & 31), i0 = 8 * m + 4 * (lane >> 5);
-  const float* W = src.w[layer];
-  float v[4][3];
-  if (layer < DC_LAYERS / 2) {
-    const float4* p = reinterpret_cast<const float4*>(W + (int64_t)o * 3 * CT_N + 3 * i0);
-    const float4 a = p[0], b = p[1], c = p[2];
-    const float t[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[i][k] = t[3 * i + k];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[i][k] = W[((int64_t)(i0 + i) * CT_N + o) * 3 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    *reinterpret_cast<float4*>(dst + (layer * 3 + k) * DC_TAP_FLOATS + 4 * (int64_t)f) =
-        make_float4(v[0][k], v[1][k], v[2][k], v[3][k]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// engine hooks of the dense conv
-// ------------------------------------------------------------------------------------------------
-// row r of a pass reads row r + shift * 2^lg when frame (r >> lg) % F + shift lies in the sequence, else zeros
-struct ALoadTapShift {
-  const float* A;    // rows of 512
-  int M;             // rows (M * 512 < 2^31: dctasnet's plan)
-  int F;             // frames per sequence
-  int lg;            // log2(rows per frame): 0 encoder, 1 decoder (two speakers per frame)
-  int shift;         // tap offset in frames
-  DEV float4 load4(int tile, int row, int k4) const {
-    const int r = tile * CT_BM + row;
-    if (r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
-    const int f = (r >> lg) % F + shift;
-    if (f < 0 || f >= F) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return *reinterpret_cast<const float4*>(A + (int64_t)(r + shift * (1 << lg)) * CT_N + 4 * k4);
-  }
-};
-
-// tap 0: out = v + bias; tap 1: out += v; tap 2: out = PReLU(out + v), then (last encoder conv) + the video row and the
-// row partials (n = 128 per column group) of the result for the GlobalNorm that follows.
-struct EpiTapConv {
-  static constexpr bool DIRECT = false;
-  static constexpr bool HAS_FINISH = false;
-  float* out;          // [M][512]
-  const float* bias;
-  const float* slope;
-  const float* vid;    // [M][512] or null
-  float2* part;        // [M][4] or null
-  int64_t M;
-  int tap;
-  struct Cols { float4 b; float a; };
-  DEV Cols cols(int colgroup, int c4) const {
-    return Cols{*reinterpret_cast<const float4*>(bias + colgroup * 128 + 4 * c4), *slope};
-  }
-  // the partial sum of the earlier taps: independent of the product (blockIdx.y is the engine's column group)
-  DEV float4 prefetch(int tile, int row, int c4) const {
-    const int64_t r = (int64_t)tile * CT_BM + row;
-    if (tap == 0 || r >= M) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return *reinterpret_cast<const float4*>(out + r * CT_N + blockIdx.y * 128 + 4 * c4);
-  }
-  DEV void row(int tile, int row, int colgroup, int c4, float4 v, float4 prev, const Cols& k) const {
-    const int64_t r = (int64_t)tile * CT_BM + row;
-    const int col = colgroup * 128 + 4 * c4;
-    if (tap == 0) {
-      v = make_float4(v.x + k.b.x, v.y + k.b.y, v.z + k.b.z, v.w + k.b.w);
-    } else {
-      v = make_float4(prev.x + v.x, prev.y + v.y, prev.z + v.z, prev.w + v.w);
-    }
-    if (tap == 2) {
-      v = make_float4(prelu(v.x, k.a), prelu(v.y, k.a), prelu(v.z, k.a), prelu(v.w, k.a));
-      if (vid != nullptr && r < M) {
-        const float4 e = *reinterpret_cast<const float4*>(vid + r * CT_N + col);
-        v = make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w);
-      }
-      if (part != nullptr) {       // uniform across the launch: every lane of the 32-lane group takes part
-        const float s = group_sum<32>((v.x + v.y) + (v.z + v.w));
-        const float mu = s * (1.0f / 128.0f);
-        const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
-        const float q = group_sum<32>((dx * dx + dy * dy) + (dz * dz + dw * dw));
-        if (r < M && c4 == 0) part[r * 4 + colgroup] = make_float2(s, q);
-      }
-    }
-    if (r >= M) return;
-    *reinterpret_cast<float4*>(out + r * CT_N + col) = v;
-  }
-};
 
 // ------------------------------------------------------------------------------------------------
 // video head (deepavconvtasnet.py:140-151)
@@ -248,36 +134,6 @@ struct dctasnet_ctx : CtHandle {
 };
 
 namespace {
-
-void build_names(dctasnet_ctx* c) {
-  auto add = [&](const std::string& n, int64_t numel) { c->add(n, numel); };
-  const int64_t dense = (int64_t)CT_N * CT_N * 3;
-  add("encoder.sequential.0.weight", (int64_t)CT_N * 2 * CT_L);
-  add("encoder.sequential.0.bias", CT_N);
-  for (int i = 1; i <= 7; i += 2) {
-    const std::string p = "encoder.sequential.";
-    add(p + std::to_string(i) + ".weight", dense);
-    add(p + std::to_string(i) + ".bias", CT_N);
-    add(p + std::to_string(i + 1) + ".weight", 1);
-  }
-  add_separator_names(c);
-  for (int i = 0; i <= 6; i += 2) {
-    const std::string p = "decoder.sequential.";
-    add(p + std::to_string(i) + ".weight", dense);
-    add(p + std::to_string(i) + ".bias", CT_N);
-    add(p + std::to_string(i + 1) + ".weight", 1);
-  }
-  add("decoder.sequential.8.weight", (int64_t)CT_N * 2 * CT_L);
-  add("decoder.sequential.8.bias", 1);
-  add("decoder.deconv.weight", (int64_t)CT_N * 2 * CT_L);
-  if (c->av) {
-    add("visual_compression.weight", (int64_t)DC_HV * CT_N);
-    add("visual_compression.bias", DC_HV);
-    add("video_ln.weight", CT_N);
-    add("video_ln.bias", CT_N);
-  }
-}
-
 int make_plan(dctasnet_ctx* c, int B, int64_t T, int Tv, Plan& p) {
   if (int rc = check_batch(c, B, T)) return rc;
   if (c->av && Tv < 1) return c->fail(DCTASNET_ERR_INVALID, "Tv must be >= 1 for the audio-visual model (got %d)", Tv);
@@ -306,20 +162,6 @@ int make_plan(dctasnet_ctx* c, int B, int64_t T, int Tv, Plan& p) {
   p.total = o;
   return DCTASNET_OK;
 }
-
-// one dense k = 3 conv: three passes of the engine on the fragment-order taps wpk[3][512 * 512]
-int launch_dense(dctasnet_ctx* c, hipStream_t st, const float* wpk, bool transposed, int dil, const float* x, float* y,
-                 int64_t rows, int F, int lg, const float* bias, const float* slope, const float* vid, float2* part) {
-  for (int k = 0; k < 3; ++k) {
-    const int shift = transposed ? (1 - k) * dil : (k - 1) * dil;
-    if (int rc = launch_gemm<CT_N>(c, st, "dctasnet dense conv", wpk + k * DC_TAP_FLOATS, nullptr, rows, CT_N / 128,
-                                   ALoadTapShift{x, (int)rows, F, lg, shift},
-                                   EpiTapConv{y, bias, slope, k == 2 ? vid : nullptr, k == 2 ? part : nullptr, rows, k}, 0))
-      return rc;
-  }
-  return DCTASNET_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -329,8 +171,7 @@ int dctasnet_abi_version(void) { return DCTASNET_ABI_VERSION; }
 int dctasnet_create(dctasnet_handle* out, int av) {
   if (int rc = ct_create(out, "deep Conv-TasNet", g_create_error)) return rc;
   dctasnet_ctx* c = *out;
-  c->av = av != 0;
-  build_names(c);
+  c->av = av != 0;  add_deepconvtasnet_names(c, c->av);
   c->w.assign(c->names.size(), nullptr);
   return DCTASNET_OK;
 }
@@ -388,6 +229,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
 
   // weights of the eight dense convs -> fragment order, this forward's copy
   PackSrc ps;
+  ps.tmask = 0xF0u;
   for (int l = 0; l < 4; ++l) {
     ps.w[l] = W[2 + 3 * l];                   // encoder.sequential.{1,3,5,7}.weight
     ps.w[4 + l] = W[DC_DEC0 + 3 * l];         // decoder.sequential.{0,2,4,6}.weight
@@ -416,8 +258,8 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
   for (int l = 0; l < 4; ++l) {
     const float* x = (l & 1) ? cbuf : enc;
     float* y = (l & 1) ? enc : cbuf;
-    if (int rc = launch_dense(c, st, wpk + (int64_t)l * 3 * DC_TAP_FLOATS, false, 1 << l, x, y, M, F, 0, W[3 + 3 * l],
-                              W[4 + 3 * l], l == 3 ? vid : nullptr, l == 3 ? part : nullptr))
+    if (int rc = launch_dense<false>(c, st, wpk + (int64_t)l * 3 * DC_TAP_FLOATS, false, 1 << l, x, nullptr, y, nullptr, M, F, 0,
+                                     W[3 + 3 * l], W[4 + 3 * l], l == 3 ? vid : nullptr, l == 3 ? part : nullptr))
       return rc;
   }
 
@@ -429,8 +271,8 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
   for (int l = 0; l < 4; ++l) {
     const float* x = (l & 1) ? dec : cbuf;
     float* y = (l & 1) ? cbuf : dec;
-    if (int rc = launch_dense(c, st, wpk + (int64_t)(4 + l) * 3 * DC_TAP_FLOATS, true, 8 >> l, x, y, 2 * M, F, 1,
-                              W[DC_DEC0 + 1 + 3 * l], W[DC_DEC0 + 2 + 3 * l], nullptr, nullptr))
+    if (int rc = launch_dense<false>(c, st, wpk + (int64_t)(4 + l) * 3 * DC_TAP_FLOATS, true, 8 >> l, x, nullptr, y, nullptr, 2 * M,
+                                     F, 1, W[DC_DEC0 + 1 + 3 * l], W[DC_DEC0 + 2 + 3 * l], nullptr, nullptr))
       return rc;
   }
   if (int rc = launch_taps(c, st, cbuf, W[DC_DEC0 + 12], M, taps)) return rc;
@@ -438,10 +280,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
 }
 
 double dctasnet_flops_per_mixture(dctasnet_handle, int64_t T) {
-  const double F = (double)frames_of(T);
-  const double dense = 3.0 * CT_N * CT_N;
-  const double mac = (double)CT_N * 2 * CT_L + 4.0 * dense + separator_macs() + 2.0 * 4.0 * dense + 2.0 * CT_N * 2 * CT_L;
-  return 2.0 * mac * F;
+  return 2.0 * deepconvtasnet_macs() * (double)frames_of(T);
 }
 
 double dctasnet_min_bytes_per_mixture(dctasnet_handle h, int64_t T) {

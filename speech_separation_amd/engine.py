@@ -472,7 +472,7 @@ class _ConvTasNetEngineBase:
     optional `alloc` hook."""
 
     def __init__(self, prefix: str, what: str, spec, device, alloc, *create_args):
-        """prefix: "ctasnet" / "dctasnet" / "cttrain"; what: the model's name in the weight-table message; spec: its
+        """prefix: "ctasnet" / "dctasnet" / "cttrain" / "dcttrain"; what: the model's name in the weight-table message; spec: its
         state_dict spec; create_args: what `<prefix>_create` takes after the handle."""
         self._prefix = prefix
         self.device = torch.device(device)
@@ -654,9 +654,15 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
     paths.  The workspace holds the tape of the last train_forward; train_backward refuses a tape that a later
     train_forward has overwritten."""
 
+    #: state_dict keys the backward never writes a gradient for (autograd gets None, the fused step skips them)
+    no_grad_keys: frozenset = frozenset()
+
     def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
         from .spec import convtasnet_state_dict_spec
-        super().__init__("cttrain", "Conv-TasNet training", convtasnet_state_dict_spec(), device, alloc)
+        self._init_train("cttrain", "Conv-TasNet training", convtasnet_state_dict_spec(), device, alloc)
+
+    def _init_train(self, prefix, what, spec, device, alloc, *create_args):
+        _ConvTasNetEngineBase.__init__(self, prefix, what, spec, device, alloc, *create_args)
         self._grads: Optional[Dict[str, torch.Tensor]] = None
         self._grads_flat: Optional[torch.Tensor] = None
         self._clip_ws: Optional[torch.Tensor] = None
@@ -665,10 +671,10 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
 
     def flat_offsets(self) -> Dict[str, int]:
         """{state_dict key: offset in floats} of the flat gradient / optimizer-state layout (cttrain_flat_offset)."""
-        return {key: int(self.lib.cttrain_flat_offset(self._h, i)) for i, (key, _) in enumerate(self.slots)}
+        return {key: int(self._fn("flat_offset")(self._h, i)) for i, (key, _) in enumerate(self.slots)}
 
     def flat_numel(self) -> int:
-        return int(self.lib.cttrain_flat_numel(self._h))
+        return int(self._fn("flat_numel")(self._h))
 
     def bind_grads(self) -> Dict[str, torch.Tensor]:
         """Allocate the gradient buffers the backward overwrites, as views of one flat tensor (`_grads_flat`, padding
@@ -683,9 +689,9 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
             g = flat[offs[key]:offs[key] + n].view(*shape)
             grads[key] = g
             ptrs[i] = g.data_ptr()
-        rc = self.lib.cttrain_bind_grads(self._h, ptrs, len(self.slots))
+        rc = self._fn("bind_grads")(self._h, ptrs, len(self.slots))
         if rc:
-            self._raise(rc, "cttrain_bind_grads")
+            self._raise(rc, f"{self._prefix}_bind_grads")
         self._grads, self._grads_flat = grads, flat
         return grads
 
@@ -696,10 +702,10 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
         ws = self._workspace(B, T)
         L = self.out_len(T)
         s1, s2 = self._empty(B, L), self._empty(B, L)
-        rc = self.lib.cttrain_train_forward(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), self._stream())
+        rc = self._fn("train_forward")(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       self._stream())
         if rc:
-            self._raise(rc, "cttrain_train_forward")
+            self._raise(rc, f"{self._prefix}_train_forward")
         self._tape_id += 1
         return s1, s2, (self._tape_id, B, T, ws.data_ptr())
 
@@ -711,43 +717,46 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
         tid, B, T, wsp = tape
         if tid != self._tape_id or self._ws is None or self._ws.data_ptr() != wsp:
             raise RuntimeError("tape_tensor: the tape was overwritten by a later train_forward")
-        off = int(self.lib.cttrain_tape_offset(self._h, B, T, which, block))
+        off = int(self._fn("tape_offset")(self._h, B, T, which, block))
         if off < 0:
-            self._raise(1, "cttrain_tape_offset")
-        M, C = B * self.frames(T), (128 if which == self.TAPE_SKIP else 512)
+            self._raise(1, f"{self._prefix}_tape_offset")
+        M, C = self._tape_shape(B * self.frames(T), which)
         return self._ws[off:off + 4 * M * C].view(torch.float32).view(M, C)
+
+    def _tape_shape(self, M: int, which: int) -> Tuple[int, int]:
+        return M, (128 if which == self.TAPE_SKIP else 512)
 
     def train_backward(self, mix: torch.Tensor, d_s1: torch.Tensor, d_s2: torch.Tensor, tape: tuple):
         """d loss / d predictions -> the bound gradient buffers (overwritten), from the tape of `train_forward`."""
         if self._grads is None:
-            raise RuntimeError("ConvTasNetTrainEngine.train_backward: gradients not bound (call bind_grads first)")
+            raise RuntimeError(f"{type(self).__name__}.train_backward: gradients not bound (call bind_grads first)")
         B, T = mix.shape
         tid, tB, tT, tws = tape
         if tid != self._tape_id or (tB, tT) != (B, T) or self._ws is None or self._ws.data_ptr() != tws:
-            raise RuntimeError("ConvTasNetTrainEngine.train_backward: the tape was overwritten by a later train_forward "
-                               "(one backward per forward, in order)")
+            raise RuntimeError(f"{type(self).__name__}.train_backward: the tape was overwritten by a later train_forward "
+                               f"(one backward per forward, in order)")
         mix = _check(mix, "mix", (B, T), self.device)
         L = self.out_len(T)
         d1 = _check(d_s1, "d_s1", (B, L), self.device)
         d2 = _check(d_s2, "d_s2", (B, L), self.device)
         ws = self._ws
-        rc = self.lib.cttrain_train_backward(self._h, mix.data_ptr(), B, T, d1.data_ptr(), d2.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), self._stream())
+        rc = self._fn("train_backward")(self._h, mix.data_ptr(), B, T, d1.data_ptr(), d2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        self._stream())
         if rc:
-            self._raise(rc, "cttrain_train_backward")
+            self._raise(rc, f"{self._prefix}_train_backward")
 
     def grad_clip(self, flat_grad: torch.Tensor, max_norm: Optional[float]) -> torch.Tensor:
         """Scales `flat_grad` (flat layout) in place like clip_grad_norm_; returns the pre-clip norm as a 0-dim device tensor."""
         flat_grad = _check(flat_grad, "flat_grad", (self.flat_numel(),), self.device)
-        need = int(self.lib.cttrain_clip_scratch_bytes(self._h))
+        need = int(self._fn("clip_scratch_bytes")(self._h))
         if self._clip_ws is None:
             self._clip_ws = self._alloc(need)
         norm = self._empty(1)
-        rc = self.lib.cttrain_grad_clip(self._h, flat_grad.data_ptr(), flat_grad.numel(),
-                                        float(max_norm) if max_norm is not None else 0.0, self._clip_ws.data_ptr(), need,
-                                        norm.data_ptr(), self._stream())
+        rc = self._fn("grad_clip")(self._h, flat_grad.data_ptr(), flat_grad.numel(),
+                                   float(max_norm) if max_norm is not None else 0.0, self._clip_ws.data_ptr(), need,
+                                   norm.data_ptr(), self._stream())
         if rc:
-            self._raise(rc, "cttrain_grad_clip")
+            self._raise(rc, f"{self._prefix}_grad_clip")
         return norm[0]
 
     def adamw_step(self, flat_grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step: int):
@@ -756,7 +765,27 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
             _check(t, name, (n,), self.device)
         if self._bound is None:
             raise RuntimeError("adamw_step: weights not bound")
-        rc = self.lib.cttrain_adamw_step(self._h, flat_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, float(lr),
-                                         float(beta1), float(beta2), float(eps), float(weight_decay), int(step), self._stream())
+        rc = self._fn("adamw_step")(self._h, flat_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, float(lr),
+                                    float(beta1), float(beta2), float(eps), float(weight_decay), int(step), self._stream())
         if rc:
-            self._raise(rc, "cttrain_adamw_step")
+            self._raise(rc, f"{self._prefix}_adamw_step")
+
+
+class DeepConvTasNetTrainEngine(ConvTasNetTrainEngine):
+    """DeepConvTasNet training step (include/dctasnet_train.h): ConvTasNetTrainEngine on the `dcttrain_*` entry points with the
+    deep model's weight table.  decoder.deconv.weight is a parameter the reference's forward never reads: its gradient
+    buffer stays zero (it does not enter the clip norm), autograd gets None for it and the AdamW step skips it.  Extra tape
+    kinds: TAPE_ENC_Z / TAPE_DEC_Z, the pre-activations of dense encoder / decoder layer `block` (0..3), [B*F][512] /
+    [2*B*F][512] with rows in (b, f, speaker) order."""
+
+    no_grad_keys = frozenset({"decoder.deconv.weight"})
+    TAPE_ENC_Z, TAPE_DEC_Z = 3, 4
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import deepconvtasnet_state_dict_spec
+        self._init_train("dcttrain", "deep Conv-TasNet training", deepconvtasnet_state_dict_spec(False), device, alloc, 0)
+
+    def _tape_shape(self, M: int, which: int) -> Tuple[int, int]:
+        if which == self.TAPE_DEC_Z:
+            return 2 * M, 512
+        return super()._tape_shape(M, which)

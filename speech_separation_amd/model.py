@@ -9,6 +9,7 @@ Mirrors (does not import) the reference interface for this path:
   * ``TrainableConvTasNet(N, L)`` (ConvTasNet with the training step) src/model/convtasnet.py:101-116
   * ``DeepConvTasNet(N, L)``, ``DeepAVConvTasNet(N, L, video_emb_size, hidden_video)`` (inference only)
                                                                     src/model/deepconvtasnet.py:122-136, deepavconvtasnet.py:122-156
+  * ``TrainableDeepConvTasNet(N, L)`` (DeepConvTasNet with the training step) src/model/deepconvtasnet.py:122-136
   * ``forward(mix, s1_embedding, s2_embedding, **batch) -> {"s1_pred","s2_pred"}``  dptn_wav.py:171,194
     -- called as ``self.model(**batch)`` by src/trainer/trainer.py:40 and inferencer.py:117, so unknown
     batch keys (mix_spectrogram, s1, s2, paths, ...) must be accepted and ignored.
@@ -31,7 +32,8 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .engine import ConvTasNetEngine, ConvTasNetTrainEngine, DeepConvTasNetEngine, DptnEngine
+from .engine import (ConvTasNetEngine, ConvTasNetTrainEngine, DeepConvTasNetEngine, DeepConvTasNetTrainEngine,
+                     DptnEngine)
 from .spec import DPTNConfig, convtasnet_state_dict_spec, deepconvtasnet_state_dict_spec, state_dict_spec
 
 
@@ -351,9 +353,10 @@ class ConvTasNet(nn.Module):
 
 
 class _ConvTasNetTrainFn(torch.autograd.Function):
-    """TrainableConvTasNet's model part of the training step, as _SeparateFn: forward records the tape
-    (cttrain_train_forward), backward turns d loss / d predictions into every parameter's gradient
-    (cttrain_train_backward) and hands autograd views of one flat copy."""
+    """The model part of TrainableConvTasNet's / TrainableDeepConvTasNet's training step, as _SeparateFn: forward records
+    the tape (<prefix>_train_forward), backward turns d loss / d predictions into every parameter's gradient
+    (<prefix>_train_backward) and hands autograd views of one flat copy -- None for a parameter the forward never reads
+    (the engine's no_grad_keys), as autograd itself leaves it."""
 
     @staticmethod
     def forward(ctx, module, mix, *params):
@@ -379,7 +382,7 @@ class _ConvTasNetTrainFn(torch.autograd.Function):
         outs = []
         for k, shape in eng.slots:
             o = eng._grad_offsets[k]
-            outs.append(flat[o:o + eng._grads[k].numel()].view(*shape))
+            outs.append(None if k in eng.no_grad_keys else flat[o:o + eng._grads[k].numel()].view(*shape))
         return (None, None) + tuple(outs)
 
 
@@ -415,7 +418,7 @@ class TrainableConvTasNet(ConvTasNet):
 class DeepConvTasNet(nn.Module):
     """Deep encoder / decoder Conv-TasNet (src/configs/model/deepconvtasnet.yaml) -- same constructor as the reference class
     of that name (src/model/deepconvtasnet.py:122-136): N and L are accepted and ignored, as there.  Inference only: the
-    forward runs on libdptnav (include/dctasnet.h); the training step is not built."""
+    forward runs on libdptnav (include/dctasnet.h); TrainableDeepConvTasNet adds the training step."""
 
     _AV = False
 
@@ -461,10 +464,40 @@ class DeepConvTasNet(nn.Module):
     __str__ = _str_with_parameter_counts
 
 
+class TrainableDeepConvTasNet(DeepConvTasNet):
+    """DeepConvTasNet with the training step on libdptnav (include/dctasnet_train.h), the counterpart of
+    TrainableConvTasNet: same constructor, state_dict keys and order, initialisation and parameter-count lines as
+    DeepConvTasNet, and checkpoints load strictly either way.  Under torch.no_grad() the forward is DeepConvTasNet's
+    inference engine (bitwise the same outputs); with grad enabled it records a tape and its backward computes every
+    parameter's gradient in HIP.  decoder.deconv.weight is a parameter the reference's forward never reads: its .grad stays
+    None, as after the reference's loss.backward(), and the fused clip / AdamW leave it out (torch.optim.AdamW skips it too)."""
+
+    def __init__(self, N=512, L=16):
+        super().__init__(N, L)
+        self._engine: Optional[DeepConvTasNetTrainEngine] = None
+        self._infer_engine: Optional[DeepConvTasNetEngine] = None
+        self._flat_grad: Optional[torch.Tensor] = None
+        for p in self.parameters():
+            p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
+
+    def _get_engine(self, device: torch.device) -> DeepConvTasNetTrainEngine:
+        return _bound_engine(self, "_engine", DeepConvTasNetTrainEngine, device)
+
+    def _get_infer_engine(self, device: torch.device) -> DeepConvTasNetEngine:
+        return _bound_engine(self, "_infer_engine", lambda dev: DeepConvTasNetEngine(dev, av=False), device)
+
+    def forward(self, mix, **batch):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
+            return {"s1_pred": s1, "s2_pred": s2}
+        s1, s2 = self._get_infer_engine(mix.device).forward(mix)
+        return {"s1_pred": s1, "s2_pred": s2}
+
+
 class DeepAVConvTasNet(DeepConvTasNet):
     """Audio-visual deep Conv-TasNet (src/configs/model/deepavconvtasnet.yaml) -- same constructor as the reference class
     (src/model/deepavconvtasnet.py:122-134); N and L are ignored as there.  Only the built sizes video_emb_size = hidden_video
-    = 512 exist.  Inference only (include/dctasnet.h)."""
+    = 512 exist.  Inference only (include/dctasnet.h): the audio-visual training step is not built."""
 
     _AV = True
 

@@ -43,7 +43,10 @@ def _flat_grad_problem(model: "nn.Module") -> Optional[str]:
         return "no gradient yet: run loss.backward() through the model first"
     eng = model._engine
     base, offs = flat.data_ptr(), eng._grad_offsets
+    unused = getattr(eng, "no_grad_keys", ())    # parameters the forward never reads: .grad None, skipped by the step
     for key, p in model.named_parameters():
+        if key in unused and p.grad is None:
+            continue
         if not p.requires_grad:
             return (f"{key} is frozen (requires_grad=False): the fused clip / optimizer step covers ALL parameters of the "
                     f"model; use torch.nn.utils.clip_grad_norm_ and torch.optim.AdamW on the trainable subset")
@@ -112,7 +115,10 @@ class FusedAdamW(torch.optim.Optimizer):
             self._m.copy_(old[0])
             self._v.copy_(old[1])
         offs = eng.flat_offsets()
+        unused = getattr(eng, "no_grad_keys", ())
         for key, p in self._model().named_parameters():
+            if key in unused:                        # .grad None: torch.optim.AdamW keeps no state for it either
+                continue
             o, n = offs[key], p.numel()
             self.state[p] = {"step": torch.tensor(float(self._step)), "exp_avg": self._m[o:o + n].view_as(p),
                              "exp_avg_sq": self._v[o:o + n].view_as(p)}

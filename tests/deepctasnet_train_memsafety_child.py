@@ -1,0 +1,56 @@
+"""TEST INFRASTRUCTURE: the memory-safety child of tests/test_gpu_deepconvtasnet_train.py (as
+tests/ctasnet_train_memsafety_child.py is for Conv-TasNet), covering dcttrain_train_forward and dcttrain_train_backward.  One mode per process:
+
+mode  poison       the workspace, gradients and outputs the engine allocates start filled with 0xFF bytes
+      guard_end    every buffer (weights, inputs, upstream gradients, workspace, gradients, outputs) ENDS flush against an
+                   unmapped page (tests/guardmem)
+      guard_start  every buffer STARTS flush against an unmapped page
+
+The call sequence (a big batch, then smaller shapes on the cached workspace) runs under test first, then with plain
+zero-filled buffers; predictions and gradients must be bit-identical (fixed reduction order everywhere).
+
+    python -m tests.deepctasnet_train_memsafety_child <mode>
+"""
+from __future__ import annotations
+
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from speech_separation_amd.engine import DeepConvTasNetTrainEngine  # noqa: E402
+from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
+from tests.ctasnet_memsafety_child import main  # noqa: E402  (the mode harness)
+from tests.deepconvtasnet_ref import synthetic_deepconvtasnet_weights  # noqa: E402
+
+SHAPES = [(3, 4001), (1, 400), (2, 17)]
+
+
+def run(dev, alloc, place):
+    eng = DeepConvTasNetTrainEngine(dev, alloc=alloc)
+    sd = synthetic_deepconvtasnet_weights(False, seed=3, slopes="distinct")
+    eng.bind({k: place(torch.from_numpy(v)) for k, v in sd.items()})
+    eng.bind_grads()
+    res = {}
+    for B, T in SHAPES:
+        mix = place(torch.from_numpy(synthetic_inputs(DPTN_AUDIO, B=B, T=T, seed=B * 7 + T)["mix"]))
+        s1, s2, tape = eng.train_forward(mix)
+        g = torch.Generator().manual_seed(B * 11 + T)
+        L = eng.out_len(T)
+        d1, d2 = (place(torch.randn(B, L, generator=g)) for _ in range(2))
+        eng.train_backward(mix, d1, d2, tape)
+        torch.cuda.synchronize()
+        res[f"{B}x{T}.s1"], res[f"{B}x{T}.s2"] = s1.cpu().numpy(), s2.cpu().numpy()
+        res[f"{B}x{T}.grad"] = eng._grads_flat.cpu().numpy()
+    eng.close()
+    return res
+
+
+if __name__ == "__main__":
+    rc = main(sys.argv[1], "dcttrain", run)
+    sys.stdout.flush()
+    os._exit(rc)      # no interpreter teardown with guard mappings still referenced by tensors

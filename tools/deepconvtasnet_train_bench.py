@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Time one DeepConvTasNet training step on the GPU (TrainableDeepConvTasNet: forward, device PIT SI-SNR loss, backward,
+fused clip, FusedAdamW) at B = 1, 4, 16 x 32000 samples: STEPS steps between synchronisations, median of REPS, mixtures/s
+and the fraction of the fp32-MFMA FLOP bound (dcttrain_flops_per_mixture = 3 x 58.0 GFLOP per mixture, 157.3 TFLOP/s).
+Baselines: the stock-PyTorch restatement (tests/deepconvtasnet_train_ref.py) trained eagerly with torch.optim.AdamW on the
+same GPU in the same run, and at B = 1 on 16 CPU threads.  After tools/convtasnet_train_bench.py.
+--check: the B = 16 gradient against fp64 autograd of the restatement on the GPU, on this forward's PReLU branches (kept
+out of the test suite for time).
+
+Usage:  python tools/deepconvtasnet_train_bench.py [--batches 1,4,16] [--steps 20] [--reps 5] [--check] [--json out.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from speech_separation_amd import FusedAdamW, SiSNRWavLoss, TrainableDeepConvTasNet  # noqa: E402
+from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
+from speech_separation_amd.train import train_step  # noqa: E402
+from tests import deepconvtasnet_train_ref as R  # noqa: E402
+from tests.deepconvtasnet_ref import synthetic_deepconvtasnet_weights  # noqa: E402
+from tests.sisnr_ref import pit_sisnr_loss  # noqa: E402
+
+PEAK = 157.3e12
+T = 32000
+
+
+def timed(fn, steps, reps, sync):
+    fn()
+    sync()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        sync()
+        out.append((time.perf_counter() - t0) / steps)
+    return statistics.median(out)
+
+
+def batch_of(B, dev):
+    inp = synthetic_inputs(DPTN_AUDIO, B=B, T=T, seed=B)
+    return {k: torch.from_numpy(inp[k]).to(dev) for k in ("mix", "s1", "s2")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,4,16")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cpu-batch", type=int, default=1)
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--no-baselines", action="store_true", help="time the HIP step only (profiling runs)")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.backends.cudnn.allow_tf32 = False
+    torch.backends.cuda.matmul.allow_tf32 = False
+    sd = {k: torch.from_numpy(v) for k, v in synthetic_deepconvtasnet_weights(False, 0).items()}
+    sync = lambda: torch.cuda.synchronize(dev)
+    res = {"T": T, "steps": a.steps, "reps": a.reps, "hip": {}, "stock_gpu": {}, "stock_cpu": {}}
+    for B in (int(b) for b in a.batches.split(",")):
+        m = TrainableDeepConvTasNet()
+        m.load_state_dict(sd, strict=True)
+        m = m.to(dev)
+        opt, crit, batch = FusedAdamW(m.parameters(), lr=1e-3), SiSNRWavLoss(), batch_of(B, dev)
+        t = timed(lambda: train_step(m, dict(batch), crit, opt, max_grad_norm=8.0), a.steps, a.reps, sync)
+        flops = m._engine.flops_per_mixture(T) * B
+        res["hip"][B] = {"ms": t * 1e3, "mix_per_s": B / t, "flop_bound_frac": flops / PEAK / t}
+        print(f"HIP     B={B:2d}: {t * 1e3:8.2f} ms/step  {B / t:8.1f} mixtures/s  {100 * flops / PEAK / t:5.1f} % of FLOP bound",
+              flush=True)
+        if a.check and B == 16:
+            m.zero_grad()
+            out = m(mix=batch["mix"])
+            masks = R.prelu_masks(m._engine, B, T)     # the fp64 / fp32 references follow this forward's PReLU branches
+            masks = {k: [t.to(dev) for t in v] if isinstance(v, list) else v.to(dev) for k, v in masks.items()}
+            g = torch.Generator().manual_seed(1)
+            d1, d2 = (torch.randn(B, T, generator=g).to(dev) for _ in range(2))
+            torch.autograd.backward([out["s1_pred"], out["s2_pred"]], [d1, d2])
+            sdd = {k: p.detach() for k, p in m.named_parameters()}
+            g64 = R.grads(sdd, batch["mix"], d1, d2, torch.float64, masks)
+            g32 = R.grads(sdd, batch["mix"], d1, d2, torch.float32, masks)
+            keys = [k for k, p in m.named_parameters() if p.grad is not None]     # all but decoder.deconv.weight
+            assert [k for k, p in m.named_parameters() if p.grad is None] == [R.UNUSED] and not g64[R.UNUSED].any()
+            grads = dict(m.named_parameters())
+            f = torch.cat([grads[k].grad.double().reshape(-1) for k in keys])
+            f64 = torch.cat([g64[k].reshape(-1) for k in keys])
+            f32 = torch.cat([g32[k].double().reshape(-1) for k in keys])
+            del g64, g32
+            res["check_b16"] = {"ratio": float((f - f64).norm() / f64.norm()), "fp32_ratio": float((f32 - f64).norm() / f64.norm())}
+            print("B=16 gradient vs fp64:", res["check_b16"], flush=True)
+        del m, opt
+        torch.cuda.empty_cache()
+        if a.no_baselines:
+            continue
+        # stock PyTorch-ROCm eager on the same GPU
+        p = {k: v.to(dev).clone().requires_grad_(True) for k, v in sd.items()}
+        sopt = torch.optim.AdamW(list(p.values()), lr=1e-3)
+
+        def stock_step(p=p, sopt=sopt, batch=batch):
+            sopt.zero_grad()
+            out = R.forward(p, batch["mix"])
+            pit_sisnr_loss(out["s1_pred"], out["s2_pred"], batch["s1"], batch["s2"]).backward()
+            torch.nn.utils.clip_grad_norm_(list(p.values()), 8.0)
+            sopt.step()
+        ts = timed(stock_step, max(2, a.steps // 4), 3, sync)
+        res["stock_gpu"][B] = {"ms": ts * 1e3, "mix_per_s": B / ts}
+        print(f"stock GPU B={B:2d}: {ts * 1e3:8.2f} ms/step  {B / ts:8.1f} mixtures/s", flush=True)
+        del p, sopt
+        torch.cuda.empty_cache()
+    if a.no_baselines:
+        print(json.dumps(res))
+        return
+    torch.set_num_threads(16)
+    B = a.cpu_batch
+    p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    sopt = torch.optim.AdamW(list(p.values()), lr=1e-3)
+    batch = batch_of(B, torch.device("cpu"))
+
+    def cpu_step():
+        sopt.zero_grad()
+        out = R.forward(p, batch["mix"])
+        pit_sisnr_loss(out["s1_pred"], out["s2_pred"], batch["s1"], batch["s2"]).backward()
+        torch.nn.utils.clip_grad_norm_(list(p.values()), 8.0)
+        sopt.step()
+    tc = timed(cpu_step, 1, 2, lambda: None)
+    res["stock_cpu"][B] = {"ms": tc * 1e3, "mix_per_s": B / tc, "threads": 16}
+    print(f"stock CPU B={B:2d} (16 threads): {tc * 1e3:8.1f} ms/step  {B / tc:8.2f} mixtures/s", flush=True)
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
