@@ -74,101 +74,74 @@ SYMBOLS = {
 }
 
 CTASNET_ABI_VERSION = 1
-
-#: name -> (restype, argtypes): every symbol include/ctasnet.h declares (Conv-TasNet forward, same shared object)
-CTASNET_SYMBOLS = {
-    "ctasnet_abi_version": (_i, []),
-    "ctasnet_create": (_i, [C.POINTER(_vp)]),
-    "ctasnet_destroy": (None, [_vp]),
-    "ctasnet_last_error": (C.c_char_p, [_vp]),
-    "ctasnet_num_weights": (_i, [_vp]),
-    "ctasnet_weight_name": (C.c_char_p, [_vp, _i]),
-    "ctasnet_weight_numel": (_i64, [_vp, _i]),
-    "ctasnet_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
-    "ctasnet_frames": (_i64, [_i64]),
-    "ctasnet_out_len": (_i64, [_i64]),
-    "ctasnet_workspace_bytes": (_sz, [_vp, _i, _i64]),
-    "ctasnet_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-    "ctasnet_flops_per_mixture": (C.c_double, [_vp, _i64]),
-    "ctasnet_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
-}
-
 DCTASNET_ABI_VERSION = 1
-
-#: name -> (restype, argtypes): every symbol include/dctasnet.h declares (deep Conv-TasNet forward, same shared object)
-DCTASNET_SYMBOLS = {
-    "dctasnet_abi_version": (_i, []),
-    "dctasnet_create": (_i, [C.POINTER(_vp), _i]),
-    "dctasnet_destroy": (None, [_vp]),
-    "dctasnet_last_error": (C.c_char_p, [_vp]),
-    "dctasnet_num_weights": (_i, [_vp]),
-    "dctasnet_weight_name": (C.c_char_p, [_vp, _i]),
-    "dctasnet_weight_numel": (_i64, [_vp, _i]),
-    "dctasnet_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
-    "dctasnet_frames": (_i64, [_i64]),
-    "dctasnet_out_len": (_i64, [_i64]),
-    "dctasnet_workspace_bytes": (_sz, [_vp, _i, _i64, _i]),
-    "dctasnet_forward": (_i, [_vp, _fp, _fp, _fp, _i, _i64, _i, _fp, _fp, _vp, _sz, _vp]),
-    "dctasnet_flops_per_mixture": (C.c_double, [_vp, _i64]),
-    "dctasnet_min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
-    "dctasnet_weight_pack_bytes": (_sz, [_vp]),
-}
-
 CTTRAIN_ABI_VERSION = 1
-
-#: name -> (restype, argtypes): every symbol include/ctasnet_train.h declares (Conv-TasNet training step, same shared object)
-CTTRAIN_SYMBOLS = {
-    "cttrain_abi_version": (_i, []),
-    "cttrain_create": (_i, [C.POINTER(_vp)]),
-    "cttrain_destroy": (None, [_vp]),
-    "cttrain_last_error": (C.c_char_p, [_vp]),
-    "cttrain_num_weights": (_i, [_vp]),
-    "cttrain_weight_name": (C.c_char_p, [_vp, _i]),
-    "cttrain_weight_numel": (_i64, [_vp, _i]),
-    "cttrain_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
-    "cttrain_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
-    "cttrain_flat_offset": (_i64, [_vp, _i]),
-    "cttrain_flat_numel": (_i64, [_vp]),
-    "cttrain_frames": (_i64, [_i64]),
-    "cttrain_out_len": (_i64, [_i64]),
-    "cttrain_workspace_bytes": (_sz, [_vp, _i, _i64]),
-    "cttrain_train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-    "cttrain_train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-    "cttrain_tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
-    "cttrain_clip_scratch_bytes": (_sz, [_vp]),
-    "cttrain_grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
-    "cttrain_adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
-                                _vp]),
-    "cttrain_flops_per_mixture": (C.c_double, [_vp, _i64]),
-}
-
 DCTTRAIN_ABI_VERSION = 1
 
-#: name -> (restype, argtypes): every symbol include/dctasnet_train.h declares (deep Conv-TasNet training step, same shared object)
-DCTTRAIN_SYMBOLS = {
-    "dcttrain_abi_version": (_i, []),
-    "dcttrain_create": (_i, [C.POINTER(_vp), _i]),
-    "dcttrain_destroy": (None, [_vp]),
-    "dcttrain_last_error": (C.c_char_p, [_vp]),
-    "dcttrain_num_weights": (_i, [_vp]),
-    "dcttrain_weight_name": (C.c_char_p, [_vp, _i]),
-    "dcttrain_weight_numel": (_i64, [_vp, _i]),
-    "dcttrain_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
-    "dcttrain_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
-    "dcttrain_flat_offset": (_i64, [_vp, _i]),
-    "dcttrain_flat_numel": (_i64, [_vp]),
-    "dcttrain_frames": (_i64, [_i64]),
-    "dcttrain_out_len": (_i64, [_i64]),
-    "dcttrain_workspace_bytes": (_sz, [_vp, _i, _i64]),
-    "dcttrain_train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-    "dcttrain_train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-    "dcttrain_tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
-    "dcttrain_clip_scratch_bytes": (_sz, [_vp]),
-    "dcttrain_grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
-    "dcttrain_adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
-                                _vp]),
-    "dcttrain_flops_per_mixture": (C.c_double, [_vp, _i64]),
-}
+
+def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
+    """The inference boundary of a Conv-TasNet family member: `create_extra` / `workspace_extra` extend the argument
+    lists of create / workspace_bytes, `forward_in` follows the mixture in forward, `more` are the member's own entries."""
+    d = {
+        "abi_version": (_i, []),
+        "create": (_i, [C.POINTER(_vp), *create_extra]),
+        "destroy": (None, [_vp]),
+        "last_error": (C.c_char_p, [_vp]),
+        "num_weights": (_i, [_vp]),
+        "weight_name": (C.c_char_p, [_vp, _i]),
+        "weight_numel": (_i64, [_vp, _i]),
+        "bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+        "frames": (_i64, [_i64]),
+        "out_len": (_i64, [_i64]),
+        "workspace_bytes": (_sz, [_vp, _i, _i64, *workspace_extra]),
+        "forward": (_i, [_vp, _fp, *forward_in, _i, _i64, *workspace_extra, _fp, _fp, _vp, _sz, _vp]),
+        "flops_per_mixture": (C.c_double, [_vp, _i64]),
+        "min_bytes_per_mixture": (C.c_double, [_vp, _i64]),
+        **(more or {}),
+    }
+    return {f"{prefix}_{k}": v for k, v in d.items()}
+
+
+def _train_symbols(prefix, create_extra=()):
+    """The training boundary of a Conv-TasNet family member; `create_extra` extends the argument list of create."""
+    d = {
+        "abi_version": (_i, []),
+        "create": (_i, [C.POINTER(_vp), *create_extra]),
+        "destroy": (None, [_vp]),
+        "last_error": (C.c_char_p, [_vp]),
+        "num_weights": (_i, [_vp]),
+        "weight_name": (C.c_char_p, [_vp, _i]),
+        "weight_numel": (_i64, [_vp, _i]),
+        "bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+        "bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
+        "flat_offset": (_i64, [_vp, _i]),
+        "flat_numel": (_i64, [_vp]),
+        "frames": (_i64, [_i64]),
+        "out_len": (_i64, [_i64]),
+        "workspace_bytes": (_sz, [_vp, _i, _i64]),
+        "train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+        "train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
+        "tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
+        "clip_scratch_bytes": (_sz, [_vp]),
+        "grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
+        "adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                            _vp]),
+        "flops_per_mixture": (C.c_double, [_vp, _i64]),
+    }
+    return {f"{prefix}_{k}": v for k, v in d.items()}
+
+
+# The four tables below are name -> (restype, argtypes), as SYMBOLS, for entry points of the same shared object.
+#: every symbol include/ctasnet.h declares (Conv-TasNet forward)
+CTASNET_SYMBOLS = _infer_symbols("ctasnet")
+#: every symbol include/dctasnet.h declares (deep Conv-TasNet forward): create takes av, workspace_bytes and forward take Tv,
+#: forward takes the two video streams after the mixture, and the weight pack has a size query
+DCTASNET_SYMBOLS = _infer_symbols("dctasnet", create_extra=[_i], workspace_extra=[_i], forward_in=[_fp, _fp],
+                                  more={"weight_pack_bytes": (_sz, [_vp])})
+#: every symbol include/ctasnet_train.h declares (Conv-TasNet training step)
+CTTRAIN_SYMBOLS = _train_symbols("cttrain")
+#: every symbol include/dctasnet_train.h declares (deep Conv-TasNet training step): create takes av
+DCTTRAIN_SYMBOLS = _train_symbols("dcttrain", create_extra=[_i])
 
 _lib: Optional[C.CDLL] = None
 
@@ -195,15 +168,12 @@ def load() -> C.CDLL:
             raise RuntimeError(f"libdptnav.so does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.dptnav_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"libdptnav ABI {lib.dptnav_abi_version()} != binding {ABI_VERSION}: rebuild")
-    if lib.ctasnet_abi_version() != CTASNET_ABI_VERSION:
-        raise RuntimeError(f"ctasnet ABI {lib.ctasnet_abi_version()} != binding {CTASNET_ABI_VERSION}: rebuild")
-    if lib.dctasnet_abi_version() != DCTASNET_ABI_VERSION:
-        raise RuntimeError(f"dctasnet ABI {lib.dctasnet_abi_version()} != binding {DCTASNET_ABI_VERSION}: rebuild")
-    if lib.cttrain_abi_version() != CTTRAIN_ABI_VERSION:
-        raise RuntimeError(f"cttrain ABI {lib.cttrain_abi_version()} != binding {CTTRAIN_ABI_VERSION}: rebuild")
-    if lib.dcttrain_abi_version() != DCTTRAIN_ABI_VERSION:
-        raise RuntimeError(f"dcttrain ABI {lib.dcttrain_abi_version()} != binding {DCTTRAIN_ABI_VERSION}: rebuild")
+    for fn, want, label in ((lib.dptnav_abi_version, ABI_VERSION, "libdptnav"),
+                            (lib.ctasnet_abi_version, CTASNET_ABI_VERSION, "ctasnet"),
+                            (lib.dctasnet_abi_version, DCTASNET_ABI_VERSION, "dctasnet"),
+                            (lib.cttrain_abi_version, CTTRAIN_ABI_VERSION, "cttrain"),
+                            (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain")):
+        if fn() != want:
+            raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib
     return lib

@@ -1,7 +1,8 @@
 // ctasnet_train_kernels.h -- what the Conv-TasNet training units share (ctasnet_train.hip: TrainableConvTasNet,
 // deepctasnet_train.hip: TrainableDeepConvTasNet): the backward kernels of the Separator and of the mask head, the engine
-// hooks of the weight / data gradients, the slab launch helpers, the Separator's part of the workspace plan and
-// launch_separator_backward -- the counterpart of launch_separator (ctasnet_kernels.h), which serves the forwards.
+// hooks of the weight / data gradients, the slab launch helpers, the Separator's part of the workspace plan,
+// launch_separator_backward -- the counterpart of launch_separator (ctasnet_kernels.h), which serves the forwards -- and
+// the training handle with the bodies of the entry points that do not depend on the model (CtTrainHandle, at the end).
 // Everything sits in an anonymous namespace, so each including unit compiles its own copy.
 //
 // Data gradients run on the weights-stationary engine in its transposed-weight form (gemm_ws.h, WT = true: the forward
@@ -667,6 +668,109 @@ int launch_separator_backward(Ctx* c, hipStream_t st, const float* const* sw, fl
                        M, denc, nullptr);
     CT_LAUNCH_CHECK(c, "cttrain GlobalNorm backward");
   }
+  return CTASNET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the training handle and what the extern "C" entry points of the training units share (idiom of ctasnet_handle.h)
+// ------------------------------------------------------------------------------------------------
+struct CtTrainHandle : CtHandle {
+  const char* const prefix;    // of the unit's entry points, for messages: "cttrain" / "dcttrain"
+  const int no_grad_slot;      // a parameter the forward never reads: no gradient, no AdamW step; -1 when there is none
+  std::vector<float*> g;
+  bool gbound = false;
+  CtTrainHandle(const char* prefix_, int no_grad_slot_) : prefix(prefix_), no_grad_slot(no_grad_slot_) {}
+};
+
+inline int bind_grads(CtTrainHandle* h, float* const* dev_ptrs, int n) {
+  if (int rc = check_table_ptrs(h, reinterpret_cast<const void* const*>(dev_ptrs), n, "gradient", 4)) return rc;
+  h->g.assign(dev_ptrs, dev_ptrs + n);
+  h->gbound = true;
+  return CTASNET_OK;
+}
+
+// the flat layout of gradient / exp_avg / exp_avg_sq: every slot rounded up to 64 floats
+inline int64_t flat_offset(const CtHandle* h, int slot) {
+  if (slot < 0 || slot > (int)h->numels.size()) return -1;
+  int64_t o = 0;
+  for (int i = 0; i < slot; ++i) o += (int64_t)align64f((size_t)h->numels[i]);
+  return o;
+}
+inline int64_t flat_numel(const CtHandle* h) { return flat_offset(h, (int)h->numels.size()); }
+
+inline int train_grad_clip(CtTrainHandle* h, float* flat_grad, int64_t n_flat, float max_norm, void* scratch, size_t scratch_bytes,
+                           float* norm_out, void* stream) {
+  if (!flat_grad || !norm_out || n_flat < 4 || (n_flat & 3) || ((uintptr_t)flat_grad & 15))
+    return h->fail(CTASNET_ERR_INVALID, "grad_clip: flat gradient must be 16-byte aligned with a multiple of 4 floats");
+  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < CLIP_PARTS * sizeof(double))
+    return h->fail(CTASNET_ERR_WORKSPACE, "grad_clip: scratch too small / misaligned");
+  launch_grad_clip((hipStream_t)stream, h->num_cus, flat_grad, n_flat, max_norm, (double*)scratch, norm_out);
+  if (hipError_t e = hipGetLastError()) return h->fail(CTASNET_ERR_HIP, "%s grad_clip: %s", h->prefix, hipGetErrorString(e));
+  return CTASNET_OK;
+}
+
+inline int train_adamw_step(CtTrainHandle* h, const float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
+  if (!h->bound) return h->fail(CTASNET_ERR_WEIGHTS, "adamw_step: weights not bound (the step updates the bound parameters in place)");
+  if (!flat_grad || !exp_avg || !exp_avg_sq || n_flat != flat_numel(h) || step < 1)
+    return h->fail(CTASNET_ERR_INVALID, "adamw_step: bad argument (flat buffers must hold %lld floats, step >= 1)",
+                   (long long)flat_numel(h));
+  launch_adamw((hipStream_t)stream, h->w.data(), h->numels.data(), (int)h->names.size(), h->no_grad_slot, 64, flat_grad, exp_avg,
+               exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step);
+  if (hipError_t e = hipGetLastError()) return h->fail(CTASNET_ERR_HIP, "%s adamw_step: %s", h->prefix, hipGetErrorString(e));
+  return CTASNET_OK;
+}
+
+// what every training plan starts with; `rows` is the unit's spelling of B*F*1024 in the message
+struct TrainPlanBase : SepTrainPlan {
+  int64_t F, M, Lout;
+  size_t total;
+};
+
+inline int plan_train_head(CtHandle* c, int B, int64_t T, const char* rows, TrainPlanBase& p) {
+  if (int rc = check_batch(c, B, T)) return rc;
+  p.F = frames_of(T);
+  p.M = (int64_t)B * p.F;
+  if (p.M * 2 * CT_N > (int64_t)INT32_MAX)      // 32-bit row indexing of the loaders
+    return c->fail(CTASNET_ERR_INVALID, "%s = %lld exceeds 32-bit indexing (B=%d, T=%lld)", rows, (long long)(p.M * 2 * CT_N), B,
+                   (long long)T);
+  p.Lout = CT_L * (T / CT_L);
+  return CTASNET_OK;
+}
+
+// *_tape_offset of the Separator's tensors (*_TAPE_V1 / _U / _SKIP in the headers); any other kind is refused
+enum { SEP_TAPE_V1 = 0, SEP_TAPE_U = 1, SEP_TAPE_SKIP = 2 };
+inline int64_t sep_tape_offset(CtHandle* h, const TrainPlanBase& p, int which, int block) {
+  if (which == SEP_TAPE_SKIP) return block == 0 ? (int64_t)p.off_skip : -1;
+  if (block < 0 || block >= CT_BLOCKS) {
+    h->fail(CTASNET_ERR_INVALID, "block %d out of range", block);
+    return -1;
+  }
+  if (which == SEP_TAPE_V1) return (int64_t)(p.off_v1 + (size_t)block * p.M * CT_H * 4);
+  if (which == SEP_TAPE_U) return (int64_t)(p.off_u + (size_t)block * p.M * CT_H * 4);
+  h->fail(CTASNET_ERR_INVALID, "unknown tape tensor %d", which);
+  return -1;
+}
+
+// typed pointers into a workspace
+struct WsPtr {
+  char* base;
+  float* fp(size_t off) const { return reinterpret_cast<float*>(base + off); }
+  float2* f2(size_t off) const { return reinterpret_cast<float2*>(base + off); }
+};
+
+// What *_train_forward (o1, o2: the predictions) and *_train_backward (their gradients; needs the gradients bound) start
+// with: the checks, the unit's plan and the workspace behind it.
+template <class Plan>
+int train_prologue(CtTrainHandle* c, int (*make_plan)(CtHandle*, int, int64_t, Plan&), bool backward, const void* mix,
+                   const void* o1, const void* o2, int B, int64_t T, void* ws, size_t ws_bytes, Plan& p, WsPtr& at) {
+  if (!c) return CTASNET_ERR_INVALID;
+  if (!c->bound) return c->fail(CTASNET_ERR_WEIGHTS, "weights not bound (%s_bind_weights)", c->prefix);
+  if (backward && !c->gbound) return c->fail(CTASNET_ERR_WEIGHTS, "gradients not bound (%s_bind_grads)", c->prefix);
+  if (!mix || !o1 || !o2) return c->fail(CTASNET_ERR_INVALID, "mix / %s must not be NULL", backward ? "d_s1 / d_s2" : "s1_pred / s2_pred");
+  if (int rc = make_plan(c, B, T, p)) return rc;
+  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
+  at.base = static_cast<char*>(ws);
   return CTASNET_OK;
 }
 

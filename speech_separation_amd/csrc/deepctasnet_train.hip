@@ -120,29 +120,24 @@ struct ALoadTapCols {
   }
 };
 
-struct Plan : SepTrainPlan {
-  int64_t F, M, Lout;
-  size_t off_wpk, off_c0, off_ez, off_dz, off_ga, off_gb, total;
+struct Plan : TrainPlanBase {
+  size_t off_wpk, off_c0, off_ez, off_dz, off_ga, off_gb;
 };
 
 }  // namespace
 
-struct dcttrain_ctx : CtHandle {
-  std::vector<float*> g;
-  bool gbound = false;
+static_assert(DCTTRAIN_TAPE_V1 == SEP_TAPE_V1 && DCTTRAIN_TAPE_U == SEP_TAPE_U && DCTTRAIN_TAPE_SKIP == SEP_TAPE_SKIP,
+              "sep_tape_offset takes the header's tape kinds");
+
+struct dcttrain_ctx : CtTrainHandle {
+  dcttrain_ctx() : CtTrainHandle("dcttrain", DCT_UNUSED) {}
 };
 
 namespace {
 
-int make_plan(dcttrain_ctx* c, int B, int64_t T, Plan& p) {
-  if (int rc = check_batch(c, B, T)) return rc;
-  p.F = frames_of(T);
-  p.M = (int64_t)B * p.F;
+int make_plan(CtHandle* c, int B, int64_t T, Plan& p) {
   // the decoder runs on 2*B*F rows of 512 (32-bit row indexing in the tap-shifted loaders)
-  if (2 * p.M * CT_N > (int64_t)INT32_MAX)
-    return c->fail(DCTTRAIN_ERR_INVALID, "2*B*F*512 = %lld exceeds 32-bit indexing (B=%d, T=%lld)", (long long)(2 * p.M * CT_N),
-                   B, (long long)T);
-  p.Lout = CT_L * (T / CT_L);
+  if (int rc = plan_train_head(c, B, T, "2*B*F*512", p)) return rc;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
   const size_t M = (size_t)p.M;
@@ -274,21 +269,12 @@ int dcttrain_bind_weights(dcttrain_handle h, const float* const* dev_ptrs, int n
 }
 
 int dcttrain_bind_grads(dcttrain_handle h, float* const* dev_ptrs, int n) {
-  if (!h) return DCTTRAIN_ERR_INVALID;
-  if (int rc = check_table_ptrs(h, reinterpret_cast<const void* const*>(dev_ptrs), n, "gradient", 4)) return rc;
-  h->g.assign(dev_ptrs, dev_ptrs + n);
-  h->gbound = true;
-  return DCTTRAIN_OK;
+  return h ? bind_grads(h, dev_ptrs, n) : DCTTRAIN_ERR_INVALID;
 }
 
-int64_t dcttrain_flat_offset(dcttrain_handle h, int slot) {
-  if (!h || slot < 0 || slot > (int)h->numels.size()) return -1;
-  int64_t o = 0;
-  for (int i = 0; i < slot; ++i) o += (int64_t)align64f((size_t)h->numels[i]);
-  return o;
-}
+int64_t dcttrain_flat_offset(dcttrain_handle h, int slot) { return h ? flat_offset(h, slot) : -1; }
 
-int64_t dcttrain_flat_numel(dcttrain_handle h) { return h ? dcttrain_flat_offset(h, (int)h->numels.size()) : -1; }
+int64_t dcttrain_flat_numel(dcttrain_handle h) { return h ? flat_numel(h) : -1; }
 
 int64_t dcttrain_frames(int64_t T) { return frames_of(T); }
 
@@ -306,7 +292,6 @@ int64_t dcttrain_tape_offset(dcttrain_handle h, int B, int64_t T, int which, int
   Plan p;
   if (make_plan(h, B, T, p)) return -1;
   const size_t M = (size_t)p.M;
-  if (which == DCTTRAIN_TAPE_SKIP) return block == 0 ? (int64_t)p.off_skip : -1;
   if (which == DCTTRAIN_TAPE_ENC_Z || which == DCTTRAIN_TAPE_DEC_Z) {
     if (block < 0 || block >= 4) {
       h->fail(DCTTRAIN_ERR_INVALID, "dense layer %d out of range", block);
@@ -315,37 +300,25 @@ int64_t dcttrain_tape_offset(dcttrain_handle h, int B, int64_t T, int which, int
     return which == DCTTRAIN_TAPE_ENC_Z ? (int64_t)(p.off_ez + (size_t)block * M * CT_N * 4)
                                         : (int64_t)(p.off_dz + (size_t)block * 2 * M * CT_N * 4);
   }
-  if (block < 0 || block >= CT_BLOCKS) {
-    h->fail(DCTTRAIN_ERR_INVALID, "block %d out of range", block);
-    return -1;
-  }
-  if (which == DCTTRAIN_TAPE_V1) return (int64_t)(p.off_v1 + (size_t)block * M * CT_H * 4);
-  if (which == DCTTRAIN_TAPE_U) return (int64_t)(p.off_u + (size_t)block * M * CT_H * 4);
-  h->fail(DCTTRAIN_ERR_INVALID, "unknown tape tensor %d", which);
-  return -1;
+  return sep_tape_offset(h, p, which, block);
 }
 
 int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T, float* s1_pred, float* s2_pred, void* ws,
                            size_t ws_bytes, void* stream) {
-  if (!h) return DCTTRAIN_ERR_INVALID;
   dcttrain_ctx* c = h;
-  if (!c->bound) return c->fail(DCTTRAIN_ERR_WEIGHTS, "weights not bound (dcttrain_bind_weights)");
-  if (!mix || !s1_pred || !s2_pred) return c->fail(DCTTRAIN_ERR_INVALID, "mix / s1_pred / s2_pred must not be NULL");
   Plan p;
-  if (int rc = make_plan(c, B, T, p)) return rc;
-  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
+  WsPtr at;
+  if (int rc = train_prologue(c, make_plan, false, mix, s1_pred, s2_pred, B, T, ws, ws_bytes, p, at)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   const int F = (int)p.F;
   const int64_t M = p.M;
   const auto& W = c->w;
-  float* wpk = fp(p.off_wpk);
-  float* enc = fp(p.off_enc);
-  float* c0 = fp(p.off_c0);
-  float* ym = fp(p.off_ym);
-  float* ydec = fp(p.off_dv);          // the last decoder activation [2M][512]: scratch until the backward's head kernel
-  float* taps = fp(p.off_taps);
+  float* wpk = at.fp(p.off_wpk);
+  float* enc = at.fp(p.off_enc);
+  float* c0 = at.fp(p.off_c0);
+  float* ym = at.fp(p.off_ym);
+  float* ydec = at.fp(p.off_dv);          // the last decoder activation [2M][512]: scratch until the backward's head kernel
+  float* taps = at.fp(p.off_taps);
   const SepBuffers sb = sep_tape_buffers(p, ws);
 
   // weights of the eight dense convs -> fragment order, this forward's copy
@@ -361,7 +334,7 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
   hipLaunchKernelGGL(ctasnet_encoder_kernel<true>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], W[1], c0, nullptr);
   CT_LAUNCH_CHECK(c, "dcttrain encoder");
   for (int l = 0; l < 4; ++l) {
-    float* z = fp(p.off_ez) + (size_t)l * M * CT_N;
+    float* z = at.fp(p.off_ez) + (size_t)l * M * CT_N;
     const float* x = l == 0 ? c0 : z - (size_t)M * CT_N;
     if (int rc = launch_dense<true>(c, st, wpk + (int64_t)l * 3 * DC_TAP_FLOATS, false, 1 << l, x, l == 0 ? nullptr : W[1 + 3 * l],
                                     z, l == 3 ? enc : nullptr, M, F, 0, W[3 + 3 * l], W[4 + 3 * l], nullptr,
@@ -374,7 +347,7 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
 
   // deep decoder (deepconvtasnet.py:96-120) on 2M rows (b, f, speaker), then the output head as taps + overlap-add
   for (int l = 0; l < 4; ++l) {
-    float* z = fp(p.off_dz) + (size_t)l * 2 * M * CT_N;
+    float* z = at.fp(p.off_dz) + (size_t)l * 2 * M * CT_N;
     const float* x = l == 0 ? ym : z - (size_t)2 * M * CT_N;
     if (int rc = launch_dense<true>(c, st, wpk + (int64_t)(4 + l) * 3 * DC_TAP_FLOATS, true, 8 >> l, x,
                                     l == 0 ? nullptr : W[DC_DEC0 + 3 * l - 1], z, l == 3 ? ydec : nullptr, 2 * M, F, 1,
@@ -387,29 +360,23 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
 
 int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t T, const float* d_s1, const float* d_s2, void* ws,
                             size_t ws_bytes, void* stream) {
-  if (!h) return DCTTRAIN_ERR_INVALID;
   dcttrain_ctx* c = h;
-  if (!c->bound) return c->fail(DCTTRAIN_ERR_WEIGHTS, "weights not bound (dcttrain_bind_weights)");
-  if (!c->gbound) return c->fail(DCTTRAIN_ERR_WEIGHTS, "gradients not bound (dcttrain_bind_grads)");
-  if (!mix || !d_s1 || !d_s2) return c->fail(DCTTRAIN_ERR_INVALID, "mix / d_s1 / d_s2 must not be NULL");
   Plan p;
-  if (int rc = make_plan(c, B, T, p)) return rc;
-  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
+  WsPtr at;
+  if (int rc = train_prologue(c, make_plan, true, mix, d_s1, d_s2, B, T, ws, ws_bytes, p, at)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
   const int F = (int)p.F;
   const int64_t M = p.M;
   const auto& W = c->w;
   const auto& G = c->g;
-  float* wpk = fp(p.off_wpk);
-  float* dtaps = fp(p.off_taps);
-  float* denc = fp(p.off_denc);
-  float* slab = fp(p.off_slab);
-  float* cslab = fp(p.off_cslab);
-  float* aslab = fp(p.off_aslab);
-  float* ga = fp(p.off_ga);
-  float* gb = fp(p.off_gb);
+  float* wpk = at.fp(p.off_wpk);
+  float* dtaps = at.fp(p.off_taps);
+  float* denc = at.fp(p.off_denc);
+  float* slab = at.fp(p.off_slab);
+  float* cslab = at.fp(p.off_cslab);
+  float* aslab = at.fp(p.off_aslab);
+  float* ga = at.fp(p.off_ga);
+  float* gb = at.fp(p.off_gb);
   int ns = 0;
 
   // the eight layers' weights for the data gradients, from the weights as they are now: the other orientation
@@ -427,7 +394,7 @@ int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t 
     hipLaunchKernelGGL(dcttrain_outsum_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, d_s1, d_s2, (int64_t)B * p.Lout, aslab);
     CT_LAUNCH_CHECK(c, "dcttrain output bias");
     if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, G[DC_DEC0 + 13], 1)) return rc;
-    const float* z3 = fp(p.off_dz) + (size_t)3 * 2 * M * CT_N;
+    const float* z3 = at.fp(p.off_dz) + (size_t)3 * 2 * M * CT_N;
     if (int rc = launch_wgrad<CT_N, 2 * CT_L>(c, st, 2 * M, ALoadDensePReLU{z3, W[DC_DEC0 + 11], 2 * M, CT_N, 32},
                                               ALoadDense{dtaps, 2 * M, 2 * CT_L, 32}, slab, &ns))
       return rc;
@@ -444,8 +411,8 @@ int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t 
   float* dy = ga;
   float* dx = gb;
   for (int l = 3; l >= 0; --l) {
-    const float* z = fp(p.off_dz) + (size_t)l * 2 * M * CT_N;
-    const DenseBwd d{true, 8 >> l, 1, 2 * M, F, dy, z, l == 0 ? fp(p.off_ym) : z - (size_t)2 * M * CT_N,
+    const float* z = at.fp(p.off_dz) + (size_t)l * 2 * M * CT_N;
+    const DenseBwd d{true, 8 >> l, 1, 2 * M, F, dy, z, l == 0 ? at.fp(p.off_ym) : z - (size_t)2 * M * CT_N,
                      l == 0 ? nullptr : W[DC_DEC0 + 3 * l - 1], W[DC_DEC0 + 2 + 3 * l], wpk + (int64_t)(4 + l) * 3 * DC_TAP_FLOATS,
                      dx, G[DC_DEC0 + 3 * l], G[DC_DEC0 + 1 + 3 * l], G[DC_DEC0 + 2 + 3 * l]};
     if (int rc = dense_backward(c, st, d, slab, cslab, aslab)) return rc;
@@ -460,8 +427,8 @@ int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t 
   dy = denc;
   dx = ga;
   for (int l = 3; l >= 0; --l) {
-    const float* z = fp(p.off_ez) + (size_t)l * M * CT_N;
-    const DenseBwd d{false, 1 << l, 0, M, F, dy, z, l == 0 ? fp(p.off_c0) : z - (size_t)M * CT_N,
+    const float* z = at.fp(p.off_ez) + (size_t)l * M * CT_N;
+    const DenseBwd d{false, 1 << l, 0, M, F, dy, z, l == 0 ? at.fp(p.off_c0) : z - (size_t)M * CT_N,
                      l == 0 ? nullptr : W[1 + 3 * l], W[4 + 3 * l], wpk + (int64_t)l * 3 * DC_TAP_FLOATS, dx, G[2 + 3 * l],
                      G[3 + 3 * l], G[4 + 3 * l]};
     if (int rc = dense_backward(c, st, d, slab, cslab, aslab)) return rc;
@@ -480,54 +447,14 @@ size_t dcttrain_clip_scratch_bytes(dcttrain_handle) { return CLIP_PARTS * sizeof
 
 int dcttrain_grad_clip(dcttrain_handle h, float* flat_grad, int64_t n_flat, float max_norm, void* scratch, size_t scratch_bytes,
                        float* norm_out, void* stream) {
-  if (!h) return DCTTRAIN_ERR_INVALID;
-  if (!flat_grad || !norm_out || n_flat < 4 || (n_flat & 3) || ((uintptr_t)flat_grad & 15))
-    return h->fail(DCTTRAIN_ERR_INVALID, "grad_clip: flat gradient must be 16-byte aligned with a multiple of 4 floats");
-  if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < CLIP_PARTS * sizeof(double))
-    return h->fail(DCTTRAIN_ERR_WORKSPACE, "grad_clip: scratch too small / misaligned");
-  hipStream_t st = (hipStream_t)stream;
-  double* partials = (double*)scratch;
-  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, flat_grad, n_flat / 4, partials);
-  hipLaunchKernelGGL(clip_scale_kernel, dim3(h->num_cus * 2), dim3(256), 0, st, flat_grad, n_flat / 4, partials, CLIP_PARTS,
-                     max_norm, norm_out);
-  CT_LAUNCH_CHECK(h, "dcttrain grad_clip");
-  return DCTTRAIN_OK;
+  return h ? train_grad_clip(h, flat_grad, n_flat, max_norm, scratch, scratch_bytes, norm_out, stream) : DCTTRAIN_ERR_INVALID;
 }
 
+// decoder.deconv.weight (no_grad_slot) takes no step and no decay: what torch.optim.AdamW does with .grad None
 int dcttrain_adamw_step(dcttrain_handle h, const float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat, double lr,
                         double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
-  if (!h) return DCTTRAIN_ERR_INVALID;
-  if (!h->bound) return h->fail(DCTTRAIN_ERR_WEIGHTS, "adamw_step: weights not bound (the step updates the bound parameters in place)");
-  if (!flat_grad || !exp_avg || !exp_avg_sq || n_flat != dcttrain_flat_numel(h) || step < 1)
-    return h->fail(DCTTRAIN_ERR_INVALID, "adamw_step: bad argument (flat buffers must hold %lld floats, step >= 1)",
-                   (long long)dcttrain_flat_numel(h));
-  // constants formed in double and rounded once, as torch does (dptnav_adamw_step)
-  const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
-  const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  const int n = (int)h->names.size();
-  int64_t off = 0;
-  AdamwArgs a{};
-  int cnt = 0;
-  auto flush = [&]() {
-    if (cnt == 0) return;
-    hipLaunchKernelGGL(adamw_kernel, dim3(cnt, ADAMW_YBLOCKS), dim3(256), 0, (hipStream_t)stream, a, flat_grad, exp_avg,
-                       exp_avg_sq, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, decay,
-                       step_size, inv_sqrt_bc2);
-    cnt = 0;
-  };
-  for (int i = 0; i < n; ++i) {
-    if (i != DCT_UNUSED) {       // no gradient, no step, no decay: what torch.optim.AdamW does with .grad None
-      a.param[cnt] = const_cast<float*>(h->w[i]);
-      a.off[cnt] = off;
-      a.n[cnt] = (int)h->numels[i];
-      if (++cnt == ADAMW_MAX) flush();
-    }
-    off += (int64_t)align64f((size_t)h->numels[i]);
-  }
-  flush();
-  CT_LAUNCH_CHECK(h, "dcttrain adamw_step");
-  return DCTTRAIN_OK;
+  return h ? train_adamw_step(h, flat_grad, exp_avg, exp_avg_sq, n_flat, lr, beta1, beta2, eps, weight_decay, step, stream)
+           : DCTTRAIN_ERR_INVALID;
 }
 
 double dcttrain_flops_per_mixture(dcttrain_handle, int64_t T) {

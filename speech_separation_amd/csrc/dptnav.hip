@@ -2477,11 +2477,7 @@ int dptnav_grad_clip(dptnav_handle h, float* flat_grad, int64_t n_flat, float ma
     return h->fail(DPTNAV_ERR_INVALID, "grad_clip: flat gradient must be 16-byte aligned with a multiple of 4 floats");
   if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < CLIP_PARTS * sizeof(double))
     return h->fail(DPTNAV_ERR_WORKSPACE, "grad_clip: scratch too small / misaligned");
-  hipStream_t st = (hipStream_t)stream;
-  double* partials = (double*)scratch;
-  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, flat_grad, n_flat / 4, partials);
-  hipLaunchKernelGGL(clip_scale_kernel, dim3(h->num_cus * 2), dim3(256), 0, st, flat_grad, n_flat / 4, partials, CLIP_PARTS, max_norm,
-                     norm_out);
+  launch_grad_clip((hipStream_t)stream, h->num_cus, flat_grad, n_flat, max_norm, (double*)scratch, norm_out);
   LAUNCH_CHECK(h, "grad_clip");
   return DPTNAV_OK;
 }
@@ -2493,27 +2489,9 @@ int dptnav_adamw_step(dptnav_handle h, const float* flat_grad, float* exp_avg, f
   if (!flat_grad || !exp_avg || !exp_avg_sq || n_flat != dptnav_flat_numel(h) || step < 1)
     return h->fail(DPTNAV_ERR_INVALID, "adamw_step: bad argument (flat buffers must hold %lld floats, step >= 1)",
                    (long long)dptnav_flat_numel(h));
-  // hyper-parameters arrive as doubles (Python floats) and every derived constant is formed in double before it is
-  // rounded to fp32 once, as torch does: 1 - 0.999f would already be off by 1.3e-5 relative
-  const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
-  const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  const int n = (int)h->names.size();
-  int64_t off = 0;
-  for (int lo = 0; lo < n; lo += ADAMW_MAX) {
-    AdamwArgs a{};
-    const int cnt = std::min(ADAMW_MAX, n - lo);
-    for (int e = 0; e < cnt; ++e) {
-      a.param[e] = const_cast<float*>(h->ptr[lo + e]);
-      a.off[e] = off;
-      a.n[e] = (int)h->numel[lo + e];
-      off += (int64_t)align64((size_t)h->numel[lo + e]);
-    }
-    hipLaunchKernelGGL(adamw_kernel, dim3(cnt, ADAMW_YBLOCKS), dim3(256), 0, (hipStream_t)stream, a, flat_grad, exp_avg, exp_avg_sq,
-                       (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, decay, step_size,
-                       inv_sqrt_bc2);
-    LAUNCH_CHECK(h, "adamw_step");
-  }
+  launch_adamw((hipStream_t)stream, h->ptr.data(), h->numel.data(), (int)h->names.size(), -1, 64, flat_grad, exp_avg, exp_avg_sq, lr,
+               beta1, beta2, eps, weight_decay, step);
+  LAUNCH_CHECK(h, "adamw_step");
   return DPTNAV_OK;
 }
 

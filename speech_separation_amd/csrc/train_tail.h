@@ -9,6 +9,9 @@
 // kernel that writes d loss / d prediction, and clip + AdamW read the flat gradient layout of dptnav_flat_offset().
 // Everything is summed in a fixed order (no float atomics): repeated steps are bit-identical.
 #pragma once
+#include <algorithm>
+#include <cmath>
+
 #include "common.h"
 #include "sisnr.h"
 
@@ -120,6 +123,13 @@ static __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restric
   f32x4* g4 = reinterpret_cast<f32x4*>(g);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) g4[i] = g4[i] * coef;
 }
+// both launches of the clip; partials: CLIP_PARTS doubles.  The caller has checked the arguments and checks the launch.
+static inline void launch_grad_clip(hipStream_t st, int num_cus, float* flat_grad, int64_t n_flat, float max_norm, double* partials,
+                                    float* norm_out) {
+  hipLaunchKernelGGL(sumsq_partials_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, flat_grad, n_flat / 4, partials);
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(num_cus * 2), dim3(256), 0, st, flat_grad, n_flat / 4, partials, CLIP_PARTS, max_norm,
+                     norm_out);
+}
 
 // ---- AdamW (torch.optim.AdamW single-tensor semantics, amsgrad off, maximize off) ---------------------------------------
 // grid (tensors of this launch, ADAMW_YBLOCKS); the parameters live in their own nn.Parameter storages (pointer per slot),
@@ -148,5 +158,37 @@ static __global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a, const fl
     v[o + i] = vi;
     const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;              // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
     p[i] = p[i] * decay - step_size * (mi / denom);                  // param.mul_(1 - lr wd); param.addcdiv_(exp_avg, denom, -step_size)
+  }
+}
+
+// One step on n parameters in batches of ADAMW_MAX; slot i's gradient and state start where the slots before it end, each
+// rounded up to `align` floats (a power of two).  skip_slot (-1: none) takes no step, no decay and no place in a batch --
+// what torch.optim.AdamW does with .grad None -- but keeps its place in the flat layout.  The caller has checked the
+// arguments and checks the launches.
+static inline void launch_adamw(hipStream_t st, const float* const* params, const int64_t* numels, int n, int skip_slot,
+                                int64_t align, const float* flat_grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
+                                double beta2, double eps, double weight_decay, int step) {
+  // hyper-parameters arrive as doubles (Python floats) and every derived constant is formed in double before it is
+  // rounded to fp32 once, as torch does: 1 - 0.999f would already be off by 1.3e-5 relative
+  const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
+  const float step_size = (float)(lr / bc1), inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
+  const float decay = (float)(1.0 - lr * weight_decay);
+  AdamwArgs a{};
+  int cnt = 0;
+  int64_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    if (i != skip_slot) {
+      a.param[cnt] = const_cast<float*>(params[i]);
+      a.off[cnt] = off;
+      a.n[cnt] = (int)numels[i];
+      ++cnt;
+    }
+    off += (numels[i] + align - 1) & ~(align - 1);
+    if (cnt == ADAMW_MAX || (i == n - 1 && cnt > 0)) {
+      hipLaunchKernelGGL(adamw_kernel, dim3(cnt, ADAMW_YBLOCKS), dim3(256), 0, st, a, flat_grad, exp_avg, exp_avg_sq, (float)beta1,
+                         (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, decay, step_size, inv_sqrt_bc2);
+      a = AdamwArgs{};
+      cnt = 0;
+    }
   }
 }

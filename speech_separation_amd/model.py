@@ -386,33 +386,37 @@ class _ConvTasNetTrainFn(torch.autograd.Function):
         return (None, None) + tuple(outs)
 
 
-class TrainableConvTasNet(ConvTasNet):
+class _TrainStep:
+    """What the Trainable* classes put in front of their inference class: the inference engine kept beside the training
+    one (`_engine`), the flat gradient of the last backward, and the forward that picks between the two."""
+
+    def __init__(self, N=512, L=16):
+        super().__init__(N, L)
+        self._infer_engine = None
+        self._flat_grad: Optional[torch.Tensor] = None
+        for p in self.parameters():
+            p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
+
+    def forward(self, mix, **batch):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
+        else:
+            s1, s2 = self._get_infer_engine(mix.device).forward(mix)
+        return {"s1_pred": s1, "s2_pred": s2}
+
+
+class TrainableConvTasNet(_TrainStep, ConvTasNet):
     """ConvTasNet with the training step on libdptnav (include/ctasnet_train.h): same constructor, state_dict keys and
     order, initialisation and parameter-count lines as ConvTasNet, and checkpoints load strictly either way.  Under
     torch.no_grad() the forward is ConvTasNet's inference engine (bitwise the same outputs); with grad enabled it records
     a tape and its backward computes every parameter's gradient in HIP.  `_get_engine` is the training engine, so
     optim.clip_grad_norm_ / optim.FusedAdamW / train.train_step take their fused paths; stock torch optimizers work too."""
 
-    def __init__(self, N=512, L=16):
-        super().__init__(N, L)
-        self._engine: Optional[ConvTasNetTrainEngine] = None
-        self._infer_engine: Optional[ConvTasNetEngine] = None
-        self._flat_grad: Optional[torch.Tensor] = None
-        for p in self.parameters():
-            p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
-
     def _get_engine(self, device: torch.device) -> ConvTasNetTrainEngine:
         return _bound_engine(self, "_engine", ConvTasNetTrainEngine, device)
 
     def _get_infer_engine(self, device: torch.device) -> ConvTasNetEngine:
         return _bound_engine(self, "_infer_engine", ConvTasNetEngine, device)
-
-    def forward(self, mix, **batch):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
-            return {"s1_pred": s1, "s2_pred": s2}
-        s1, s2 = self._get_infer_engine(mix.device).forward(mix)
-        return {"s1_pred": s1, "s2_pred": s2}
 
 
 class DeepConvTasNet(nn.Module):
@@ -464,7 +468,7 @@ class DeepConvTasNet(nn.Module):
     __str__ = _str_with_parameter_counts
 
 
-class TrainableDeepConvTasNet(DeepConvTasNet):
+class TrainableDeepConvTasNet(_TrainStep, DeepConvTasNet):
     """DeepConvTasNet with the training step on libdptnav (include/dctasnet_train.h), the counterpart of
     TrainableConvTasNet: same constructor, state_dict keys and order, initialisation and parameter-count lines as
     DeepConvTasNet, and checkpoints load strictly either way.  Under torch.no_grad() the forward is DeepConvTasNet's
@@ -472,26 +476,11 @@ class TrainableDeepConvTasNet(DeepConvTasNet):
     parameter's gradient in HIP.  decoder.deconv.weight is a parameter the reference's forward never reads: its .grad stays
     None, as after the reference's loss.backward(), and the fused clip / AdamW leave it out (torch.optim.AdamW skips it too)."""
 
-    def __init__(self, N=512, L=16):
-        super().__init__(N, L)
-        self._engine: Optional[DeepConvTasNetTrainEngine] = None
-        self._infer_engine: Optional[DeepConvTasNetEngine] = None
-        self._flat_grad: Optional[torch.Tensor] = None
-        for p in self.parameters():
-            p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
-
     def _get_engine(self, device: torch.device) -> DeepConvTasNetTrainEngine:
         return _bound_engine(self, "_engine", DeepConvTasNetTrainEngine, device)
 
     def _get_infer_engine(self, device: torch.device) -> DeepConvTasNetEngine:
         return _bound_engine(self, "_infer_engine", lambda dev: DeepConvTasNetEngine(dev, av=False), device)
-
-    def forward(self, mix, **batch):
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
-            return {"s1_pred": s1, "s2_pred": s2}
-        s1, s2 = self._get_infer_engine(mix.device).forward(mix)
-        return {"s1_pred": s1, "s2_pred": s2}
 
 
 class DeepAVConvTasNet(DeepConvTasNet):

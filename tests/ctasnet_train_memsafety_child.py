@@ -1,5 +1,7 @@
-"""TEST INFRASTRUCTURE: the memory-safety child of tests/test_gpu_convtasnet_train.py (as tests/ctasnet_memsafety_child.py is
-for the inference forward), covering cttrain_train_forward and cttrain_train_backward.  One mode per process:
+"""TEST INFRASTRUCTURE: the memory-safety child of tests/test_gpu_convtasnet_train.py and
+tests/test_gpu_deepconvtasnet_train.py (as tests/ctasnet_memsafety_child.py is for the inference forward), covering
+<model>_train_forward and <model>_train_backward for model cttrain (Conv-TasNet) or dcttrain (DeepConvTasNet).  One mode per
+process:
 
 mode  poison       the workspace, gradients and outputs the engine allocates start filled with 0xFF bytes
       guard_end    every buffer (weights, inputs, upstream gradients, workspace, gradients, outputs) ENDS flush against an
@@ -9,10 +11,11 @@ mode  poison       the workspace, gradients and outputs the engine allocates sta
 The call sequence (a big batch, then smaller shapes on the cached workspace) runs under test first, then with plain
 zero-filled buffers; predictions and gradients must be bit-identical (fixed reduction order everywhere).
 
-    python -m tests.ctasnet_train_memsafety_child <mode>
+    python -m tests.ctasnet_train_memsafety_child <mode> <model>
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 
@@ -23,16 +26,21 @@ if ROOT not in sys.path:
 import torch  # noqa: E402
 
 from oracle.convtasnet_stock import synthetic_convtasnet_weights  # noqa: E402
-from speech_separation_amd.engine import ConvTasNetTrainEngine  # noqa: E402
+from speech_separation_amd.engine import ConvTasNetTrainEngine, DeepConvTasNetTrainEngine  # noqa: E402
 from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
 from tests.ctasnet_memsafety_child import main  # noqa: E402  (the mode harness)
+from tests.deepconvtasnet_ref import synthetic_deepconvtasnet_weights  # noqa: E402
 
 SHAPES = [(3, 4001), (1, 400), (2, 17)]
+#: model -> (engine, its synthetic weights)
+MODELS = {"cttrain": (ConvTasNetTrainEngine, lambda: synthetic_convtasnet_weights(seed=3)),
+          "dcttrain": (DeepConvTasNetTrainEngine, lambda: synthetic_deepconvtasnet_weights(False, seed=3, slopes="distinct"))}
 
 
-def run(dev, alloc, place):
-    eng = ConvTasNetTrainEngine(dev, alloc=alloc)
-    sd = synthetic_convtasnet_weights(seed=3)
+def run(model, dev, alloc, place):
+    engine, weights = MODELS[model]
+    eng = engine(dev, alloc=alloc)
+    sd = weights()
     eng.bind({k: place(torch.from_numpy(v)) for k, v in sd.items()})
     eng.bind_grads()
     res = {}
@@ -51,6 +59,6 @@ def run(dev, alloc, place):
 
 
 if __name__ == "__main__":
-    rc = main(sys.argv[1], "cttrain", run)
+    rc = main(sys.argv[1], sys.argv[2], functools.partial(run, sys.argv[2]))
     sys.stdout.flush()
     os._exit(rc)      # no interpreter teardown with guard mappings still referenced by tensors

@@ -338,7 +338,7 @@ def test_memory_safety():
     (tests/ctasnet_train_memsafety_child.py): one child process per mode; each result equals the plain run."""
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for mode in ("poison", "guard_end", "guard_start"):
-        r = subprocess.run([sys.executable, "-m", "tests.ctasnet_train_memsafety_child", mode], cwd=ROOT, env=env,
+        r = subprocess.run([sys.executable, "-m", "tests.ctasnet_train_memsafety_child", mode, "cttrain"], cwd=ROOT, env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
         assert r.returncode == 0, f"{mode}: child ended with code {r.returncode}\n{r.stdout[-3000:]}"
         assert f"OK {mode} cttrain" in r.stdout, r.stdout[-3000:]

@@ -4,7 +4,7 @@ inference forward; gradients agree with fp64 autograd of the stock-PyTorch resta
 on the same PReLU branches as closely as the fp32 restatement does (check_gradients); the tape's values; the loss path,
 determinism, the fused and the stock training steps (decoder.deconv.weight, which the forward never reads, keeps .grad None
 and its value), no host synchronisation, the rejected paths and guard-page memory safety.  The B = 16 x 2 s gradient check
-and the timings live in tools/deepconvtasnet_train_bench.py."""
+and the timings live in tools/convtasnet_train_bench.py --model deepconvtasnet."""
 from __future__ import annotations
 
 import ctypes
@@ -269,10 +269,10 @@ def test_rejected_paths(dev, sd):
 
 def test_memory_safety():
     """Poisoned workspace, then every buffer flush against an unmapped page at its end, then at its start
-    (tests/deepctasnet_train_memsafety_child.py): one child process per mode; each result equals the plain run."""
+    (tests/ctasnet_train_memsafety_child.py): one child process per mode; each result equals the plain run."""
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for mode in ("poison", "guard_end", "guard_start"):
-        r = subprocess.run([sys.executable, "-m", "tests.deepctasnet_train_memsafety_child", mode], cwd=ROOT, env=env,
+        r = subprocess.run([sys.executable, "-m", "tests.ctasnet_train_memsafety_child", mode, "dcttrain"], cwd=ROOT, env=env,
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
         assert r.returncode == 0, f"{mode}: child ended with code {r.returncode}\n{r.stdout[-3000:]}"
         assert f"OK {mode} dcttrain" in r.stdout, r.stdout[-3000:]

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""Time one Conv-TasNet training step on the GPU (TrainableConvTasNet: forward, device PIT SI-SNR loss, backward, fused clip,
-FusedAdamW) at B = 1, 4, 16 x 32000 samples: STEPS steps between synchronisations, median of REPS, mixtures/s and the
-fraction of the fp32-MFMA FLOP bound (cttrain_flops_per_mixture, 157.3 TFLOP/s).  Baselines: the stock-PyTorch
-restatement (tests/convtasnet_train_ref.py) trained eagerly with torch.optim.AdamW on the same GPU and on 16 CPU threads.
+"""Time one training step of the Conv-TasNet family on the GPU (--model convtasnet: TrainableConvTasNet, deepconvtasnet:
+TrainableDeepConvTasNet; forward, device PIT SI-SNR loss, backward, fused clip, FusedAdamW) at B = 1, 4, 16 x 32000
+samples: STEPS steps between synchronisations, median of REPS, mixtures/s and the fraction of the fp32-MFMA FLOP bound
+(<prefix>_flops_per_mixture, 157.3 TFLOP/s).  Baselines: the model's stock-PyTorch restatement
+(tests/convtasnet_train_ref.py, tests/deepconvtasnet_train_ref.py) trained eagerly with torch.optim.AdamW on the same GPU
+in the same run, and at B = 1 on 16 CPU threads.
 --check: the B = 16 gradient against fp64 autograd of the restatement on the GPU, on this forward's PReLU branches (kept
-out of the test suite for time).
+out of the test suite for time), over every parameter the forward reads.
 
-Usage:  python tools/convtasnet_train_bench.py [--batches 1,4,16] [--steps 20] [--reps 5] [--check] [--json out.json]
+Usage:  python tools/convtasnet_train_bench.py [--model convtasnet] [--batches 1,4,16] [--steps 20] [--reps 5] [--check]
+                                               [--json out.json]
 """
 from __future__ import annotations
 
@@ -21,13 +24,18 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from oracle import convtasnet_stock as CT  # noqa: E402
-from speech_separation_amd import FusedAdamW, SiSNRWavLoss, TrainableConvTasNet  # noqa: E402
+from oracle.convtasnet_stock import synthetic_convtasnet_weights  # noqa: E402
+from speech_separation_amd import FusedAdamW, SiSNRWavLoss, TrainableConvTasNet, TrainableDeepConvTasNet  # noqa: E402
 from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
 from speech_separation_amd.train import train_step  # noqa: E402
-from tests import convtasnet_train_ref as R  # noqa: E402
+from tests import convtasnet_train_ref, deepconvtasnet_train_ref  # noqa: E402
+from tests.deepconvtasnet_ref import synthetic_deepconvtasnet_weights  # noqa: E402
 from tests.sisnr_ref import pit_sisnr_loss  # noqa: E402
 
+#: --model -> (module class, its stock restatement, synthetic weights)
+MODELS = {"convtasnet": (TrainableConvTasNet, convtasnet_train_ref, lambda: synthetic_convtasnet_weights(0)),
+          "deepconvtasnet": (TrainableDeepConvTasNet, deepconvtasnet_train_ref,
+                             lambda: synthetic_deepconvtasnet_weights(False, 0))}
 PEAK = 157.3e12
 T = 32000
 
@@ -52,6 +60,7 @@ def batch_of(B, dev):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=sorted(MODELS), default="convtasnet")
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
@@ -60,14 +69,15 @@ def main():
     ap.add_argument("--no-baselines", action="store_true", help="time the HIP step only (profiling runs)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    module, R, weights = MODELS[a.model]
     dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
-    sd = {k: torch.from_numpy(v) for k, v in CT.synthetic_convtasnet_weights(0).items()}
+    sd = {k: torch.from_numpy(v) for k, v in weights().items()}
     sync = lambda: torch.cuda.synchronize(dev)
-    res = {"T": T, "steps": a.steps, "reps": a.reps, "hip": {}, "stock_gpu": {}, "stock_cpu": {}}
+    res = {"model": a.model, "T": T, "steps": a.steps, "reps": a.reps, "hip": {}, "stock_gpu": {}, "stock_cpu": {}}
     for B in (int(b) for b in a.batches.split(",")):
-        m = TrainableConvTasNet()
+        m = module()
         m.load_state_dict(sd, strict=True)
         m = m.to(dev)
         opt, crit, batch = FusedAdamW(m.parameters(), lr=1e-3), SiSNRWavLoss(), batch_of(B, dev)
@@ -80,15 +90,21 @@ def main():
             m.zero_grad()
             out = m(mix=batch["mix"])
             masks = R.prelu_masks(m._engine, B, T)     # the fp64 / fp32 references follow this forward's PReLU branches
+            masks = {k: [t.to(dev) for t in v] if isinstance(v, list) else v.to(dev) for k, v in masks.items()}
             g = torch.Generator().manual_seed(1)
             d1, d2 = (torch.randn(B, T, generator=g).to(dev) for _ in range(2))
             torch.autograd.backward([out["s1_pred"], out["s2_pred"]], [d1, d2])
             sdd = {k: p.detach() for k, p in m.named_parameters()}
             g64 = R.grads(sdd, batch["mix"], d1, d2, torch.float64, masks)
             g32 = R.grads(sdd, batch["mix"], d1, d2, torch.float32, masks)
-            f = torch.cat([p.grad.double().reshape(-1) for _, p in m.named_parameters()])
-            f64 = torch.cat([g64[k].reshape(-1) for k, _ in m.named_parameters()])
-            f32 = torch.cat([g32[k].double().reshape(-1) for k, _ in m.named_parameters()])
+            keys = [k for k, p in m.named_parameters() if p.grad is not None]     # the deep model: all but decoder.deconv.weight
+            unused = [k for k, p in m.named_parameters() if p.grad is None]
+            assert unused == list(m._engine.no_grad_keys) and not any(g64[k].any() for k in unused)
+            grads = dict(m.named_parameters())
+            f = torch.cat([grads[k].grad.double().reshape(-1) for k in keys])
+            f64 = torch.cat([g64[k].reshape(-1) for k in keys])
+            f32 = torch.cat([g32[k].double().reshape(-1) for k in keys])
+            del g64, g32
             res["check_b16"] = {"ratio": float((f - f64).norm() / f64.norm()), "fp32_ratio": float((f32 - f64).norm() / f64.norm())}
             print("B=16 gradient vs fp64:", res["check_b16"], flush=True)
         del m, opt
