@@ -3,16 +3,17 @@ from .spec import DPRNN_AUDIO, DPRNN_AV, DPTN_AUDIO, DPTN_AV, DPTN_MASK, DPTNCon
 
 __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "DPRNN_AV", "DPRNNEncDec", "DPRNNAVEncDec", "state_dict_spec", "synthetic_state_dict", "synthetic_inputs",
            "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
-           "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss"]
+           "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
     if name in ("DptnEngine", "ConvTasNetEngine", "ConvTasNetTrainEngine", "DeepConvTasNetEngine",
-                "DeepConvTasNetTrainEngine"):
+                "DeepConvTasNetTrainEngine", "DeepAVConvTasNetTrainEngine"):
         from . import engine
         return getattr(engine, name)
     if name in ("DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "DPRNNEncDec", "DPRNNAVEncDec", "ConvTasNet",
-                "TrainableConvTasNet", "DeepConvTasNet", "DeepAVConvTasNet", "TrainableDeepConvTasNet"):
+                "TrainableConvTasNet", "DeepConvTasNet", "DeepAVConvTasNet", "TrainableDeepConvTasNet",
+                "TrainableDeepAVConvTasNet"):
         from . import model
         return getattr(model, name)
     if name in ("FusedAdamW", "clip_grad_norm_"):

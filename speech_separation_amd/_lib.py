@@ -77,6 +77,7 @@ CTASNET_ABI_VERSION = 1
 DCTASNET_ABI_VERSION = 1
 CTTRAIN_ABI_VERSION = 1
 DCTTRAIN_ABI_VERSION = 1
+DAVTRAIN_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -102,8 +103,10 @@ def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), m
     return {f"{prefix}_{k}": v for k, v in d.items()}
 
 
-def _train_symbols(prefix, create_extra=()):
-    """The training boundary of a Conv-TasNet family member; `create_extra` extends the argument list of create."""
+def _train_symbols(prefix, create_extra=(), shape_extra=(), forward_in=()):
+    """The training boundary of a Conv-TasNet family member; `create_extra` extends the argument list of create,
+    `shape_extra` follows (B, T) wherever a shape is passed, `forward_in` follows the mixture in train_forward /
+    train_backward."""
     d = {
         "abi_version": (_i, []),
         "create": (_i, [C.POINTER(_vp), *create_extra]),
@@ -118,10 +121,10 @@ def _train_symbols(prefix, create_extra=()):
         "flat_numel": (_i64, [_vp]),
         "frames": (_i64, [_i64]),
         "out_len": (_i64, [_i64]),
-        "workspace_bytes": (_sz, [_vp, _i, _i64]),
-        "train_forward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-        "train_backward": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp, _sz, _vp]),
-        "tape_offset": (_i64, [_vp, _i, _i64, _i, _i]),
+        "workspace_bytes": (_sz, [_vp, _i, _i64, *shape_extra]),
+        "train_forward": (_i, [_vp, _fp, *forward_in, _i, _i64, *shape_extra, _fp, _fp, _vp, _sz, _vp]),
+        "train_backward": (_i, [_vp, _fp, *forward_in, _i, _i64, *shape_extra, _fp, _fp, _vp, _sz, _vp]),
+        "tape_offset": (_i64, [_vp, _i, _i64, *shape_extra, _i, _i]),
         "clip_scratch_bytes": (_sz, [_vp]),
         "grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
         "adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
@@ -131,7 +134,7 @@ def _train_symbols(prefix, create_extra=()):
     return {f"{prefix}_{k}": v for k, v in d.items()}
 
 
-# The four tables below are name -> (restype, argtypes), as SYMBOLS, for entry points of the same shared object.
+# The five tables below are name -> (restype, argtypes), as SYMBOLS, for entry points of the same shared object.
 #: every symbol include/ctasnet.h declares (Conv-TasNet forward)
 CTASNET_SYMBOLS = _infer_symbols("ctasnet")
 #: every symbol include/dctasnet.h declares (deep Conv-TasNet forward): create takes av, workspace_bytes and forward take Tv,
@@ -142,6 +145,9 @@ DCTASNET_SYMBOLS = _infer_symbols("dctasnet", create_extra=[_i], workspace_extra
 CTTRAIN_SYMBOLS = _train_symbols("cttrain")
 #: every symbol include/dctasnet_train.h declares (deep Conv-TasNet training step): create takes av
 DCTTRAIN_SYMBOLS = _train_symbols("dcttrain", create_extra=[_i])
+#: every symbol include/davctasnet_train.h declares (deep audio-visual Conv-TasNet training step): every shape carries Tv and
+#: the two video streams follow the mixture
+DAVTRAIN_SYMBOLS = _train_symbols("davtrain", shape_extra=[_i], forward_in=[_fp, _fp])
 
 _lib: Optional[C.CDLL] = None
 
@@ -161,7 +167,8 @@ def load() -> C.CDLL:
             f"g.build()'` at the repo root).  speech_separation_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
-                      + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())):
+                      + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
+                              + list(DAVTRAIN_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -172,7 +179,8 @@ def load() -> C.CDLL:
                             (lib.ctasnet_abi_version, CTASNET_ABI_VERSION, "ctasnet"),
                             (lib.dctasnet_abi_version, DCTASNET_ABI_VERSION, "dctasnet"),
                             (lib.cttrain_abi_version, CTTRAIN_ABI_VERSION, "cttrain"),
-                            (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain")):
+                            (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain"),
+                            (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

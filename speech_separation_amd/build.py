@@ -36,14 +36,14 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            # mask_tail.hip: the masked tail of DPTNEncDec (plain VALU, no MFMA)
            "mask_tail.hip": [],
            # ctasnet.hip (Conv-TasNet forward), deepctasnet.hip (DeepConvTasNet / DeepAVConvTasNet forward), ctasnet_train.hip
-           # (Conv-TasNet training step), deepctasnet_train.hip (DeepConvTasNet training step): each instantiates the GEMM
-           # engine
+           # (Conv-TasNet training step), deepctasnet_train.hip (DeepConvTasNet and DeepAVConvTasNet training steps): each
+           # instantiates the GEMM engine
            "ctasnet.hip": _GEMM_ENGINE_FLAGS, "deepctasnet.hip": _GEMM_ENGINE_FLAGS, "ctasnet_train.hip": _GEMM_ENGINE_FLAGS,
            "deepctasnet_train.hip": _GEMM_ENGINE_FLAGS}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h")]
 
 
 def source_digest() -> str:

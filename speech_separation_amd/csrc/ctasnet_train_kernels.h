@@ -761,8 +761,9 @@ struct WsPtr {
 
 // What *_train_forward (o1, o2: the predictions) and *_train_backward (their gradients; needs the gradients bound) start
 // with: the checks, the unit's plan and the workspace behind it.
-template <class Plan>
-int train_prologue(CtTrainHandle* c, int (*make_plan)(CtHandle*, int, int64_t, Plan&), bool backward, const void* mix,
+// make_plan(c, B, T, p): the unit's plan (a function, or a callable that carries what else the plan depends on).
+template <class Plan, class MakePlan>
+int train_prologue(CtTrainHandle* c, MakePlan make_plan, bool backward, const void* mix,
                    const void* o1, const void* o2, int B, int64_t T, void* ws, size_t ws_bytes, Plan& p, WsPtr& at) {
   if (!c) return CTASNET_ERR_INVALID;
   if (!c->bound) return c->fail(CTASNET_ERR_WEIGHTS, "weights not bound (%s_bind_weights)", c->prefix);

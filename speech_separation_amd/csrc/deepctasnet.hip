@@ -1,5 +1,6 @@
 // deepctasnet.hip -- DeepConvTasNet / DeepAVConvTasNet inference forward (src/model/deepconvtasnet.py,
-// src/model/deepavconvtasnet.py) for gfx950: kernels, handle and the extern "C" boundary declared in include/dctasnet.h.
+// src/model/deepavconvtasnet.py) for gfx950: handle and the extern "C" boundary declared in include/dctasnet.h; the kernels
+// are in deepctasnet_kernels.h, shared with the training step.
 //
 // The Separator is Conv-TasNet's, unchanged (ctasnet_kernels.h).  New here are the deep encoder / decoder -- eight dense
 // dilated k = 3 convs 512 -> 512, about 65 % of the FLOPs -- and the audio-visual head.
@@ -31,93 +32,6 @@ static_assert(DCTASNET_OK == CTASNET_OK && DCTASNET_ERR_INVALID == CTASNET_ERR_I
 
 namespace {
 thread_local std::string g_create_error;
-
-// ------------------------------------------------------------------------------------------------
-// video head (deepavconvtasnet.py:140-151)
-// (1) vcat[b*Tv + t][s*256 + j] = bias[j] + sum_k Wvc[j][k] e_s[b][k][t]: one workgroup per (b, 8 frames), both speakers'
-//     embedding columns staged in LDS, thread j owns output column j
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dctasnet_video_linear_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
-                                                                    const float* __restrict__ Wvc, const float* __restrict__ bvc,
-                                                                    int Tv, float* __restrict__ vcat) {
-  __shared__ __attribute__((aligned(16))) float es[2][DC_VT][CT_N];
-  const int b = blockIdx.y, t0 = blockIdx.x * DC_VT, tid = threadIdx.x;
-  for (int i = tid; i < 2 * DC_VT * CT_N; i += 256) {          // t fastest: coalesced along the embedding's time axis
-    const int tt = i % DC_VT, k = (i / DC_VT) % CT_N, s = i / (DC_VT * CT_N);
-    const float* e = s ? e2 : e1;
-    es[s][tt][k] = t0 + tt < Tv ? e[((int64_t)b * CT_N + k) * Tv + t0 + tt] : 0.f;
-  }
-  __syncthreads();
-  const int j = tid;
-  const float bj = bvc[j];
-  float acc[2][DC_VT];
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int tt = 0; tt < DC_VT; ++tt) acc[s][tt] = bj;
-  const float* wr = Wvc + (int64_t)j * CT_N;
-  for (int k4 = 0; k4 < CT_N / 4; ++k4) {
-    const float4 w = *reinterpret_cast<const float4*>(wr + 4 * k4);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int tt = 0; tt < DC_VT; ++tt) {
-        const float4 x = *reinterpret_cast<const float4*>(&es[s][tt][4 * k4]);
-        acc[s][tt] = fmaf(w.w, x.w, fmaf(w.z, x.z, fmaf(w.y, x.y, fmaf(w.x, x.x, acc[s][tt]))));
-      }
-  }
-#pragma unroll
-  for (int tt = 0; tt < DC_VT; ++tt)
-    if (t0 + tt < Tv) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) vcat[((int64_t)b * Tv + t0 + tt) * CT_N + s * DC_HV + j] = acc[s][tt];
-    }
-}
-
-// (2) vid[b*F + f] = LayerNorm_512(interpolate(vcat[b], Tv -> F, linear, align_corners=False)[f]): one wave per frame,
-//     lane: channels 4 lane .. +3 and 256 + 4 lane .. +3.  Interpolation arithmetic as the DPTN-AV head (headtail.h).
-__global__ __launch_bounds__(256) void dctasnet_video_frames_kernel(const float* __restrict__ vcat, const float* __restrict__ g,
-                                                                    const float* __restrict__ be, int F, int Tv, int64_t M,
-                                                                    float* __restrict__ vid) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
-  if (r >= M) return;                                          // wave-uniform
-  const int64_t b = r / F;
-  const int f = (int)(r - b * F);
-  const float scale = (float)Tv / (float)F;
-  float src = ((float)f + 0.5f) * scale - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  const int i0 = (int)floorf(src);
-  const int i1 = i0 + 1 < Tv ? i0 + 1 : Tv - 1;
-  const float lam = src - (float)i0;
-  float u[8];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int ch = h * 256 + 4 * lane;
-    const float4 a = *reinterpret_cast<const float4*>(vcat + (b * Tv + i0) * CT_N + ch);
-    const float4 c = *reinterpret_cast<const float4*>(vcat + (b * Tv + i1) * CT_N + ch);
-    u[4 * h + 0] = a.x * (1.f - lam) + c.x * lam;
-    u[4 * h + 1] = a.y * (1.f - lam) + c.y * lam;
-    u[4 * h + 2] = a.z * (1.f - lam) + c.z * lam;
-    u[4 * h + 3] = a.w * (1.f - lam) + c.w * lam;
-  }
-  const float mu = wave_sum(((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7]))) * (1.0f / CT_N);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    u[i] -= mu;
-    q += u[i] * u[i];
-  }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / CT_N) + 1e-5f);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int ch = h * 256 + 4 * lane;
-    const float4 ga = *reinterpret_cast<const float4*>(g + ch), bb = *reinterpret_cast<const float4*>(be + ch);
-    *reinterpret_cast<float4*>(vid + r * CT_N + ch) =
-        make_float4(u[4 * h] * rstd * ga.x + bb.x, u[4 * h + 1] * rstd * ga.y + bb.y, u[4 * h + 2] * rstd * ga.z + bb.z,
-                    u[4 * h + 3] * rstd * ga.w + bb.w);
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // host side

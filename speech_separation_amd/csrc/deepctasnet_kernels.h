@@ -1,6 +1,6 @@
 // deepctasnet_kernels.h -- what the deep Conv-TasNet units share (deepctasnet.hip: DeepConvTasNet / DeepAVConvTasNet
-// forward, deepctasnet_train.hip: TrainableDeepConvTasNet): the weight table, the fragment-order pack of the eight dense
-// k = 3 convs, their engine hooks and launch_dense.  Everything sits in an anonymous namespace, so each including unit
+// forward, deepctasnet_train.hip: TrainableDeepConvTasNet / TrainableDeepAVConvTasNet): the weight table, the fragment-order
+// pack of the eight dense k = 3 convs, their engine hooks and launch_dense, and the two kernels of the audio-visual head.  Everything sits in an anonymous namespace, so each including unit
 // compiles its own copy.
 //
 // TAPE (the training forward): a dense conv stores its pre-activation z (the input of its PReLU) where the inference mode
@@ -143,6 +143,102 @@ struct EpiTapConvT {
     *reinterpret_cast<float4*>((TAPE && tap == 2 ? act : out) + r * CT_N + col) = v;
   }
 };
+
+// ------------------------------------------------------------------------------------------------
+// video head (deepavconvtasnet.py:140-151)
+// (1) vcat[b*Tv + t][s*256 + j] = bias[j] + sum_k Wvc[j][k] e_s[b][k][t]: one workgroup per (b, 8 frames), both speakers'
+//     embedding columns staged in LDS, thread j owns output column j
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dctasnet_video_linear_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
+                                                                    const float* __restrict__ Wvc, const float* __restrict__ bvc,
+                                                                    int Tv, float* __restrict__ vcat) {
+  __shared__ __attribute__((aligned(16))) float es[2][DC_VT][CT_N];
+  const int b = blockIdx.y, t0 = blockIdx.x * DC_VT, tid = threadIdx.x;
+  for (int i = tid; i < 2 * DC_VT * CT_N; i += 256) {          // t fastest: coalesced along the embedding's time axis
+    const int tt = i % DC_VT, k = (i / DC_VT) % CT_N, s = i / (DC_VT * CT_N);
+    const float* e = s ? e2 : e1;
+    es[s][tt][k] = t0 + tt < Tv ? e[((int64_t)b * CT_N + k) * Tv + t0 + tt] : 0.f;
+  }
+  __syncthreads();
+  const int j = tid;
+  const float bj = bvc[j];
+  float acc[2][DC_VT];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int tt = 0; tt < DC_VT; ++tt) acc[s][tt] = bj;
+  const float* wr = Wvc + (int64_t)j * CT_N;
+  for (int k4 = 0; k4 < CT_N / 4; ++k4) {
+    const float4 w = *reinterpret_cast<const float4*>(wr + 4 * k4);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int tt = 0; tt < DC_VT; ++tt) {
+        const float4 x = *reinterpret_cast<const float4*>(&es[s][tt][4 * k4]);
+        acc[s][tt] = fmaf(w.w, x.w, fmaf(w.z, x.z, fmaf(w.y, x.y, fmaf(w.x, x.x, acc[s][tt]))));
+      }
+  }
+#pragma unroll
+  for (int tt = 0; tt < DC_VT; ++tt)
+    if (t0 + tt < Tv) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) vcat[((int64_t)b * Tv + t0 + tt) * CT_N + s * DC_HV + j] = acc[s][tt];
+    }
+}
+
+// frame f of F reads rows i0, i1 of the Tv video rows with weights 1 - lam, lam (F.interpolate, linear, align_corners=False).
+// One text for the forward and for the backward's recomputation (deepctasnet_train.hip): the same float operations.
+struct VideoSrc { int i0, i1; float lam; };
+DEV VideoSrc video_src(int f, int F, int Tv) {
+  const float scale = (float)Tv / (float)F;
+  float src = ((float)f + 0.5f) * scale - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  const int i0 = (int)floorf(src);
+  const int i1 = i0 + 1 < Tv ? i0 + 1 : Tv - 1;
+  return VideoSrc{i0, i1, src - (float)i0};
+}
+
+// (2) vid[b*F + f] = LayerNorm_512(interpolate(vcat[b], Tv -> F, linear, align_corners=False)[f]): one wave per frame,
+//     lane: channels 4 lane .. +3 and 256 + 4 lane .. +3.  Interpolation arithmetic as the DPTN-AV head (headtail.h).
+__global__ __launch_bounds__(256) void dctasnet_video_frames_kernel(const float* __restrict__ vcat, const float* __restrict__ g,
+                                                                    const float* __restrict__ be, int F, int Tv, int64_t M,
+                                                                    float* __restrict__ vid) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  if (r >= M) return;                                          // wave-uniform
+  const int64_t b = r / F;
+  const int f = (int)(r - b * F);
+  const VideoSrc vs = video_src(f, F, Tv);
+  const int i0 = vs.i0, i1 = vs.i1;
+  const float lam = vs.lam;
+  float u[8];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ch = h * 256 + 4 * lane;
+    const float4 a = *reinterpret_cast<const float4*>(vcat + (b * Tv + i0) * CT_N + ch);
+    const float4 c = *reinterpret_cast<const float4*>(vcat + (b * Tv + i1) * CT_N + ch);
+    u[4 * h + 0] = a.x * (1.f - lam) + c.x * lam;
+    u[4 * h + 1] = a.y * (1.f - lam) + c.y * lam;
+    u[4 * h + 2] = a.z * (1.f - lam) + c.z * lam;
+    u[4 * h + 3] = a.w * (1.f - lam) + c.w * lam;
+  }
+  const float mu = wave_sum(((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7]))) * (1.0f / CT_N);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    u[i] -= mu;
+    q += u[i] * u[i];
+  }
+  const float rstd = rsqrtf(wave_sum(q) * (1.0f / CT_N) + 1e-5f);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ch = h * 256 + 4 * lane;
+    const float4 ga = *reinterpret_cast<const float4*>(g + ch), bb = *reinterpret_cast<const float4*>(be + ch);
+    *reinterpret_cast<float4*>(vid + r * CT_N + ch) =
+        make_float4(u[4 * h] * rstd * ga.x + bb.x, u[4 * h + 1] * rstd * ga.y + bb.y, u[4 * h + 2] * rstd * ga.z + bb.z,
+                    u[4 * h + 3] * rstd * ga.w + bb.w);
+  }
+}
 
 // the audio-only table (deepconvtasnet.py), then the audio-visual head's four tensors (deepavconvtasnet.py) if av
 inline void add_deepconvtasnet_names(CtHandle* c, bool av) {

@@ -1,5 +1,7 @@
-// deepctasnet_train.hip -- DeepConvTasNet training step (src/model/deepconvtasnet.py forward + its autograd backward) for
-// gfx950: handle and the extern "C" boundary declared in include/dctasnet_train.h.
+// deepctasnet_train.hip -- DeepConvTasNet and DeepAVConvTasNet training steps (src/model/deepconvtasnet.py,
+// src/model/deepavconvtasnet.py: forward + autograd backward) for gfx950: handles and the extern "C" boundaries declared in
+// include/dctasnet_train.h (dcttrain_*, audio only) and include/davctasnet_train.h (davtrain_*, audio-visual).  One plan, one
+// forward body and one backward body serve both; the audio-visual handle takes the `av` branches.
 //
 // Training forward: the launch sequence of deepctasnet.hip in its TAPE mode (deepctasnet_kernels.h, ctasnet_kernels.h: one
 // text for both), so the predictions are bitwise those of dctasnet_forward.  On top of the Separator's tape
@@ -18,7 +20,19 @@
 // at the start of every backward from the weights as they are then.  No atomics: every partial goes to a slab and is
 // summed in a fixed order, so two backward calls on one tape give bitwise-identical gradients.
 // decoder.deconv.weight is never read by the reference's forward: its gradient buffer is never written and
-// dcttrain_adamw_step leaves the weight alone.
+// *_adamw_step leaves the weight alone.
+//
+// Audio-visual head (deepavconvtasnet.py:140-155).  Forward: the two video launches of deepctasnet.hip run before the
+// encoder, vcat [B Tv][512] stays on the tape and the video rows sit in scratch until the last dense encoder pass adds
+// them in its epilogue and writes the GlobalNorm partials of the fused tensor; the tape's enc is the fused tensor.
+// Backward: d fused = the Separator backward's d enc is also d vid.  The encoder's PReLU backward works in place, so the
+// video backward runs between launch_separator_backward and encoder layer 3 and reads d fused before it is overwritten:
+// (1) one workgroup per (b, t) walks the frames that interpolate from video row t in ascending f, recomputes the
+// interpolated row, mu and rstd from vcat with the forward's float operations, forms the LayerNorm's data gradient and
+// gathers its weighted sum into d vcat[b, t] (no scatter); the frames whose i0 is t also give the workgroup's partial of
+// d gamma, d beta (each frame has one such t), summed afterwards in (b, t) order; (2) the Linear's d W, d b as register
+// tiles over fixed row chunks of d vcat, the embeddings staged through LDS along their time axis, partials summed in chunk
+// order.  Nothing of size [M][512] is written for the head; the embeddings get no gradient.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +41,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/davctasnet_train.h"
 #include "../../include/dctasnet_train.h"
 #include "ctasnet_train_kernels.h"
 #include "deepctasnet_kernels.h"
@@ -35,12 +50,22 @@ static_assert(DCTTRAIN_OK == CTASNET_OK && DCTTRAIN_ERR_INVALID == CTASNET_ERR_I
                   DCTTRAIN_ERR_WORKSPACE == CTASNET_ERR_WORKSPACE && DCTTRAIN_ERR_WEIGHTS == CTASNET_ERR_WEIGHTS &&
                   DCTTRAIN_ERR_HIP == CTASNET_ERR_HIP,
               "the shared Conv-TasNet code returns CTASNET_* codes");
+static_assert(DAVTRAIN_OK == CTASNET_OK && DAVTRAIN_ERR_INVALID == CTASNET_ERR_INVALID &&
+                  DAVTRAIN_ERR_WORKSPACE == CTASNET_ERR_WORKSPACE && DAVTRAIN_ERR_WEIGHTS == CTASNET_ERR_WEIGHTS &&
+                  DAVTRAIN_ERR_HIP == CTASNET_ERR_HIP,
+              "the shared Conv-TasNet code returns CTASNET_* codes");
 
 namespace {
 
 constexpr int DCT_G_W = 256;                        // workgroups of a dense weight-gradient launch (at most): one per CU
 constexpr int DCT_WN = CT_N, DCT_WK = 128;          // its tile: dW[512][128 columns of one tap]
 constexpr int DCT_UNUSED = DC_DEC0 + 14;            // decoder.deconv.weight
+constexpr int DAV_KT = 32;                          // video Linear backward: input channels (columns of dW) per workgroup
+constexpr int DAV_TT = 64;                          // video frames of one mixture per row chunk
+constexpr int DAV_LD = DAV_KT + 4;                  // LDS row stride of the staged embeddings (float4 reads stay aligned)
+constexpr int DAV_G_R = 64;                         // row-chunk workgroups (at most): one partial dW [256][512] each
+static_assert((size_t)DAV_G_R * DC_HV * CT_N <= (size_t)DCT_G_W * DCT_WN * DCT_WK, "the dense wgrad slab holds the Linear's partials");
+static_assert(DAV_G_R * DC_HV <= CTT_G_C * 2 * CT_N, "the column-sum slab holds the Linear's bias partials");
 
 thread_local std::string g_create_error;
 
@@ -120,8 +145,157 @@ struct ALoadTapCols {
   }
 };
 
+// ------------------------------------------------------------------------------------------------
+// audio-visual head, backward
+// ------------------------------------------------------------------------------------------------
+// first frame f of [0, F) whose i0 is >= t, F if there is none: video_src's i0 does not decrease with f
+DEV int video_first_frame(int t, int F, int Tv) {
+  int lo = 0, hi = F;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (video_src(mid, F, Tv).i0 >= t) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// LayerNorm(512) and interpolation backward.  Workgroup (t, b): the frames with i0 in {t - 1, t} are the ones that read
+// video row t (i1 = min(i0 + 1, Tv - 1)), one contiguous range.  Wave w takes frames f_lo + w, f_lo + w + 4, ... in
+// ascending order (lane: channels 4 lane .. +3 and 256 + 4 lane .. +3, as dctasnet_video_frames_kernel, whose operations
+// give u, mu, rstd again); the four waves are then summed in wave order.  With dy = dfused[b F + f], g = dy gamma,
+// xhat = (u - mu) rstd:  du = rstd (g - mean(g) - xhat mean(g xhat)),  dvcat[b Tv + t] = sum_f ((1 - lam)[i0 = t] +
+// lam [i1 = t]) du,  vslab[b Tv + t] = (sum dy xhat | sum dy) over the frames with i0 = t.  An empty range writes zeros.
+__global__ __launch_bounds__(256) void davtrain_video_ln_bwd_kernel(const float* __restrict__ dfused, const float* __restrict__ vcat,
+                                                                    const float* __restrict__ g, int F, int Tv,
+                                                                    float* __restrict__ dvcat, float* __restrict__ vslab) {
+  __shared__ __attribute__((aligned(16))) float red[4][3][CT_N];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int t = blockIdx.x;
+  const int64_t b = blockIdx.y;
+  const int f_lo = video_first_frame(t - 1, F, Tv), f_hi = video_first_frame(t + 1, F, Tv);
+  float4 ga[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) ga[h] = *reinterpret_cast<const float4*>(g + h * 256 + 4 * lane);
+  const float gam[8] = {ga[0].x, ga[0].y, ga[0].z, ga[0].w, ga[1].x, ga[1].y, ga[1].z, ga[1].w};
+  float acc[8], sg[8], sb[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = sg[i] = sb[i] = 0.f;
+  for (int f = f_lo + wave; f < f_hi; f += 4) {              // wave-uniform
+    const VideoSrc vs = video_src(f, F, Tv);
+    const int i0 = vs.i0, i1 = vs.i1;
+    const float lam = vs.lam;
+    float u[8], dy[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int ch = h * 256 + 4 * lane;
+      const float4 a = *reinterpret_cast<const float4*>(vcat + (b * Tv + i0) * CT_N + ch);
+      const float4 c = *reinterpret_cast<const float4*>(vcat + (b * Tv + i1) * CT_N + ch);
+      const float4 d = *reinterpret_cast<const float4*>(dfused + (b * F + f) * CT_N + ch);
+      u[4 * h + 0] = a.x * (1.f - lam) + c.x * lam;
+      u[4 * h + 1] = a.y * (1.f - lam) + c.y * lam;
+      u[4 * h + 2] = a.z * (1.f - lam) + c.z * lam;
+      u[4 * h + 3] = a.w * (1.f - lam) + c.w * lam;
+      dy[4 * h + 0] = d.x; dy[4 * h + 1] = d.y; dy[4 * h + 2] = d.z; dy[4 * h + 3] = d.w;
+    }
+    const float mu = wave_sum(((u[0] + u[1]) + (u[2] + u[3])) + ((u[4] + u[5]) + (u[6] + u[7]))) * (1.0f / CT_N);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      u[i] -= mu;
+      q += u[i] * u[i];
+    }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / CT_N) + 1e-5f);
+    float gg[8], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      u[i] *= rstd;                                          // xhat
+      gg[i] = dy[i] * gam[i];
+      s1 += gg[i];
+      s2 = fmaf(gg[i], u[i], s2);
+    }
+    const float m1 = wave_sum(s1) * (1.0f / CT_N), m2 = wave_sum(s2) * (1.0f / CT_N);
+    const float w0 = i0 == t ? 1.f - lam : 0.f, w1 = i1 == t ? lam : 0.f;
+    const bool own = i0 == t;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float du = rstd * (gg[i] - m1 - u[i] * m2);
+      acc[i] = fmaf(w1, du, fmaf(w0, du, acc[i]));
+      if (own) {
+        sg[i] = fmaf(dy[i], u[i], sg[i]);
+        sb[i] += dy[i];
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int ch = h * 256 + 4 * lane;
+    *reinterpret_cast<float4*>(&red[wave][0][ch]) = make_float4(acc[4 * h], acc[4 * h + 1], acc[4 * h + 2], acc[4 * h + 3]);
+    *reinterpret_cast<float4*>(&red[wave][1][ch]) = make_float4(sg[4 * h], sg[4 * h + 1], sg[4 * h + 2], sg[4 * h + 3]);
+    *reinterpret_cast<float4*>(&red[wave][2][ch]) = make_float4(sb[4 * h], sb[4 * h + 1], sb[4 * h + 2], sb[4 * h + 3]);
+  }
+  __syncthreads();
+  const int64_t row = b * Tv + t;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = tid + 256 * h;
+    float s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = ((red[0][k][c] + red[1][k][c]) + red[2][k][c]) + red[3][k][c];
+    dvcat[row * CT_N + c] = s[0];
+    vslab[row * 2 * CT_N + c] = s[1];
+    vslab[row * 2 * CT_N + CT_N + c] = s[2];
+  }
+}
+
+// Linear(512 -> 256) backward, shared by the two speakers: dW[j][k] = sum_{s, b, t} dvcat[b Tv + t][256 s + j] e_s[b][k][t],
+// d b[j] = sum_{s, b, t} dvcat[b Tv + t][256 s + j].  Workgroup (x, y): columns k0 = 32 x .. +31 of dW over the row chunks
+// (b, 64 frames) y, y + gridDim.y, ... in that order; thread j owns row j.  Both speakers' embedding tile is staged in LDS
+// with t fastest on the global side (coalesced along the embedding's time axis, as dctasnet_video_linear_kernel).
+// Partials: slab[y][256][512] and, from the x = 0 workgroups, bslab[y][256].
+__global__ __launch_bounds__(256) void davtrain_video_linear_bwd_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
+                                                                        const float* __restrict__ dvcat, int B, int Tv, int nchunk,
+                                                                        float* __restrict__ slab, float* __restrict__ bslab) {
+  __shared__ __attribute__((aligned(16))) float es[2][DAV_TT][DAV_LD];
+  const int j = threadIdx.x, k0 = blockIdx.x * DAV_KT;
+  float acc[DAV_KT];
+#pragma unroll
+  for (int i = 0; i < DAV_KT; ++i) acc[i] = 0.f;
+  float bs = 0.f;
+  for (int rc = blockIdx.y; rc < B * nchunk; rc += gridDim.y) {
+    const int64_t b = rc / nchunk;
+    const int t0 = (rc % nchunk) * DAV_TT;
+    __syncthreads();
+    for (int i = j; i < 2 * DAV_KT * DAV_TT; i += 256) {
+      const int tt = i % DAV_TT, k = (i / DAV_TT) % DAV_KT, s = i / (DAV_TT * DAV_KT);
+      const float* e = s ? e2 : e1;
+      es[s][tt][k] = t0 + tt < Tv ? e[(b * CT_N + k0 + k) * Tv + t0 + tt] : 0.f;
+    }
+    __syncthreads();
+    const int nt = Tv - t0 < DAV_TT ? Tv - t0 : DAV_TT;
+    for (int tt = 0; tt < nt; ++tt) {
+      const float* d = dvcat + (b * Tv + t0 + tt) * CT_N;
+      const float d0 = d[j], d1 = d[DC_HV + j];
+      bs += d0 + d1;
+#pragma unroll
+      for (int k4 = 0; k4 < DAV_KT / 4; ++k4) {
+        const float4 x0 = *reinterpret_cast<const float4*>(&es[0][tt][4 * k4]);
+        const float4 x1 = *reinterpret_cast<const float4*>(&es[1][tt][4 * k4]);
+        acc[4 * k4 + 0] = fmaf(d1, x1.x, fmaf(d0, x0.x, acc[4 * k4 + 0]));
+        acc[4 * k4 + 1] = fmaf(d1, x1.y, fmaf(d0, x0.y, acc[4 * k4 + 1]));
+        acc[4 * k4 + 2] = fmaf(d1, x1.z, fmaf(d0, x0.z, acc[4 * k4 + 2]));
+        acc[4 * k4 + 3] = fmaf(d1, x1.w, fmaf(d0, x0.w, acc[4 * k4 + 3]));
+      }
+    }
+  }
+  float* out = slab + ((size_t)blockIdx.y * DC_HV + j) * CT_N + k0;
+#pragma unroll
+  for (int k4 = 0; k4 < DAV_KT / 4; ++k4)
+    *reinterpret_cast<float4*>(out + 4 * k4) = make_float4(acc[4 * k4], acc[4 * k4 + 1], acc[4 * k4 + 2], acc[4 * k4 + 3]);
+  if (blockIdx.x == 0) bslab[(size_t)blockIdx.y * DC_HV + j] = bs;
+}
+
 struct Plan : TrainPlanBase {
   size_t off_wpk, off_c0, off_ez, off_dz, off_ga, off_gb;
+  size_t off_dvcat, off_vslab, off_vcat;      // audio-visual only (empty otherwise)
 };
 
 }  // namespace
@@ -129,15 +303,37 @@ struct Plan : TrainPlanBase {
 static_assert(DCTTRAIN_TAPE_V1 == SEP_TAPE_V1 && DCTTRAIN_TAPE_U == SEP_TAPE_U && DCTTRAIN_TAPE_SKIP == SEP_TAPE_SKIP,
               "sep_tape_offset takes the header's tape kinds");
 
-struct dcttrain_ctx : CtTrainHandle {
-  dcttrain_ctx() : CtTrainHandle("dcttrain", DCT_UNUSED) {}
+static_assert(DAVTRAIN_TAPE_V1 == SEP_TAPE_V1 && DAVTRAIN_TAPE_U == SEP_TAPE_U && DAVTRAIN_TAPE_SKIP == SEP_TAPE_SKIP &&
+                  DAVTRAIN_TAPE_ENC_Z == DCTTRAIN_TAPE_ENC_Z && DAVTRAIN_TAPE_DEC_Z == DCTTRAIN_TAPE_DEC_Z,
+              "one tape_offset body serves both headers");
+
+namespace {
+// what the two handles share: the audio-visual one takes the `av` branches of the plan, the forward and the backward
+struct DctCtx : CtTrainHandle {
+  const bool av;
+  DctCtx(const char* prefix_, bool av_) : CtTrainHandle(prefix_, DCT_UNUSED), av(av_) {}
+};
+}  // namespace
+
+struct dcttrain_ctx : DctCtx {
+  dcttrain_ctx() : DctCtx("dcttrain", false) {}
+};
+
+struct davtrain_ctx : DctCtx {
+  davtrain_ctx() : DctCtx("davtrain", true) {}
 };
 
 namespace {
 
-int make_plan(CtHandle* c, int B, int64_t T, Plan& p) {
+// Tv: video frames (audio-visual handle; the audio-only entry points pass 0)
+int make_plan(CtHandle* h, int B, int64_t T, int Tv, Plan& p) {
+  const bool av = static_cast<DctCtx*>(h)->av;
+  CtHandle* c = h;
   // the decoder runs on 2*B*F rows of 512 (32-bit row indexing in the tap-shifted loaders)
   if (int rc = plan_train_head(c, B, T, "2*B*F*512", p)) return rc;
+  if (av && Tv < 1) return c->fail(CTASNET_ERR_INVALID, "Tv must be >= 1 (got %d)", Tv);
+  if (av && (int64_t)B * Tv * CT_N > (int64_t)INT32_MAX)
+    return c->fail(CTASNET_ERR_INVALID, "B*Tv*512 = %lld exceeds 32-bit indexing (B=%d, Tv=%d)", (long long)B * Tv * CT_N, B, Tv);
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
   const size_t M = (size_t)p.M;
@@ -148,6 +344,10 @@ int make_plan(CtHandle* c, int B, int64_t T, Plan& p) {
   p.off_dz = take(4 * 2 * M * CT_N * 4);                          // tape: decoder pre-activations
   p.off_ga = take(2 * M * CT_N * 4);                              // backward ping-pong
   p.off_gb = take(2 * M * CT_N * 4);
+  const size_t rows_v = av ? (size_t)B * Tv : 0;
+  p.off_dvcat = take(rows_v * CT_N * 4);                         // d vcat
+  p.off_vslab = take(rows_v * 2 * CT_N * 4);                     // per-(b, t) partials of d video_ln.weight | bias
+  p.off_vcat = take(rows_v * CT_N * 4);                          // tape: compressed embeddings; the workspace ends with it
   p.total = o;
   return DCTTRAIN_OK;
 }
@@ -162,7 +362,7 @@ void pack_sources(const std::vector<const float*>& W, PackSrc& ps) {
 // one tap's 128-column slice of a dense weight gradient: partial tiles of wgrad_kernel (static schedule), then the sum
 // into out[row * 1536 + col * 3]
 template <class YL, class XL>
-int launch_dense_wgrad(dcttrain_ctx* c, hipStream_t st, int64_t rows, const YL& yl, const XL& xl, float* slab, float* out) {
+int launch_dense_wgrad(DctCtx* c, hipStream_t st, int64_t rows, const YL& yl, const XL& xl, float* slab, float* out) {
   auto kern = wgrad_kernel<DCT_WN, DCT_WK, YL, XL, false>;
   const size_t lds = WgradShape<DCT_WN, DCT_WK>::lds_bytes();
   static PerDeviceOnce once;
@@ -196,7 +396,7 @@ struct DenseBwd {
 };
 
 template <bool PRE>
-int dense_wgrads(dcttrain_ctx* c, hipStream_t st, const DenseBwd& d, float* slab) {
+int dense_wgrads(DctCtx* c, hipStream_t st, const DenseBwd& d, float* slab) {
   const int rows = (int)d.rows;
   for (int k = 0; k < 3; ++k) {
     const int shift = d.transposed ? (1 - k) * d.dil : (k - 1) * d.dil;
@@ -216,7 +416,7 @@ int dense_wgrads(dcttrain_ctx* c, hipStream_t st, const DenseBwd& d, float* slab
 }
 
 // backward of one dense k = 3 layer + PReLU
-int dense_backward(dcttrain_ctx* c, hipStream_t st, const DenseBwd& d, float* slab, float* cslab, float* aslab) {
+int dense_backward(DctCtx* c, hipStream_t st, const DenseBwd& d, float* slab, float* cslab, float* aslab) {
   // PReLU: dz = dy (z > 0 ? 1 : a) in place, d a = sum dy z over z <= 0
   hipLaunchKernelGGL(cttrain_prelu_bwd_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, d.dy, d.z, d.slope, d.rows * CT_N, aslab);
   CT_LAUNCH_CHECK(c, "dcttrain dense prelu backward");
@@ -234,63 +434,11 @@ int dense_backward(dcttrain_ctx* c, hipStream_t st, const DenseBwd& d, float* sl
   return DCTTRAIN_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dcttrain_abi_version(void) { return DCTTRAIN_ABI_VERSION; }
-
-int dcttrain_create(dcttrain_handle* out, int av) {
-  if (av != 0) {
-    if (out) *out = nullptr;
-    g_create_error = "the audio-visual training step (DeepAVConvTasNet) is not built: dcttrain_create takes av = 0";
-    return DCTTRAIN_ERR_INVALID;
-  }
-  if (int rc = ct_create(out, "deep Conv-TasNet training step", g_create_error)) return rc;
-  dcttrain_ctx* c = *out;
-  add_deepconvtasnet_names(c, false);
-  c->w.assign(c->names.size(), nullptr);
-  c->g.assign(c->names.size(), nullptr);
-  return DCTTRAIN_OK;
-}
-
-void dcttrain_destroy(dcttrain_handle h) { delete h; }
-
-const char* dcttrain_last_error(dcttrain_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-int dcttrain_num_weights(dcttrain_handle h) { return h ? (int)h->names.size() : 0; }
-
-const char* dcttrain_weight_name(dcttrain_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
-
-int64_t dcttrain_weight_numel(dcttrain_handle h, int i) { return h ? h->weight_numel(i) : -1; }
-
-int dcttrain_bind_weights(dcttrain_handle h, const float* const* dev_ptrs, int n) {
-  return h ? bind_weights(h, dev_ptrs, n) : DCTTRAIN_ERR_INVALID;
-}
-
-int dcttrain_bind_grads(dcttrain_handle h, float* const* dev_ptrs, int n) {
-  return h ? bind_grads(h, dev_ptrs, n) : DCTTRAIN_ERR_INVALID;
-}
-
-int64_t dcttrain_flat_offset(dcttrain_handle h, int slot) { return h ? flat_offset(h, slot) : -1; }
-
-int64_t dcttrain_flat_numel(dcttrain_handle h) { return h ? flat_numel(h) : -1; }
-
-int64_t dcttrain_frames(int64_t T) { return frames_of(T); }
-
-int64_t dcttrain_out_len(int64_t T) { return out_len_of(T); }
-
-size_t dcttrain_workspace_bytes(dcttrain_handle h, int B, int64_t T) {
-  if (!h) return 0;
-  Plan p;
-  if (make_plan(h, B, T, p)) return 0;
-  return p.total;
-}
-
-int64_t dcttrain_tape_offset(dcttrain_handle h, int B, int64_t T, int which, int block) {
+int64_t dct_tape_offset(DctCtx* h, int B, int64_t T, int Tv, int which, int block) {
   if (!h) return -1;
   Plan p;
-  if (make_plan(h, B, T, p)) return -1;
+  if (make_plan(h, B, T, Tv, p)) return -1;
+  if (h->av && which == DAVTRAIN_TAPE_VCAT) return (int64_t)p.off_vcat;
   const size_t M = (size_t)p.M;
   if (which == DCTTRAIN_TAPE_ENC_Z || which == DCTTRAIN_TAPE_DEC_Z) {
     if (block < 0 || block >= 4) {
@@ -303,12 +451,21 @@ int64_t dcttrain_tape_offset(dcttrain_handle h, int B, int64_t T, int which, int
   return sep_tape_offset(h, p, which, block);
 }
 
-int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T, float* s1_pred, float* s2_pred, void* ws,
-                           size_t ws_bytes, void* stream) {
-  dcttrain_ctx* c = h;
+// the audio-visual handle needs both embeddings (Tv is checked by the plan)
+int check_embeddings(DctCtx* c, const float* e1, const float* e2) {
+  if (c && c->av && (!e1 || !e2))
+    return c->fail(CTASNET_ERR_INVALID, "the audio-visual model needs both speaker embeddings (e1 / e2 must not be NULL)");
+  return CTASNET_OK;
+}
+
+// *_train_forward of both handles; e1, e2, Tv: the audio-visual one's
+int dct_train_forward(DctCtx* c, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv, float* s1_pred,
+                      float* s2_pred, void* ws, size_t ws_bytes, void* stream) {
   Plan p;
   WsPtr at;
-  if (int rc = train_prologue(c, make_plan, false, mix, s1_pred, s2_pred, B, T, ws, ws_bytes, p, at)) return rc;
+  if (int rc = check_embeddings(c, e1, e2)) return rc;
+  auto plan = [Tv](CtHandle* h, int b, int64_t t, Plan& q) { return make_plan(h, b, t, Tv, q); };
+  if (int rc = train_prologue(c, plan, false, mix, s1_pred, s2_pred, B, T, ws, ws_bytes, p, at)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int F = (int)p.F;
   const int64_t M = p.M;
@@ -328,8 +485,22 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
   hipLaunchKernelGGL(dctasnet_pack_kernel, dim3((unsigned)(DC_TAP_FLOATS / 4 / 256), DC_LAYERS), dim3(256), 0, st, ps, wpk);
   CT_LAUNCH_CHECK(c, "dcttrain weight pack");
 
+  // video rows (deepavconvtasnet.py:140-151), the launches of dctasnet_forward: vcat stays on the tape; vid waits in the
+  // scratch that holds the last decoder activation later on
+  float* vid = nullptr;
+  if (c->av) {
+    float* vcat = at.fp(p.off_vcat);
+    hipLaunchKernelGGL(dctasnet_video_linear_kernel, dim3((unsigned)((Tv + DC_VT - 1) / DC_VT), B), dim3(256), 0, st, e1, e2,
+                       W[DC_AV0], W[DC_AV0 + 1], Tv, vcat);
+    CT_LAUNCH_CHECK(c, "davtrain video linear");
+    vid = ydec;
+    hipLaunchKernelGGL(dctasnet_video_frames_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, vcat, W[DC_AV0 + 2],
+                       W[DC_AV0 + 3], F, Tv, M, vid);
+    CT_LAUNCH_CHECK(c, "davtrain video frames");
+  }
+
   // deep encoder (deepconvtasnet.py:7-26): first conv -> c0; layer l reads c0 / PReLU(z_{l-1}) and writes z_l; the last one
-  // also writes enc = PReLU(z_3) and the GlobalNorm partials
+  // also writes enc = PReLU(z_3) (+ the video rows: the fused tensor) and the GlobalNorm partials of enc
   const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
   hipLaunchKernelGGL(ctasnet_encoder_kernel<true>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], W[1], c0, nullptr);
   CT_LAUNCH_CHECK(c, "dcttrain encoder");
@@ -337,7 +508,7 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
     float* z = at.fp(p.off_ez) + (size_t)l * M * CT_N;
     const float* x = l == 0 ? c0 : z - (size_t)M * CT_N;
     if (int rc = launch_dense<true>(c, st, wpk + (int64_t)l * 3 * DC_TAP_FLOATS, false, 1 << l, x, l == 0 ? nullptr : W[1 + 3 * l],
-                                    z, l == 3 ? enc : nullptr, M, F, 0, W[3 + 3 * l], W[4 + 3 * l], nullptr,
+                                    z, l == 3 ? enc : nullptr, M, F, 0, W[3 + 3 * l], W[4 + 3 * l], l == 3 ? vid : nullptr,
                                     l == 3 ? sb.part : nullptr))
       return rc;
   }
@@ -358,12 +529,14 @@ int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T
   return launch_overlap_add<true>(c, st, taps, W[DC_DEC0 + 13], B, F, p.Lout, s1_pred, s2_pred);
 }
 
-int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t T, const float* d_s1, const float* d_s2, void* ws,
-                            size_t ws_bytes, void* stream) {
-  dcttrain_ctx* c = h;
+// *_train_backward of both handles
+int dct_train_backward(DctCtx* c, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv, const float* d_s1,
+                       const float* d_s2, void* ws, size_t ws_bytes, void* stream) {
   Plan p;
   WsPtr at;
-  if (int rc = train_prologue(c, make_plan, true, mix, d_s1, d_s2, B, T, ws, ws_bytes, p, at)) return rc;
+  if (int rc = check_embeddings(c, e1, e2)) return rc;
+  auto plan = [Tv](CtHandle* h, int b, int64_t t, Plan& q) { return make_plan(h, b, t, Tv, q); };
+  if (int rc = train_prologue(c, plan, true, mix, d_s1, d_s2, B, T, ws, ws_bytes, p, at)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int F = (int)p.F;
   const int64_t M = p.M;
@@ -423,6 +596,26 @@ int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t 
   if (int rc = launch_separator_backward<HEAD_DYM>(c, st, W.data() + DC_SEP0, G.data() + DC_SEP0, dy, nullptr, B, F, M, p, ws))
     return rc;
 
+  // ---- video head (deepavconvtasnet.py:140-153): d fused is also d vid; read here, before encoder layer 3's PReLU
+  // backward overwrites denc in place
+  if (c->av) {
+    float* dvcat = at.fp(p.off_dvcat);
+    float* vslab = at.fp(p.off_vslab);
+    const int rows_v = B * Tv;
+    hipLaunchKernelGGL(davtrain_video_ln_bwd_kernel, dim3(Tv, B), dim3(256), 0, st, denc, at.fp(p.off_vcat), W[DC_AV0 + 2], F, Tv,
+                       dvcat, vslab);
+    CT_LAUNCH_CHECK(c, "davtrain video LayerNorm backward");
+    if (int rc = launch_reduce(c, st, vslab, rows_v, 2 * CT_N, 1, CT_N, G[DC_AV0 + 2], CT_N)) return rc;
+    if (int rc = launch_reduce(c, st, vslab + CT_N, rows_v, 2 * CT_N, 1, CT_N, G[DC_AV0 + 3], CT_N)) return rc;
+    const int nchunk = (Tv + DAV_TT - 1) / DAV_TT;
+    const int gr = (int)std::min<int64_t>((int64_t)B * nchunk, DAV_G_R);
+    hipLaunchKernelGGL(davtrain_video_linear_bwd_kernel, dim3(CT_N / DAV_KT, gr), dim3(256), 0, st, e1, e2, dvcat, B, Tv, nchunk,
+                       slab, cslab);
+    CT_LAUNCH_CHECK(c, "davtrain video linear backward");
+    if (int rc = launch_reduce(c, st, slab, gr, (int64_t)DC_HV * CT_N, DC_HV, CT_N, G[DC_AV0], CT_N)) return rc;
+    if (int rc = launch_reduce(c, st, cslab, gr, DC_HV, 1, DC_HV, G[DC_AV0 + 1], DC_HV)) return rc;
+  }
+
   // ---- deep encoder, layers 3..0 (d = 8, 4, 2, 1) on M rows: denc -> ga -> gb -> ga -> gb = d c0
   dy = denc;
   dx = ga;
@@ -441,6 +634,73 @@ int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t 
     return rc;
   if (int rc = launch_reduce(c, st, slab, ns, (int64_t)CT_N * 2 * CT_L, CT_N, 2 * CT_L, G[0], 2 * CT_L)) return rc;
   return launch_colsum<CT_N>(c, st, dy, M, CT_N, 0, cslab, G[1]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcttrain_abi_version(void) { return DCTTRAIN_ABI_VERSION; }
+
+int dcttrain_create(dcttrain_handle* out, int av) {
+  if (av != 0) {
+    if (out) *out = nullptr;
+    g_create_error = "the audio-visual training step (DeepAVConvTasNet) is not built: dcttrain_create takes av = 0";
+    return DCTTRAIN_ERR_INVALID;
+  }
+  if (int rc = ct_create(out, "deep Conv-TasNet training step", g_create_error)) return rc;
+  dcttrain_ctx* c = *out;
+  add_deepconvtasnet_names(c, false);
+  c->w.assign(c->names.size(), nullptr);
+  c->g.assign(c->names.size(), nullptr);
+  return DCTTRAIN_OK;
+}
+
+void dcttrain_destroy(dcttrain_handle h) { delete h; }
+
+const char* dcttrain_last_error(dcttrain_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int dcttrain_num_weights(dcttrain_handle h) { return h ? (int)h->names.size() : 0; }
+
+const char* dcttrain_weight_name(dcttrain_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
+
+int64_t dcttrain_weight_numel(dcttrain_handle h, int i) { return h ? h->weight_numel(i) : -1; }
+
+int dcttrain_bind_weights(dcttrain_handle h, const float* const* dev_ptrs, int n) {
+  return h ? bind_weights(h, dev_ptrs, n) : DCTTRAIN_ERR_INVALID;
+}
+
+int dcttrain_bind_grads(dcttrain_handle h, float* const* dev_ptrs, int n) {
+  return h ? bind_grads(h, dev_ptrs, n) : DCTTRAIN_ERR_INVALID;
+}
+
+int64_t dcttrain_flat_offset(dcttrain_handle h, int slot) { return h ? flat_offset(h, slot) : -1; }
+
+int64_t dcttrain_flat_numel(dcttrain_handle h) { return h ? flat_numel(h) : -1; }
+
+int64_t dcttrain_frames(int64_t T) { return frames_of(T); }
+
+int64_t dcttrain_out_len(int64_t T) { return out_len_of(T); }
+
+size_t dcttrain_workspace_bytes(dcttrain_handle h, int B, int64_t T) {
+  if (!h) return 0;
+  Plan p;
+  if (make_plan(h, B, T, 0, p)) return 0;
+  return p.total;
+}
+
+int64_t dcttrain_tape_offset(dcttrain_handle h, int B, int64_t T, int which, int block) {
+  return dct_tape_offset(h, B, T, 0, which, block);
+}
+
+int dcttrain_train_forward(dcttrain_handle h, const float* mix, int B, int64_t T, float* s1_pred, float* s2_pred, void* ws,
+                           size_t ws_bytes, void* stream) {
+  return dct_train_forward(h, mix, nullptr, nullptr, B, T, 0, s1_pred, s2_pred, ws, ws_bytes, stream);
+}
+
+int dcttrain_train_backward(dcttrain_handle h, const float* mix, int B, int64_t T, const float* d_s1, const float* d_s2, void* ws,
+                            size_t ws_bytes, void* stream) {
+  return dct_train_backward(h, mix, nullptr, nullptr, B, T, 0, d_s1, d_s2, ws, ws_bytes, stream);
 }
 
 size_t dcttrain_clip_scratch_bytes(dcttrain_handle) { return CLIP_PARTS * sizeof(double); }
@@ -462,5 +722,80 @@ double dcttrain_flops_per_mixture(dcttrain_handle, int64_t T) {
   // forward product
   return 3.0 * 2.0 * deepconvtasnet_macs() * (double)frames_of(T);
 }
+
+// ---- davtrain_*: the same bodies on the audio-visual handle (include/davctasnet_train.h)
+int davtrain_abi_version(void) { return DAVTRAIN_ABI_VERSION; }
+
+int davtrain_create(davtrain_handle* out) {
+  if (int rc = ct_create(out, "deep audio-visual Conv-TasNet training step", g_create_error)) return rc;
+  davtrain_ctx* c = *out;
+  add_deepconvtasnet_names(c, true);
+  c->w.assign(c->names.size(), nullptr);
+  c->g.assign(c->names.size(), nullptr);
+  return DAVTRAIN_OK;
+}
+
+void davtrain_destroy(davtrain_handle h) { delete h; }
+
+const char* davtrain_last_error(davtrain_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int davtrain_num_weights(davtrain_handle h) { return h ? (int)h->names.size() : 0; }
+
+const char* davtrain_weight_name(davtrain_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
+
+int64_t davtrain_weight_numel(davtrain_handle h, int i) { return h ? h->weight_numel(i) : -1; }
+
+int davtrain_bind_weights(davtrain_handle h, const float* const* dev_ptrs, int n) {
+  return h ? bind_weights(h, dev_ptrs, n) : DAVTRAIN_ERR_INVALID;
+}
+
+int davtrain_bind_grads(davtrain_handle h, float* const* dev_ptrs, int n) {
+  return h ? bind_grads(h, dev_ptrs, n) : DAVTRAIN_ERR_INVALID;
+}
+
+int64_t davtrain_flat_offset(davtrain_handle h, int slot) { return h ? flat_offset(h, slot) : -1; }
+
+int64_t davtrain_flat_numel(davtrain_handle h) { return h ? flat_numel(h) : -1; }
+
+int64_t davtrain_frames(int64_t T) { return frames_of(T); }
+
+int64_t davtrain_out_len(int64_t T) { return out_len_of(T); }
+
+size_t davtrain_workspace_bytes(davtrain_handle h, int B, int64_t T, int Tv) {
+  if (!h) return 0;
+  Plan p;
+  if (make_plan(h, B, T, Tv, p)) return 0;
+  return p.total;
+}
+
+int64_t davtrain_tape_offset(davtrain_handle h, int B, int64_t T, int Tv, int which, int block) {
+  return dct_tape_offset(h, B, T, Tv, which, block);
+}
+
+int davtrain_train_forward(davtrain_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,
+                           float* s1_pred, float* s2_pred, void* ws, size_t ws_bytes, void* stream) {
+  return dct_train_forward(h, mix, e1, e2, B, T, Tv, s1_pred, s2_pred, ws, ws_bytes, stream);
+}
+
+int davtrain_train_backward(davtrain_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,
+                            const float* d_s1, const float* d_s2, void* ws, size_t ws_bytes, void* stream) {
+  return dct_train_backward(h, mix, e1, e2, B, T, Tv, d_s1, d_s2, ws, ws_bytes, stream);
+}
+
+size_t davtrain_clip_scratch_bytes(davtrain_handle) { return CLIP_PARTS * sizeof(double); }
+
+int davtrain_grad_clip(davtrain_handle h, float* flat_grad, int64_t n_flat, float max_norm, void* scratch, size_t scratch_bytes,
+                       float* norm_out, void* stream) {
+  return h ? train_grad_clip(h, flat_grad, n_flat, max_norm, scratch, scratch_bytes, norm_out, stream) : DAVTRAIN_ERR_INVALID;
+}
+
+int davtrain_adamw_step(davtrain_handle h, const float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_flat, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
+  return h ? train_adamw_step(h, flat_grad, exp_avg, exp_avg_sq, n_flat, lr, beta1, beta2, eps, weight_decay, step, stream)
+           : DAVTRAIN_ERR_INVALID;
+}
+
+// the video head is left out of the cost model, as in dctasnet_flops_per_mixture
+double davtrain_flops_per_mixture(davtrain_handle, int64_t T) { return 3.0 * 2.0 * deepconvtasnet_macs() * (double)frames_of(T); }
 
 }  // extern "C"

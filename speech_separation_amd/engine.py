@@ -472,7 +472,7 @@ class _ConvTasNetEngineBase:
     optional `alloc` hook."""
 
     def __init__(self, prefix: str, what: str, spec, device, alloc, *create_args):
-        """prefix: "ctasnet" / "dctasnet" / "cttrain" / "dcttrain"; what: the model's name in the weight-table message; spec: its
+        """prefix: "ctasnet" / "dctasnet" / "cttrain" / "dcttrain" / "davtrain"; what: the model's name in the weight-table message; spec: its
         state_dict spec; create_args: what `<prefix>_create` takes after the handle."""
         self._prefix = prefix
         self.device = torch.device(device)
@@ -695,44 +695,57 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
         self._grads, self._grads_flat = grads, flat
         return grads
 
-    def train_forward(self, mix: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, tuple]:
+    def _video_args(self, B: int, emb: tuple) -> Tuple[tuple, tuple]:
+        """What an audio-visual member passes beside the mixture: (device pointers that follow mix, what follows (B, T)
+        wherever a shape is passed).  Nothing here."""
+        if emb:
+            raise TypeError(f"{type(self).__name__} takes no speaker embeddings")
+        return (), ()
+
+    def train_forward(self, mix: torch.Tensor, *emb) -> Tuple[torch.Tensor, torch.Tensor, tuple]:
         """mix [B][T] -> (s1_pred, s2_pred, tape); the tape lives in the engine's workspace until the next train_forward."""
         mix, B, T = self._mix_2d(mix)
+        ptrs, more = self._video_args(B, emb)
         self._need_bound("train_forward")
-        ws = self._workspace(B, T)
+        ws = self._workspace(B, T, *more)
         L = self.out_len(T)
         s1, s2 = self._empty(B, L), self._empty(B, L)
-        rc = self._fn("train_forward")(self._h, mix.data_ptr(), B, T, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       self._stream())
+        rc = self._fn("train_forward")(self._h, mix.data_ptr(), *ptrs, B, T, *more, s1.data_ptr(), s2.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), self._stream())
         if rc:
             self._raise(rc, f"{self._prefix}_train_forward")
         self._tape_id += 1
-        return s1, s2, (self._tape_id, B, T, ws.data_ptr())
+        return s1, s2, (self._tape_id, B, T, ws.data_ptr(), *more)
 
     TAPE_V1, TAPE_U, TAPE_SKIP = 0, 1, 2
 
     def tape_tensor(self, tape: tuple, which: int, block: int = 0) -> torch.Tensor:
         """A view of a pre-activation the forward of `tape` stored (cttrain_tape_offset): TAPE_V1 / TAPE_U of `block`
         [B*F][512], TAPE_SKIP [B*F][128], frame-major.  Valid until the next train_forward (tests: PReLU branch masks)."""
-        tid, B, T, wsp = tape
+        tid, B, T, wsp, *more = tape
         if tid != self._tape_id or self._ws is None or self._ws.data_ptr() != wsp:
             raise RuntimeError("tape_tensor: the tape was overwritten by a later train_forward")
-        off = int(self._fn("tape_offset")(self._h, B, T, which, block))
+        off = int(self._fn("tape_offset")(self._h, B, T, *more, which, block))
         if off < 0:
             self._raise(1, f"{self._prefix}_tape_offset")
-        M, C = self._tape_shape(B * self.frames(T), which)
+        M, C = self._tape_shape(B * self.frames(T), which, B, *more)
         return self._ws[off:off + 4 * M * C].view(torch.float32).view(M, C)
 
-    def _tape_shape(self, M: int, which: int) -> Tuple[int, int]:
+    def _tape_shape(self, M: int, which: int, *shape) -> Tuple[int, int]:
+        """(rows, columns) of tape kind `which`; M = B * F, shape = (B,) + what follows (B, T) in the tape's identity."""
         return M, (128 if which == self.TAPE_SKIP else 512)
 
-    def train_backward(self, mix: torch.Tensor, d_s1: torch.Tensor, d_s2: torch.Tensor, tape: tuple):
-        """d loss / d predictions -> the bound gradient buffers (overwritten), from the tape of `train_forward`."""
+    def train_backward(self, mix: torch.Tensor, *args):
+        """(mix, [embeddings of an audio-visual member,] d_s1, d_s2, tape): d loss / d predictions -> the bound gradient
+        buffers (overwritten), from the tape of `train_forward`."""
+        *emb, d_s1, d_s2, tape = args
         if self._grads is None:
             raise RuntimeError(f"{type(self).__name__}.train_backward: gradients not bound (call bind_grads first)")
         B, T = mix.shape
-        tid, tB, tT, tws = tape
-        if tid != self._tape_id or (tB, tT) != (B, T) or self._ws is None or self._ws.data_ptr() != tws:
+        ptrs, more = self._video_args(B, tuple(emb))
+        tid, tB, tT, tws, *tmore = tape
+        if (tid != self._tape_id or (tB, tT, *tmore) != (B, T, *more) or self._ws is None
+                or self._ws.data_ptr() != tws):
             raise RuntimeError(f"{type(self).__name__}.train_backward: the tape was overwritten by a later train_forward "
                                f"(one backward per forward, in order)")
         mix = _check(mix, "mix", (B, T), self.device)
@@ -740,8 +753,8 @@ class ConvTasNetTrainEngine(_ConvTasNetEngineBase):
         d1 = _check(d_s1, "d_s1", (B, L), self.device)
         d2 = _check(d_s2, "d_s2", (B, L), self.device)
         ws = self._ws
-        rc = self._fn("train_backward")(self._h, mix.data_ptr(), B, T, d1.data_ptr(), d2.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        self._stream())
+        rc = self._fn("train_backward")(self._h, mix.data_ptr(), *ptrs, B, T, *more, d1.data_ptr(), d2.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), self._stream())
         if rc:
             self._raise(rc, f"{self._prefix}_train_backward")
 
@@ -785,7 +798,37 @@ class DeepConvTasNetTrainEngine(ConvTasNetTrainEngine):
         from .spec import deepconvtasnet_state_dict_spec
         self._init_train("dcttrain", "deep Conv-TasNet training", deepconvtasnet_state_dict_spec(False), device, alloc, 0)
 
-    def _tape_shape(self, M: int, which: int) -> Tuple[int, int]:
+    def _tape_shape(self, M: int, which: int, *shape) -> Tuple[int, int]:
         if which == self.TAPE_DEC_Z:
             return 2 * M, 512
-        return super()._tape_shape(M, which)
+        return super()._tape_shape(M, which, *shape)
+
+
+class DeepAVConvTasNetTrainEngine(DeepConvTasNetTrainEngine):
+    """DeepAVConvTasNet training step (include/davctasnet_train.h): DeepConvTasNetTrainEngine on the `davtrain_*` entry points
+    with the audio-visual weight table.  train_forward(mix, e1, e2) / train_backward(mix, e1, e2, d_s1, d_s2, tape) take the
+    speaker embeddings [B][512][Tv], which get no gradient; Tv is part of the tape's identity.  Extra tape kind: TAPE_VCAT,
+    the two speakers' compressed embeddings side by side before the interpolation, [B*Tv][512]."""
+
+    TAPE_VCAT = 5
+
+    def __init__(self, device: torch.device | str = "cuda:0", alloc=None):
+        from .spec import deepconvtasnet_state_dict_spec
+        self._init_train("davtrain", "deep audio-visual Conv-TasNet training", deepconvtasnet_state_dict_spec(True), device,
+                         alloc)
+
+    def _video_args(self, B: int, emb: tuple) -> Tuple[tuple, tuple]:
+        if len(emb) != 2 or emb[0] is None or emb[1] is None:
+            raise ValueError("DeepAVConvTasNet needs s1_embedding and s2_embedding")
+        if emb[0].dim() != 3:
+            raise ValueError(f"s1_embedding: expected (B,512,Tv), got {tuple(emb[0].shape)}")
+        Tv = int(emb[0].shape[-1])
+        e1 = _check(emb[0], "s1_embedding", (B, 512, Tv), self.device)
+        e2 = _check(emb[1], "s2_embedding", (B, 512, Tv), self.device)
+        return (e1.data_ptr(), e2.data_ptr()), (Tv,)
+
+    def _tape_shape(self, M: int, which: int, *shape) -> Tuple[int, int]:
+        if which == self.TAPE_VCAT:
+            B, Tv = shape
+            return B * Tv, 512
+        return super()._tape_shape(M, which, *shape)

@@ -32,8 +32,8 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from .engine import (ConvTasNetEngine, ConvTasNetTrainEngine, DeepConvTasNetEngine, DeepConvTasNetTrainEngine,
-                     DptnEngine)
+from .engine import (ConvTasNetEngine, ConvTasNetTrainEngine, DeepAVConvTasNetTrainEngine, DeepConvTasNetEngine,
+                     DeepConvTasNetTrainEngine, DptnEngine)
 from .spec import DPTNConfig, convtasnet_state_dict_spec, deepconvtasnet_state_dict_spec, state_dict_spec
 
 
@@ -353,18 +353,20 @@ class ConvTasNet(nn.Module):
 
 
 class _ConvTasNetTrainFn(torch.autograd.Function):
-    """The model part of TrainableConvTasNet's / TrainableDeepConvTasNet's training step, as _SeparateFn: forward records
-    the tape (<prefix>_train_forward), backward turns d loss / d predictions into every parameter's gradient
-    (<prefix>_train_backward) and hands autograd views of one flat copy -- None for a parameter the forward never reads
-    (the engine's no_grad_keys), as autograd itself leaves it."""
+    """The model part of TrainableConvTasNet's / TrainableDeepConvTasNet's / TrainableDeepAVConvTasNet's training step, as
+    _SeparateFn: forward records the tape (<prefix>_train_forward), backward turns d loss / d predictions into every
+    parameter's gradient (<prefix>_train_backward) and hands autograd views of one flat copy -- None for a parameter the
+    forward never reads (the engine's no_grad_keys), as autograd itself leaves it.  e1, e2: the speaker embeddings of the
+    audio-visual model (None otherwise); they get no gradient."""
 
     @staticmethod
-    def forward(ctx, module, mix, *params):
+    def forward(ctx, module, mix, e1, e2, *params):
         eng = module._get_engine(mix.device)
         if eng._grads is None:
             eng.bind_grads()
-        s1, s2, tape = eng.train_forward(mix)
-        ctx.module, ctx.tape, ctx.mix = module, tape, mix
+        emb = () if e1 is None else (e1, e2)
+        s1, s2, tape = eng.train_forward(mix, *emb)
+        ctx.module, ctx.tape, ctx.mix, ctx.emb = module, tape, mix, emb
         return s1, s2
 
     @staticmethod
@@ -373,7 +375,7 @@ class _ConvTasNetTrainFn(torch.autograd.Function):
         mix = ctx.mix
         L = eng.out_len(mix.shape[1])
         zeros = lambda g: torch.zeros(mix.shape[0], L, device=mix.device) if g is None else g.contiguous()
-        eng.train_backward(mix, zeros(d_s1), zeros(d_s2), ctx.tape)
+        eng.train_backward(mix, *ctx.emb, zeros(d_s1), zeros(d_s2), ctx.tape)
         ctx.tape = None
         # the library's gradient buffers are reused by the next step: autograd gets its own flat copy, whose views become
         # .grad (train.allreduce_gradients and the fused clip / AdamW find it again through `_flat_grad`)
@@ -383,26 +385,35 @@ class _ConvTasNetTrainFn(torch.autograd.Function):
         for k, shape in eng.slots:
             o = eng._grad_offsets[k]
             outs.append(None if k in eng.no_grad_keys else flat[o:o + eng._grads[k].numel()].view(*shape))
-        return (None, None) + tuple(outs)
+        return (None, None, None, None) + tuple(outs)
 
 
 class _TrainStep:
     """What the Trainable* classes put in front of their inference class: the inference engine kept beside the training
     one (`_engine`), the flat gradient of the last backward, and the forward that picks between the two."""
 
-    def __init__(self, N=512, L=16):
-        super().__init__(N, L)
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)            # the inference class's constructor
         self._infer_engine = None
         self._flat_grad: Optional[torch.Tensor] = None
         for p in self.parameters():
             p._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
 
-    def forward(self, mix, **batch):
+    def _step(self, mix, *emb):
+        """emb: the two speaker embeddings of an audio-visual model, or nothing"""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), *self.parameters())
+            for name, e in zip(("s1_embedding", "s2_embedding"), emb):
+                if isinstance(e, torch.Tensor) and e.requires_grad:
+                    raise NotImplementedError(f"{type(self).__name__}: no gradient is computed for {name} (it comes from a "
+                                              f"frozen lip-reader): pass it detached")
+            e1, e2 = emb if emb else (None, None)
+            s1, s2 = _ConvTasNetTrainFn.apply(self, mix.contiguous(), e1, e2, *self.parameters())
         else:
-            s1, s2 = self._get_infer_engine(mix.device).forward(mix)
+            s1, s2 = self._get_infer_engine(mix.device).forward(mix, *emb)
         return {"s1_pred": s1, "s2_pred": s2}
+
+    def forward(self, mix, **batch):
+        return self._step(mix)
 
 
 class TrainableConvTasNet(_TrainStep, ConvTasNet):
@@ -486,7 +497,7 @@ class TrainableDeepConvTasNet(_TrainStep, DeepConvTasNet):
 class DeepAVConvTasNet(DeepConvTasNet):
     """Audio-visual deep Conv-TasNet (src/configs/model/deepavconvtasnet.yaml) -- same constructor as the reference class
     (src/model/deepavconvtasnet.py:122-134); N and L are ignored as there.  Only the built sizes video_emb_size = hidden_video
-    = 512 exist.  Inference only (include/dctasnet.h): the audio-visual training step is not built."""
+    = 512 exist.  Inference only (include/dctasnet.h); TrainableDeepAVConvTasNet adds the training step."""
 
     _AV = True
 
@@ -498,3 +509,22 @@ class DeepAVConvTasNet(DeepConvTasNet):
 
     def forward(self, mix, s1_embedding, s2_embedding, **batch):
         return self._run(mix, s1_embedding, s2_embedding)
+
+
+class TrainableDeepAVConvTasNet(_TrainStep, DeepAVConvTasNet):
+    """DeepAVConvTasNet with the training step on libdptnav (include/davctasnet_train.h), the counterpart of
+    TrainableDeepConvTasNet: same constructor, state_dict keys and order, initialisation and parameter-count lines as
+    DeepAVConvTasNet, and checkpoints load strictly either way.  Under torch.no_grad() the forward is DeepAVConvTasNet's
+    inference engine (bitwise the same outputs); with grad enabled it records a tape and its backward computes every
+    parameter's gradient in HIP, the audio-visual head's included.  The speaker embeddings get no gradient (the reference
+    feeds them from a frozen lip-reader through the dataset): one that requires grad is refused.  decoder.deconv.weight
+    behaves as in TrainableDeepConvTasNet."""
+
+    def _get_engine(self, device: torch.device) -> DeepAVConvTasNetTrainEngine:
+        return _bound_engine(self, "_engine", DeepAVConvTasNetTrainEngine, device)
+
+    def _get_infer_engine(self, device: torch.device) -> DeepConvTasNetEngine:
+        return _bound_engine(self, "_infer_engine", lambda dev: DeepConvTasNetEngine(dev, av=True), device)
+
+    def forward(self, mix, s1_embedding, s2_embedding, **batch):
+        return self._step(mix, s1_embedding, s2_embedding)

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Time one training step of the Conv-TasNet family on the GPU (--model convtasnet: TrainableConvTasNet, deepconvtasnet:
-TrainableDeepConvTasNet; forward, device PIT SI-SNR loss, backward, fused clip, FusedAdamW) at B = 1, 4, 16 x 32000
-samples: STEPS steps between synchronisations, median of REPS, mixtures/s and the fraction of the fp32-MFMA FLOP bound
-(<prefix>_flops_per_mixture, 157.3 TFLOP/s).  Baselines: the model's stock-PyTorch restatement
-(tests/convtasnet_train_ref.py, tests/deepconvtasnet_train_ref.py) trained eagerly with torch.optim.AdamW on the same GPU
-in the same run, and at B = 1 on 16 CPU threads.
+TrainableDeepConvTasNet, deepavconvtasnet: TrainableDeepAVConvTasNet with Tv = 50 video frames; forward, device PIT SI-SNR
+loss, backward, fused clip, FusedAdamW) at B = 1, 4, 16 x 32000 samples: STEPS steps between synchronisations, median of
+REPS, mixtures/s and the fraction of the fp32-MFMA FLOP bound (<prefix>_flops_per_mixture, 157.3 TFLOP/s).  Baselines: the
+model's stock-PyTorch restatement (tests/convtasnet_train_ref.py, tests/deepconvtasnet_train_ref.py,
+tests/deepavconvtasnet_train_ref.py) trained eagerly with torch.optim.AdamW on the same GPU in the same run, and at B = 1 on
+16 CPU threads.  --model takes a comma-separated list: the models are timed one after the other in this process, which is
+what makes their times comparable (the audio-visual step over the audio-only one).
 --check: the B = 16 gradient against fp64 autograd of the restatement on the GPU, on this forward's PReLU branches (kept
 out of the test suite for time), over every parameter the forward reads.
 
@@ -25,19 +27,23 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle.convtasnet_stock import synthetic_convtasnet_weights  # noqa: E402
-from speech_separation_amd import FusedAdamW, SiSNRWavLoss, TrainableConvTasNet, TrainableDeepConvTasNet  # noqa: E402
+from speech_separation_amd import (FusedAdamW, SiSNRWavLoss, TrainableConvTasNet, TrainableDeepAVConvTasNet,  # noqa: E402
+                                   TrainableDeepConvTasNet)
 from speech_separation_amd.spec import DPTN_AUDIO, synthetic_inputs  # noqa: E402
 from speech_separation_amd.train import train_step  # noqa: E402
-from tests import convtasnet_train_ref, deepconvtasnet_train_ref  # noqa: E402
+from tests import convtasnet_train_ref, deepavconvtasnet_train_ref, deepconvtasnet_train_ref  # noqa: E402
 from tests.deepconvtasnet_ref import synthetic_deepconvtasnet_weights  # noqa: E402
 from tests.sisnr_ref import pit_sisnr_loss  # noqa: E402
 
-#: --model -> (module class, its stock restatement, synthetic weights)
-MODELS = {"convtasnet": (TrainableConvTasNet, convtasnet_train_ref, lambda: synthetic_convtasnet_weights(0)),
+#: --model -> (module class, its stock restatement, synthetic weights, video frames Tv or 0)
+MODELS = {"convtasnet": (TrainableConvTasNet, convtasnet_train_ref, lambda: synthetic_convtasnet_weights(0), 0),
           "deepconvtasnet": (TrainableDeepConvTasNet, deepconvtasnet_train_ref,
-                             lambda: synthetic_deepconvtasnet_weights(False, 0))}
+                             lambda: synthetic_deepconvtasnet_weights(False, 0), 0),
+          "deepavconvtasnet": (TrainableDeepAVConvTasNet, deepavconvtasnet_train_ref,
+                               lambda: deepavconvtasnet_train_ref.synthetic_weights(0, "0.25"), 50)}
 PEAK = 157.3e12
 T = 32000
+EMB = ("s1_embedding", "s2_embedding")
 
 
 def timed(fn, steps, reps, sync):
@@ -53,14 +59,18 @@ def timed(fn, steps, reps, sync):
     return statistics.median(out)
 
 
-def batch_of(B, dev):
+def batch_of(B, dev, Tv=0):
     inp = synthetic_inputs(DPTN_AUDIO, B=B, T=T, seed=B)
-    return {k: torch.from_numpy(inp[k]).to(dev) for k in ("mix", "s1", "s2")}
+    batch = {k: torch.from_numpy(inp[k]).to(dev) for k in ("mix", "s1", "s2")}
+    if Tv:
+        for k, e in zip(EMB, deepavconvtasnet_train_ref.synthetic_embeddings(B, Tv, seed=B)):
+            batch[k] = torch.from_numpy(e).to(dev)
+    return batch
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=sorted(MODELS), default="convtasnet")
+    ap.add_argument("--model", default="convtasnet", help="one of %s, or several separated by commas" % ", ".join(sorted(MODELS)))
     ap.add_argument("--batches", default="1,4,16")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
@@ -69,18 +79,33 @@ def main():
     ap.add_argument("--no-baselines", action="store_true", help="time the HIP step only (profiling runs)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
-    module, R, weights = MODELS[a.model]
-    dev = torch.device("cuda:0")
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
+    names = a.model.split(",")
+    if any(n not in MODELS for n in names):
+        ap.error(f"--model: choose from {sorted(MODELS)}")
+    results = [run(n, a) for n in names]
+    if len(results) > 1:      # same process, same device: the ratio of the last model's step to the first's
+        for B in results[0]["hip"]:
+            print(f"{names[-1]} / {names[0]} B={B}: {results[-1]['hip'][B]['ms'] / results[0]['hip'][B]['ms']:.4f}", flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(results[0] if len(results) == 1 else results, f, indent=1)
+
+
+def run(model, a):
+    module, R, weights, Tv = MODELS[model]
+    emb = lambda batch: [batch[k] for k in EMB] if Tv else []
+    tv = [Tv] if Tv else []
+    dev = torch.device("cuda:0")
     sd = {k: torch.from_numpy(v) for k, v in weights().items()}
     sync = lambda: torch.cuda.synchronize(dev)
-    res = {"model": a.model, "T": T, "steps": a.steps, "reps": a.reps, "hip": {}, "stock_gpu": {}, "stock_cpu": {}}
+    res = {"model": model, "T": T, "Tv": Tv, "steps": a.steps, "reps": a.reps, "hip": {}, "stock_gpu": {}, "stock_cpu": {}}
     for B in (int(b) for b in a.batches.split(",")):
         m = module()
         m.load_state_dict(sd, strict=True)
         m = m.to(dev)
-        opt, crit, batch = FusedAdamW(m.parameters(), lr=1e-3), SiSNRWavLoss(), batch_of(B, dev)
+        opt, crit, batch = FusedAdamW(m.parameters(), lr=1e-3), SiSNRWavLoss(), batch_of(B, dev, Tv)
         t = timed(lambda: train_step(m, dict(batch), crit, opt, max_grad_norm=8.0), a.steps, a.reps, sync)
         flops = m._engine.flops_per_mixture(T) * B
         res["hip"][B] = {"ms": t * 1e3, "mix_per_s": B / t, "flop_bound_frac": flops / PEAK / t}
@@ -88,15 +113,15 @@ def main():
               flush=True)
         if a.check and B == 16:
             m.zero_grad()
-            out = m(mix=batch["mix"])
-            masks = R.prelu_masks(m._engine, B, T)     # the fp64 / fp32 references follow this forward's PReLU branches
+            out = m(mix=batch["mix"], **{k: batch[k] for k in EMB if Tv})
+            masks = R.prelu_masks(m._engine, B, T, *tv)     # the fp64 / fp32 references follow this forward's PReLU branches
             masks = {k: [t.to(dev) for t in v] if isinstance(v, list) else v.to(dev) for k, v in masks.items()}
             g = torch.Generator().manual_seed(1)
             d1, d2 = (torch.randn(B, T, generator=g).to(dev) for _ in range(2))
             torch.autograd.backward([out["s1_pred"], out["s2_pred"]], [d1, d2])
             sdd = {k: p.detach() for k, p in m.named_parameters()}
-            g64 = R.grads(sdd, batch["mix"], d1, d2, torch.float64, masks)
-            g32 = R.grads(sdd, batch["mix"], d1, d2, torch.float32, masks)
+            g64 = R.grads(sdd, batch["mix"], *emb(batch), d1, d2, torch.float64, masks)
+            g32 = R.grads(sdd, batch["mix"], *emb(batch), d1, d2, torch.float32, masks)
             keys = [k for k, p in m.named_parameters() if p.grad is not None]     # the deep model: all but decoder.deconv.weight
             unused = [k for k, p in m.named_parameters() if p.grad is None]
             assert unused == list(m._engine.no_grad_keys) and not any(g64[k].any() for k in unused)
@@ -117,7 +142,7 @@ def main():
 
         def stock_step(p=p, sopt=sopt, batch=batch):
             sopt.zero_grad()
-            out = R.forward(p, batch["mix"])
+            out = R.forward(p, batch["mix"], *emb(batch))
             pit_sisnr_loss(out["s1_pred"], out["s2_pred"], batch["s1"], batch["s2"]).backward()
             torch.nn.utils.clip_grad_norm_(list(p.values()), 8.0)
             sopt.step()
@@ -128,16 +153,16 @@ def main():
         torch.cuda.empty_cache()
     if a.no_baselines:
         print(json.dumps(res))
-        return
+        return res
     torch.set_num_threads(16)
     B = a.cpu_batch
     p = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     sopt = torch.optim.AdamW(list(p.values()), lr=1e-3)
-    batch = batch_of(B, torch.device("cpu"))
+    batch = batch_of(B, torch.device("cpu"), Tv)
 
     def cpu_step():
         sopt.zero_grad()
-        out = R.forward(p, batch["mix"])
+        out = R.forward(p, batch["mix"], *emb(batch))
         pit_sisnr_loss(out["s1_pred"], out["s2_pred"], batch["s1"], batch["s2"]).backward()
         torch.nn.utils.clip_grad_norm_(list(p.values()), 8.0)
         sopt.step()
@@ -145,9 +170,7 @@ def main():
     res["stock_cpu"][B] = {"ms": tc * 1e3, "mix_per_s": B / tc, "threads": 16}
     print(f"stock CPU B={B:2d} (16 threads): {tc * 1e3:8.1f} ms/step  {B / tc:8.2f} mixtures/s", flush=True)
     print(json.dumps(res))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    return res
 
 
 if __name__ == "__main__":
