@@ -78,6 +78,7 @@ DCTASNET_ABI_VERSION = 1
 CTTRAIN_ABI_VERSION = 1
 DCTTRAIN_ABI_VERSION = 1
 DAVTRAIN_ABI_VERSION = 1
+WAVLOSS_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -134,7 +135,7 @@ def _train_symbols(prefix, create_extra=(), shape_extra=(), forward_in=()):
     return {f"{prefix}_{k}": v for k, v in d.items()}
 
 
-# The five tables below are name -> (restype, argtypes), as SYMBOLS, for entry points of the same shared object.
+# The six tables below are name -> (restype, argtypes), as SYMBOLS, for entry points of the same shared object.
 #: every symbol include/ctasnet.h declares (Conv-TasNet forward)
 CTASNET_SYMBOLS = _infer_symbols("ctasnet")
 #: every symbol include/dctasnet.h declares (deep Conv-TasNet forward): create takes av, workspace_bytes and forward take Tv,
@@ -148,6 +149,14 @@ DCTTRAIN_SYMBOLS = _train_symbols("dcttrain", create_extra=[_i])
 #: every symbol include/davctasnet_train.h declares (deep audio-visual Conv-TasNet training step): every shape carries Tv and
 #: the two video streams follow the mixture
 DAVTRAIN_SYMBOLS = _train_symbols("davtrain", shape_extra=[_i], forward_in=[_fp, _fp])
+
+#: every symbol include/wavloss.h declares (waveform criteria: MAE / MSE / SI-SNR under batch or utterance PIT; stateless)
+WAVLOSS_SYMBOLS = {
+    "wavloss_abi_version": (_i, []),
+    "wavloss_strerror": (C.c_char_p, [_i]),
+    "wavloss_scratch_bytes": (_sz, [_i]),
+    "wavloss_pit_loss": (_i, [_i, _i, _fp, _fp, _fp, _fp, _i, _i64, C.c_float, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+}
 
 _lib: Optional[C.CDLL] = None
 
@@ -168,7 +177,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
-                              + list(DAVTRAIN_SYMBOLS.items())):
+                              + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -180,7 +189,8 @@ def load() -> C.CDLL:
                             (lib.dctasnet_abi_version, DCTASNET_ABI_VERSION, "dctasnet"),
                             (lib.cttrain_abi_version, CTTRAIN_ABI_VERSION, "cttrain"),
                             (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain"),
-                            (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain")):
+                            (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain"),
+                            (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -39,11 +39,13 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            # (Conv-TasNet training step), deepctasnet_train.hip (DeepConvTasNet and DeepAVConvTasNet training steps): each
            # instantiates the GEMM engine
            "ctasnet.hip": _GEMM_ENGINE_FLAGS, "deepctasnet.hip": _GEMM_ENGINE_FLAGS, "ctasnet_train.hip": _GEMM_ENGINE_FLAGS,
-           "deepctasnet_train.hip": _GEMM_ENGINE_FLAGS}
+           "deepctasnet_train.hip": _GEMM_ENGINE_FLAGS,
+           # wavloss.hip: the waveform criteria (MAE / MSE / SI-SNR, batch or utterance PIT), plain VALU
+           "wavloss.hip": []}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h")]
 
 
 def source_digest() -> str:

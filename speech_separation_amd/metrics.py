@@ -1,17 +1,20 @@
-"""PIT SI-SNR loss (forward + backward) and SI-SNR(i) metrics computed on the GPU.
+"""Waveform criteria (forward + backward) and SI-SNR(i) metrics computed on the GPU.
 
 Mirrors (does not import) the reference interfaces that consume the model's outputs:
   * ``SiSNRWavLoss()(**batch) -> {"loss": tensor}``          src/loss/ss_losses.py:117-130 (+ BaseSSLoss :21-26)
+  * ``MAEWavLoss()`` / ``MSEWavLoss()``, same call            src/loss/ss_losses.py:65-93   (+ BaseSSLoss :21-26)
   * ``SISNRiMetric(name=..., device=...)(**batch) -> value``  src/metrics/si_snri.py:7-30
   * ``SISNRMetric(name=..., device=...)(**batch) -> value``   src/metrics/si_snr.py:6-12
-Both resolve the speaker permutation at BATCH level (compare the two batch means), exactly as the reference does
-(ss_losses.py:21-25, base_metric.py:57-60) -- this is not per-utterance PIT.
+All resolve the speaker permutation at BATCH level by default (compare the two batch means), exactly as the reference
+does (ss_losses.py:21-25, base_metric.py:57-60) -- this is not per-utterance PIT.  The three criteria take
+``pit="utterance"`` for per-utterance PIT (include/wavloss.h: the reference's class on every item alone, averaged); the
+metrics stay batch level.
 
 The reference needs >= 6 ``.item()`` syncs per batch for the metrics (base_metric.py:53-56, si_snri.py:25-26); here the
 per-item statistics come from ``dptnav_sisnr_pairs`` (one launch) and the 12*B numbers are reduced on the host with ONE
-device->host copy.  The LOSS never touches the host: ``dptnav_pit_sisnr_loss`` resolves the permutation on the device,
-returns the loss as a 0-dim device tensor and leaves d loss / d prediction ready for ``loss.backward()`` (two launches
-instead of ~40 PyTorch kernels and a tensor->bool conversion).
+device->host copy.  The LOSS never touches the host: ``dptnav_pit_sisnr_loss`` / ``wavloss_pit_loss`` resolve the
+permutation on the device, return the loss as a 0-dim device tensor and leave d loss / d prediction ready for
+``loss.backward()`` (two launches instead of ~40 PyTorch kernels and a tensor->bool conversion).
 """
 from __future__ import annotations
 
@@ -58,12 +61,113 @@ class _PitSisnrFn(torch.autograd.Function):
         return g * d1, g * d2, None, None
 
 
-class SiSNRWavLoss(torch.nn.Module):
-    """The reference's PIT SI-SNR loss: ``SiSNRWavLoss()(**batch) -> {"loss": 0-dim tensor}`` (ss_losses.py:117-130),
-    differentiable w.r.t. s1_pred / s2_pred, no host synchronisation.  ``self.last`` keeps the device tensor
-    [loss, permutation, loss perm 0, loss perm 1] of the latest call for logging."""
+_KINDS = {"mae": 0, "mse": 1, "sisnr": 2}            # WAVLOSS_MAE / _MSE / _SISNR       (include/wavloss.h)
+_LEVELS = {"batch": 0, "utterance": 1}               # WAVLOSS_PIT_BATCH / _UTTERANCE
+
+
+def _check_pit(pit) -> str:
+    if pit not in _LEVELS:
+        raise ValueError(f"pit must be 'batch' or 'utterance', got {pit!r}")
+    return pit
+
+
+def _wav_inputs(s1_pred, s2_pred, s1, s2):
+    """Four fp32 tensors of one 2-D shape on one GPU -> detached, contiguous."""
+    named = (("s1_pred", s1_pred), ("s2_pred", s2_pred), ("s1", s1), ("s2", s2))
+    for n, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{n}: expected a torch.Tensor, got {type(t).__name__}")
+    dev = s1_pred.device
+    if dev.type != "cuda":
+        raise RuntimeError("speech_separation_amd.metrics computes on an AMD GPU through libdptnav; there is no CPU path")
+    for n, t in named:
+        if tuple(t.shape) != tuple(s1_pred.shape) or t.dim() != 2:
+            raise ValueError(f"{n}: shape {tuple(t.shape)} does not match s1_pred's {tuple(s1_pred.shape)}; the criterion takes "
+                             f"four [batch, samples] tensors of one shape (the reference would broadcast or fail here)")
+        if t.device != dev:
+            raise ValueError(f"{n}: lives on {t.device}, s1_pred on {dev}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{n}: expected float32, got {t.dtype}")
+    return [t.detach().contiguous() for _, t in named]
+
+
+def wavloss_pit_loss(kind: str, pit: str, s1_pred, s2_pred, s1, s2, grad_scale: float = 1.0):
+    """wavloss_pit_loss (include/wavloss.h) on the inputs' device and the current stream
+    -> (d loss / d s1_pred, d loss / d s2_pred, out[4] = loss, #items on permutation 1, L0, L1, perm int32 [B]);
+    all on the device, no synchronisation; scratch and outputs come from torch's allocator."""
+    from . import _lib
+    ts = _wav_inputs(s1_pred, s2_pred, s1, s2)
+    lib = _lib.load()
+    B, T = ts[0].shape
+    dev = ts[0].device
+    with torch.cuda.device(dev):
+        d1, d2 = torch.empty_like(ts[0]), torch.empty_like(ts[0])
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        perm = torch.empty(B, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.wavloss_scratch_bytes(max(B, 1))), dtype=torch.uint8, device=dev)
+        rc = lib.wavloss_pit_loss(_KINDS[kind], _LEVELS[pit], *[t.data_ptr() for t in ts], B, T, float(grad_scale),
+                                  d1.data_ptr(), d2.data_ptr(), out.data_ptr(), perm.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise RuntimeError(f"wavloss_pit_loss({kind}, {pit}, B={B}, T={T}): {lib.wavloss_strerror(rc).decode()}")
+    return d1, d2, out, perm
+
+
+class _PitWavFn(torch.autograd.Function):
+    """loss = BaseSSLoss(element loss) (ss_losses.py:21-26, :65-93, :100-114) or its per-utterance variant; the forward
+    launch pair already writes the gradient."""
+
+    @staticmethod
+    def forward(ctx, s1_pred, s2_pred, s1, s2, kind, pit):
+        d1, d2, out, perm = wavloss_pit_loss(kind, pit, s1_pred, s2_pred, s1, s2)
+        ctx.save_for_backward(d1, d2)
+        ctx.mark_non_differentiable(out, perm)
+        return out[0].clone(), out, perm
+
+    @staticmethod
+    def backward(ctx, g, _g_stats, _g_perm):
+        d1, d2 = ctx.saved_tensors
+        return g * d1, g * d2, None, None, None, None
+
+
+class _PitWavLoss(torch.nn.Module):
+    """``Loss(pit="batch")(**batch) -> {"loss": 0-dim device tensor}``, differentiable w.r.t. s1_pred / s2_pred, no host
+    synchronisation.  ``self.last`` keeps the device tensor [loss, #items on permutation 1, loss perm 0, loss perm 1] of
+    the latest call for logging, ``self.last_perm`` the int32 [B] permutation of every item."""
+
+    kind: str
+
+    def __init__(self, pit: str = "batch"):
+        super().__init__()
+        self.pit = _check_pit(pit)
+        self.last = self.last_perm = None
 
     def forward(self, s1_pred, s2_pred, s1, s2, **batch):
+        loss, self.last, self.last_perm = _PitWavFn.apply(s1_pred, s2_pred, s1, s2, self.kind, self.pit)
+        return {"loss": loss}
+
+
+class MAEWavLoss(_PitWavLoss):
+    """The reference's PIT L1 loss on waveforms (ss_losses.py:65-77), or its per-utterance variant (``pit="utterance"``)."""
+    kind = "mae"
+
+
+class MSEWavLoss(_PitWavLoss):
+    """The reference's PIT MSE loss on waveforms (ss_losses.py:80-93), or its per-utterance variant (``pit="utterance"``)."""
+    kind = "mse"
+
+
+class SiSNRWavLoss(_PitWavLoss):
+    """The reference's PIT SI-SNR loss: ``SiSNRWavLoss()(**batch) -> {"loss": 0-dim tensor}`` (ss_losses.py:117-130),
+    differentiable w.r.t. s1_pred / s2_pred, no host synchronisation.  With the default ``pit="batch"`` the call is
+    ``dptnav_pit_sisnr_loss`` and ``self.last`` keeps the device tensor [loss, permutation, loss perm 0, loss perm 1] of
+    the latest call for logging (``self.last_perm`` stays None); ``pit="utterance"`` goes through ``wavloss_pit_loss``
+    (``self.last`` / ``self.last_perm`` as MAEWavLoss)."""
+    kind = "sisnr"
+
+    def forward(self, s1_pred, s2_pred, s1, s2, **batch):
+        if self.pit != "batch":
+            return super().forward(s1_pred, s2_pred, s1, s2)
         loss, self.last = _PitSisnrFn.apply(s1_pred, s2_pred, s1, s2)
         return {"loss": loss}
 

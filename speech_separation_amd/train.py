@@ -6,12 +6,13 @@ Trainer.process_batch (src/trainer/trainer.py:13-59) with one-process-per-GPU da
 
 Every piece runs on the device without host synchronisation: the model's forward/backward are libdptnav kernels
 (model.py), the loss is `metrics.SiSNRWavLoss` (dptnav_pit_sisnr_loss: permutation resolved on the device, gradient
-written by the forward), the clip and AdamW are `optim.clip_grad_norm_` / `optim.FusedAdamW` over the model's ONE flat
-gradient tensor (17.8 MB), which is also what the data-parallel all-reduce reduces in place: on xGMI (7 point-to-point
+written by the forward) or `metrics.MAEWavLoss` / `MSEWavLoss` (wavloss_pit_loss, likewise), the clip and AdamW are
+`optim.clip_grad_norm_` / `optim.FusedAdamW` over the model's ONE flat gradient tensor (17.8 MB), which is also what the data-parallel all-reduce reduces in place: on xGMI (7 point-to-point
 links per GPU) one large collective beats 228 small ones; the global-norm clip runs after the all-reduce, as the
 reference's clip does on the full gradient (base_trainer.py:383-391).  The returned loss / gradient norm are 0-dim
 DEVICE tensors: reading them (logging, trainer.py:55) is the caller's only synchronisation, not one per step.
-PIT is batch level: every rank resolves the permutation on its own 16 mixtures (SURVEY.md 8e caveat).
+PIT is batch level by default: every rank resolves the permutation on its own 16 mixtures (SURVEY.md 8e caveat); the
+criteria's `pit="utterance"` resolves it per mixture, which does not depend on how the batch was cut.
 Stock torch.optim optimizers and torch.nn.utils.clip_grad_norm_ keep working (the parameters and .grad are ordinary
 tensors); `train_step` picks the fused clip whenever every `.grad` is a view of the drop-in's flat gradient and torch's otherwise
 (frozen parameters, gradient accumulation).
@@ -23,7 +24,7 @@ from typing import Dict, Mapping, Optional
 import torch
 from torch import nn
 
-from .metrics import SiSNRWavLoss  # noqa: F401  (re-export: the criterion of the training step)
+from .metrics import MAEWavLoss, MSEWavLoss, SiSNRWavLoss  # noqa: F401  (re-export: the criteria of the training step)
 from .optim import FusedAdamW, clip_grad_norm_, flat_grad_or_none  # noqa: F401
 from .parallel import DistEnv
 
