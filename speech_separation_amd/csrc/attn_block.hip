@@ -36,7 +36,6 @@ constexpr int N = 128, DH = 32;
 constexpr int LDX = N + 4;                  // token rows: conflict-free ds_read_b128 fragments
 constexpr int LDP = 136;                    // partial-tile row stride: rows 4 apart (the two lane halves) are 32 banks apart
 
-DEV float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // group_sum<32> of FOUR independent values, step by step side by side: one reduction is a chain of five dependent
 // cross-lane operations (each waits out the previous one's result), and the row-space code was four such passes one
 // after the other -- 2.6-2.9 k cycles per 32-row block in the phase stamps (tools/attn_stamps.py).
@@ -95,26 +94,6 @@ DEV void layernorm_rows_x4(float4 (&v)[4], const float4 ga, const float4 be) {
 }
 // MFMAs issued by iteration kb of the softmax pipeline: PV(kb-1) (kb > 0) + S(kb+1) (kb + 1 < nkb), 16 each
 constexpr int kb_mfmas(int kb, int nkb) { return (kb > 0 ? 16 : 0) + (kb + 1 < nkb ? 16 : 0); }
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
-
-// max / sum across the two 32-lane halves (lanes (c,0) and (c,1) hold the two halves of a query's keys)
-DEV float half_max(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-}
-DEV float half_sum(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
 
 // PRO = true: the block's input rows are not read from memory but PRODUCED here, as the second half of the PREVIOUS
 // TransformerDPRNN:  x = LayerNorm2(ReLU(h) W_f^T + b_f + y1_prev)  (dptn.py:50-51; K6 of dptnav.hip).  That GEMM is
@@ -622,12 +601,6 @@ DEV void split_row8(const float* p, bf16x8& hi, bf16x8& lo) {     // 8 consecuti
     hi[e] = h;
     lo[e] = l;
   }
-}
-// three-term product on split operands
-DEV f32x16 mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x16 c) {
-  c = mfma32_bf16(ah, bh, c);
-  c = mfma32_bf16(ah, bl, c);
-  return mfma32_bf16(al, bh, c);
 }
 
 constexpr int LDXB = N + 8;                 // bf16 token rows (272 bytes): conflict-free ds_read_b128 fragments

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "attn_block.h"
+#include "vmem_asm.h"
 
 namespace {
 
@@ -34,65 +35,7 @@ constexpr int LDX = N + 4;                  // token rows: conflict-free ds_read
 constexpr int LDHC = 256 + 4;               // h rows (1 040 bytes: a DMA request per row, 16-byte aligned)
 constexpr int OB_FLOATS = 4 * 4 * 64 * 4;   // O^T exchange: [head][j][lane][4]
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-DEV float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-DEV uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-// One LDS-DMA request: lane L's 16 bytes at (wave-uniform base + voff) land at LDS byte address lds_base + 16 L.  Inline assembly on
-// purpose (fcln.hip has the long version): issued through the builtin, the compiler waits with vmcnt(0) in front of every later LDS
-// access.  Every wait on this traffic is written by hand below.  (s_nop: the wait state the ISA asks for between a scalar write of
-// M0 and an LDS-DMA that reads it; the hazard recogniser does not look into inline assembly.)
-DEV void dma_row(const void* sbase, uint32_t voff, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base), "v"(voff), "s"(sbase) : "memory", "m0");
-}
-// a fragment load the compiler does not count (same reason): 16 bytes at base + voff + OFF
-template <int OFF>
-DEV void ldg4_uncounted(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-// ... into the AGPR half of the register file (the W_f fragments: A operands of the prologue's MFMAs, which read them there)
-template <int OFF>
-DEV void ldg4_uncounted_a(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=a"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-// wait until at most KEEP of this wave's vector-memory requests are outstanding; sixteen AGPR quads are operands so that no use of
-// them can be scheduled in front of the wait (an asm statement takes at most 30 operands: call it once per half of W_f)
-template <int KEEP>
-DEV void wait_vm_a16(f32x4* r) {
-  asm volatile("s_waitcnt vmcnt(%[n])"
-               : "+a"(r[0]), "+a"(r[1]), "+a"(r[2]), "+a"(r[3]), "+a"(r[4]), "+a"(r[5]), "+a"(r[6]), "+a"(r[7]), "+a"(r[8]), "+a"(r[9]),
-                 "+a"(r[10]), "+a"(r[11]), "+a"(r[12]), "+a"(r[13]), "+a"(r[14]), "+a"(r[15])
-               : [n] "n"(KEEP)
-               : "memory");
-}
-// wait until at most KEEP of this wave's vector-memory requests are outstanding; the four registers are operands so that no use
-// of them can be scheduled in front of the wait
-template <int KEEP>
-DEV void wait_vm(f32x4 (&r)[4]) {
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : [n] "n"(KEEP) : "memory");
-}
-
 constexpr int kb_mfmas(int kb, int nkb) { return (kb > 0 ? 16 : 0) + (kb + 1 < nkb ? 16 : 0); }
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
-
-// max / sum across the two 32-lane halves (lanes (c,0) and (c,1) hold the two halves of a query's keys / a token's columns)
-DEV float half_max(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-}
-DEV float half_sum(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
 
 // ---- LayerNorm over 128 columns held as 4 waves x (lane pair x 16 registers) -------------------------------------------------
 // Step 1 (per wave): mean and centred sum of squares of the wave's 32 columns of token c; v becomes v - mean_w.
@@ -255,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
       constexpr int rb = decltype(RB)::value;
       int row = rb * 32 + 8 * h + i;
       if (rb == NKB - 1) row = row < len ? row : len - 1;
-      dma_row(hbase + (uint32_t)row * rs_h, lane16, hbuf_lds(rb) + (uint32_t)((8 * h + i) * LDHC * 4));
+      dma_part<false>(hbase + (uint32_t)row * rs_h, lane16, hbuf_lds(rb) + (uint32_t)((8 * h + i) * LDHC * 4));
     };
     auto issue_r1 = [&](auto RB, f32x4 (&rr)[4], int j) {
       constexpr int rb = decltype(RB)::value;

@@ -39,10 +39,7 @@ constexpr int LDX = N + 4;                  // token rows: conflict-free ds_read
 constexpr int LDP = N + 4;                  // partial tiles / product tile
 constexpr int KF = 256, LDHC = KF + 4;      // ReLU(h) rows of the prologue
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 DEV f32x4v zero4() { return (f32x4v){0.f, 0.f, 0.f, 0.f}; }
-DEV float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // max / sum over the four lanes (i16, ks = 0..3) that share a query: lanes 16 and 32 apart
 DEV float quad_rows_max(float v) {
@@ -69,15 +66,6 @@ DEV float4 layernorm_row16(float4 v, const float4 ga, const float4 be) {
   const float var = group_sum<16>((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w)) * (1.0f / N);
   const float rstd = rsqrtf(var + 1e-5f);
   return make_float4(v.x * rstd * ga.x + be.x, v.y * rstd * ga.y + be.y, v.z * rstd * ga.z + be.z, v.w * rstd * ga.w + be.w);
-}
-
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
 }
 
 struct FfnPro64 {

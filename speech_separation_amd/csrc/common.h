@@ -37,6 +37,36 @@ DEV void split_bf16(float x, __bf16& hi, __bf16& lo) {
 
 DEV f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 DEV f32x16 mfma32_bf16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+// three-term product on split operands (hi hi + hi lo + lo hi)
+DEV f32x16 mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x16 c) {
+  c = mfma32_bf16(ah, bh, c);
+  c = mfma32_bf16(ah, bl, c);
+  return mfma32_bf16(al, bh, c);
+}
+// v_mfma_f32_16x16x4_f32 (16-token tiles): lane l: i16 = l & 15, ks = l >> 4; A[i16][ks], B[ks][i16], D reg r = (row 4 ks + r, col i16)
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N_ - 1>): a loop whose index is a constant expression in the body
+template <class F, int... I>
+DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N_, class F>
+DEV void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N_>{});
+}
+
+DEV float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// LDS-DMA through the builtin (compiler-counted) with an immediate offset, applied to the global AND the LDS address
+template <int OFF>
+DEV void glds16_off(const float* gsrc, float* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, OFF, 0);
+}
+// ReLU in ONE instruction (v_max_i32 on the bit pattern: negative floats are negative integers): fmaxf on a value that comes
+// from memory costs a canonicalising v_max_f32 first
+DEV float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
 DEV f32x16 zero16() {
   f32x16 z;
@@ -94,6 +124,17 @@ DEV float group_sum(float v) {
     v = __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
   }
   return v;
+}
+// max / sum across the two 32-lane halves: lanes (c, 0) and (c, 1) hold the two halves of a query's keys / a token's columns
+DEV float half_max(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+DEV float half_sum(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
 }
 
 // Counter-based dropout randomness for the attention probabilities (train mode, dptn.py:16-21): a pure function of

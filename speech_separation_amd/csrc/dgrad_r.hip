@@ -23,62 +23,9 @@
 
 #include "common.h"
 #include "dgrad_r.h"
+#include "vmem_asm.h"
 
 namespace {
-
-DEV uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-// LDS-DMA request (dgrad_t.hip): lane L's 16 bytes at (base + voff) -> LDS lds_base + 16 L; HALF: lanes 0..31 only (512 bytes).
-// s_nop 4 in EVERY asm statement here that issues a vector-memory instruction with a scalar operand: the operand may have been
-// written by a VALU instruction just in front of the statement (v_readlane of a spilled SGPR, v_readfirstlane), the ISA asks for
-// five wait states between such a write and a VMEM instruction that reads the register, and the compiler's recogniser does not
-// look into inline assembly.  Found on the hardware: this kernel has SGPR spills, and a request went out with a stale base
-// (memory access fault at M = 4 097; none at M = 1 or 33 -- the hazard depends on what the allocator put in front of the statement).
-template <bool HALF>
-DEV void dma_part(const void* sbase, uint32_t voff, uint32_t lds_base) {
-  if constexpr (!HALF) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base), "v"(voff), "s"(sbase) : "memory", "m0");
-  } else {
-    uint32_t saved;
-    asm volatile("s_mov_b32 m0, %1\n\ts_mov_b32 %0, exec_hi\n\ts_mov_b32 exec_hi, 0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 exec_hi, %0"
-                 : "=&s"(saved)
-                 : "s"(lds_base), "v"(voff), "s"(sbase)
-                 : "memory", "m0");
-  }
-}
-template <int OFF>
-DEV void ldg4_uncounted(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-// (s_nop: a store of more than 8 bytes reads its data registers for a few cycles after issue -- dgrad_t.hip)
-template <int OFF>
-DEV void stg4_uncounted(void* sbase, uint32_t voff, f32x4 v) {
-  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase), "n"(OFF) : "memory");
-}
-template <int KEEP>
-DEV void wait_vm_v16(f32x4* r) {
-  asm volatile("s_waitcnt vmcnt(%[n])"
-               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]),
-                 "+v"(r[10]), "+v"(r[11]), "+v"(r[12]), "+v"(r[13]), "+v"(r[14]), "+v"(r[15])
-               : [n] "n"(KEEP)
-               : "memory");
-}
-template <int KEEP>
-DEV void wait_vm1(int& r) {
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r) : [n] "n"(KEEP) : "memory");
-}
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
-DEV float half_sum(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
 
 constexpr int KIN = 128, CH = KIN / 8;      // 16 k-chunks
 
@@ -94,9 +41,11 @@ struct DgradRShape {
   static constexpr size_t lds_bytes() { return sizeof(float) * (4 + 2 * (size_t)STAGE); }
 };
 
-// Vector-memory operations of a wave inside tile i, in issue order (the waits are derived from it, as in dgrad_t.hip):
+// Vector-memory operations of a wave inside tile i, in issue order (the waits are derived from it):
 //     [ticket atomic, one lane] | rows(i + 1) x 16 behind the 16 k-chunks of the data gradient [HN] | stores(i - 1) x NS between the
-//     rider's MFMAs [HP]        -- end of the tile: rows(i + 1) must be in -> at most (HP ? NS : 0) younger operations outstanding
+//     rider's MFMAs [HP]        -- end of the tile: rows(i + 1) must be in -> at most (HP ? NS : 0) younger operations outstanding [HN]
+//     -- last tile, in front of its own stores: the ticket atomic must be back -> at most (HP ? NS : 0), the stores(i - 1) [!HN]; the
+//        slab and column-sum epilogue then runs with nothing of the atomic in flight
 template <int NOUT, bool GATE>
 __global__ __launch_bounds__(256) void dgrad_r_kernel(const float* __restrict__ A, const float* __restrict__ Wp, const float* __restrict__ X,
                                                       float* __restrict__ out, int64_t M, int ntiles, unsigned* queue,
@@ -104,6 +53,8 @@ __global__ __launch_bounds__(256) void dgrad_r_kernel(const float* __restrict__ 
   using Sh = DgradRShape<NOUT>;
   constexpr int NT = Sh::NT, CB = Sh::CB, LDA = Sh::LDA, LDX = Sh::LDX, STAGE = Sh::STAGE, NS = Sh::NS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  // The ticket protocol of vmem_asm.h's TicketLoop, written out: on the struct this kernel's generated tile loop came out with
+  // other scalar registers (it is the one with SGPR spills), so it keeps the text its code was verified with.
   int* s_next = reinterpret_cast<int*>(smem);      // [2] tile tickets
   float* St = smem + 4;                            // [2][ A [32][LDA] | X [32][LDX] ]
   const int tid = threadIdx.x;
@@ -278,7 +229,10 @@ __global__ __launch_bounds__(256) void dgrad_r_kernel(const float* __restrict__ 
       }
     pbase = obase;
     poff = eoff;
-    if constexpr (!HN) static_for<NS>([&](auto J) { store_piece(pbase, poff, J); });
+    if constexpr (!HN) {
+      retire_vm1<HP ? NS : 0>(ticket_ahead);      // the ticket nobody will use is back: its register stays its own until here
+      static_for<NS>([&](auto J) { store_piece(pbase, poff, J); });
+    }
     // the next tile's rows (this wave's requests) are in; the ticket requested in front of them is older still
     if constexpr (HN) wait_vm1<HP ? NS : 0>(ticket_ahead);
   };

@@ -29,70 +29,9 @@
 
 #include "common.h"
 #include "dgrad_t.h"
+#include "vmem_asm.h"
 
 namespace {
-
-DEV uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-// One LDS-DMA request (global_load_lds_dwordx4): lane L's 16 bytes at (wave-uniform base + voff) land at LDS byte address
-// lds_base + 16 L (attn_block2.hip).  HALF: only lanes 0..31 take part (512 bytes: the tail of a 1 536-byte row) -- the upper half
-// of EXEC is cleared around the request inside the one asm statement (EXEC is full wherever this is called).  s_nop: the wait
-// state the ISA asks for between a scalar write of M0 and an LDS-DMA that reads it (the hazard recogniser does not look into
-// inline assembly).
-template <bool HALF>
-DEV void dma_part(const void* sbase, uint32_t voff, uint32_t lds_base) {
-  if constexpr (!HALF) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base), "v"(voff), "s"(sbase) : "memory", "m0");
-  } else {
-    uint32_t saved;
-    asm volatile("s_mov_b32 m0, %1\n\ts_mov_b32 %0, exec_hi\n\ts_mov_b32 exec_hi, 0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 exec_hi, %0"
-                 : "=&s"(saved)
-                 : "s"(lds_base), "v"(voff), "s"(sbase)
-                 : "memory", "m0");
-  }
-}
-// fragment load / store the compiler does not count: 16 bytes at base + voff + OFF
-template <int OFF>
-DEV void ldg4_uncounted(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-// ... into the AGPR half of the register file
-template <int OFF>
-DEV void ldg4_uncounted_a(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=a"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-template <int OFF>
-DEV void stg4_uncounted(void* sbase, uint32_t voff, f32x4 v) {
-  // (s_nop: a store of more than 8 bytes reads its data registers for a few cycles after issue, and the hazard recogniser does
-  //  not look into inline assembly -- without it the next VALU write to `v` changed what lanes 8-15 / 24-31 of each half stored)
-  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase), "n"(OFF) : "memory");
-}
-// wait until at most KEEP of this wave's vector-memory operations are outstanding; the registers are operands so that no use of
-// them is scheduled in front of the wait
-template <int KEEP>
-DEV void wait_vm(f32x4 (&r)[4]) {
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : [n] "n"(KEEP) : "memory");
-}
-template <int KEEP>
-DEV void wait_vm_a16(f32x4* r) {
-  asm volatile("s_waitcnt vmcnt(%[n])"
-               : "+a"(r[0]), "+a"(r[1]), "+a"(r[2]), "+a"(r[3]), "+a"(r[4]), "+a"(r[5]), "+a"(r[6]), "+a"(r[7]), "+a"(r[8]), "+a"(r[9]),
-                 "+a"(r[10]), "+a"(r[11]), "+a"(r[12]), "+a"(r[13]), "+a"(r[14]), "+a"(r[15])
-               : [n] "n"(KEEP)
-               : "memory");
-}
-template <int KEEP>
-DEV void wait_vm1(int& r) {
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r) : [n] "n"(KEEP) : "memory");
-}
-
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
 
 constexpr int NOUT = 128;
 
@@ -133,7 +72,8 @@ struct DgradTShape {
 //     [ticket atomic, one lane]  |  addend(i) x 4  |  rows(i + 1) x NREQ, from the start of the MFMA block   [a next tile exists: HN]
 //                                |  stores(i - 1) x 4, behind them                                         [a previous tile: HP]
 //     -- end of the block: addend(i) must be in      -> at most (HN ? NREQ : 0) + (HP ? 4 : 0) younger operations outstanding
-//     -- end of the tile:  rows(i + 1) must be in    -> at most (HP ? 4 : 0)
+//     -- end of the tile:  rows(i + 1) must be in    -> at most (HP ? 4 : 0)                                   [HN]
+//     -- last tile, in front of its own stores: the ticket atomic must be back -> at most (HP ? 4 : 0): stores(i - 1)  [!HN]
 // The results of a tile stay in 16 registers and leave one store at a time between the MFMAs of the NEXT tile (four stores back
 // to back cost 600 of a tile's 18.8 k cycles: phase stamps, tools/microbench/dgrad_t_check.hip); the last tile stores at once.
 // Tokens beyond M: their lanes carry copies of token M - 1 through the same arithmetic (rows and addend are clamped, read before
@@ -145,23 +85,13 @@ __global__ __launch_bounds__(256) void dgrad_t_kernel(const float* __restrict__ 
   constexpr int LDA = Sh::LDA, BUF = Sh::BUF, RPR = Sh::RPR, NREQ = Sh::NREQ, CH = Sh::CH, NB = Sh::NB;
   static_assert(2 * (NREQ + 4) <= CH, "one request, then one store, behind every second k-chunk");
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int* s_next = reinterpret_cast<int*>(smem);      // [2] tile tickets
-  float* As = smem + 4;                            // [2][32][LDA]
+  float* As = smem + 4;                            // [2][32][LDA], behind the [2] tile tickets
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, c = lane & 31, hh = lane >> 5;
-  const bool dyn = queue != nullptr;
-  int ticket_ahead = 0;
-  if (dyn) {
-    if (tid == 0) {
-      s_next[0] = (int)atomicAdd(queue, 1u);
-      ticket_ahead = (int)atomicAdd(queue, 1u);
-    }
-  } else if (tid == 0) {
-    s_next[0] = (int)blockIdx.x;
-  }
+  TicketLoop tk(reinterpret_cast<int*>(smem), queue, ntiles);
   __syncthreads();
-  int tile = __builtin_amdgcn_readfirstlane(s_next[0]);
+  int tile = tk.first_tile();
   if (tile >= ntiles) return;
 
   const uint32_t lane16 = (uint32_t)lane * 16u;
@@ -216,6 +146,7 @@ __global__ __launch_bounds__(256) void dgrad_t_kernel(const float* __restrict__ 
   };
   auto body = [&](auto HAS_NEXT, auto HAS_PREV, int next) {
     constexpr bool HN = decltype(HAS_NEXT)::value, HP = decltype(HAS_PREV)::value;
+    DGT_MARK(1)      // the barrier (and the ticket's hand-over behind it)
     const int64_t tok0 = (int64_t)tile * 32;
     const int last = (int)(M - 1 - tok0 < 31 ? M - 1 - tok0 : 31);      // wave-uniform
     const uint32_t eoff = (uint32_t)(((c < last ? c : last) * NOUT + 32 * w + 4 * hh) * 4);
@@ -279,26 +210,20 @@ __global__ __launch_bounds__(256) void dgrad_t_kernel(const float* __restrict__ 
     pbase = obase;
     poff = eoff;
     if constexpr (!HN) {
+      tk.retire<HP ? 4 : 0>();      // the ticket nobody will use is back: its register stays its own until here
 #pragma unroll
       for (int j = 0; j < 4; ++j) store_piece(pbase, poff, j);
     }
     DGT_MARK(3)
     // the next tile's rows (this wave's requests) are in; the ticket requested in front of the addend is older still
-    if constexpr (HN) wait_vm1<HP ? 4 : 0>(ticket_ahead);
+    if constexpr (HN) tk.wait<HP ? 4 : 0>();
     DGT_MARK(4)
   };
 
+  // (the four-way dispatch of TicketLoop::run, written out: through run() this kernel's generated tile loop came out different)
   bool first = true;
   while (true) {
-    if (dyn && tid == 0) s_next[buf ^ 1] = ticket_ahead;      // the ticket AFTER the next one, requested a tile ago
-    __syncthreads();      // every wave's rows of `tile` are in LDS; everyone is through with the other buffer
-    DGT_MARK(1)
-    const int next = dyn ? __builtin_amdgcn_readfirstlane(s_next[buf ^ 1]) : tile + (int)gridDim.x;
-    if (dyn && tid == 0) {
-      // uncounted like the rest (a counted atomic would make the compiler wait for everything, stores included, where the
-      // ticket is published); the wait at the end of the tile covers it
-      asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(ticket_ahead) : "v"(0u), "v"(1u), "s"(queue) : "memory");
-    }
+    const int next = tk.next_tile(tile, buf);
     if (next < ntiles) {
       if (first) body(std::true_type{}, std::false_type{}, next);
       else body(std::true_type{}, std::true_type{}, next);

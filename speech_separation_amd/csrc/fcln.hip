@@ -22,22 +22,9 @@
 
 #include "common.h"
 #include "fcln.h"
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+#include "vmem_asm.h"
 
 namespace {
-
-// One LDS-DMA request of the wave: lane L's 16 bytes at `g` land at LDS byte address lds_base + 16 L.  Issued as inline assembly ON
-// PURPOSE: the compiler then does not know that memory -> LDS traffic is outstanding.  If it knows (the builtin), it puts
-// s_waitcnt vmcnt(0) in front of EVERY LDS access that follows -- it cannot tell the buffers apart -- and a wave sits out the whole
-// latency of the tiles it has just requested, each iteration.  The price: every wait on this traffic is written by hand below.
-static __device__ __forceinline__ void dma16(const void* g, uint32_t lds_base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_base), "v"(g) : "memory", "m0");
-}
-static __device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
 
 // ACT: what A is read through (0 nothing, 1 ReLU, 2 PReLU with the shared slope *act_w); LN: LayerNorm + residual epilogue (else
 // bias + store: no residual tile is fetched); PRE: the residual goes in before the LayerNorm; SAVE: normalised rows + 1/sigma out

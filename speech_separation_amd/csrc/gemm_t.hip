@@ -17,77 +17,31 @@
 
 #include "common.h"
 #include "gemm_t.h"
+#include "vmem_asm.h"
 
 namespace {
-
-DEV uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-// (s_nop 4 / s_nop 1: the wait states of dgrad_r.hip -- a VALU-written scalar operand in front of the statement, a 16-byte store's data)
-DEV void dma_half(const void* sbase, uint32_t voff, uint32_t lds_base) {      // lanes 0..31: 512 bytes -> LDS lds_base + 16 L
-  uint32_t saved;
-  asm volatile("s_mov_b32 m0, %1\n\ts_mov_b32 %0, exec_hi\n\ts_mov_b32 exec_hi, 0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 exec_hi, %0"
-               : "=&s"(saved)
-               : "s"(lds_base), "v"(voff), "s"(sbase)
-               : "memory", "m0");
-}
-template <int OFF>
-DEV void ldg4_uncounted_a(f32x4& dst, const void* sbase, uint32_t voff) {
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=a"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-template <int OFF>
-DEV void stg4_uncounted(void* sbase, uint32_t voff, f32x4 v) {
-  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase), "n"(OFF) : "memory");
-}
-template <int KEEP>
-DEV void wait_vm_a16(f32x4* r) {
-  asm volatile("s_waitcnt vmcnt(%[n])"
-               : "+a"(r[0]), "+a"(r[1]), "+a"(r[2]), "+a"(r[3]), "+a"(r[4]), "+a"(r[5]), "+a"(r[6]), "+a"(r[7]), "+a"(r[8]), "+a"(r[9]),
-                 "+a"(r[10]), "+a"(r[11]), "+a"(r[12]), "+a"(r[13]), "+a"(r[14]), "+a"(r[15])
-               : [n] "n"(KEEP)
-               : "memory");
-}
-template <int KEEP>
-DEV void wait_vm1(int& r) {
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r) : [n] "n"(KEEP) : "memory");
-}
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-DEV void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
 
 constexpr int KIN = 128, CH = KIN / 8, LDA = KIN + 4;
 
 // Vector-memory operations of a wave inside tile i, in issue order: [ticket atomic, one lane] | rows(i + 1) x 8 [HN] | stores(i - 1)
 // x NS [HP] (two slots per k-chunk: the requests first, the stores behind them) -- end of the tile: rows(i + 1) must be in -> at most
-// (HP ? NS : 0) younger operations outstanding.
+// (HP ? NS : 0) younger operations outstanding [HN]; last tile, in front of its own stores: the ticket atomic must be back -> at most
+// (HP ? NS : 0), the stores(i - 1) [!HN].
 template <int NOUT>
 __global__ __launch_bounds__(256) void gemm_t_kernel(const float* __restrict__ A, const float* __restrict__ Wp, const float* __restrict__ bias,
                                                      float* __restrict__ out, int64_t M, int ntiles, unsigned* queue) {
   constexpr int NT = NOUT / 128, NS = 4 * NT, WCOLS = NOUT / 4;
   static_assert(8 + NS <= 2 * CH, "two request slots per k-chunk");
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  int* s_next = reinterpret_cast<int*>(smem);      // [2] tile tickets
-  float* Bs = smem + 4;                            // [NOUT] bias
+  float* Bs = smem + 4;                            // [NOUT] bias, behind the [2] tile tickets
   float* As = Bs + NOUT;                           // [2][32][LDA]
   const int tid = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, c = lane & 31, hh = lane >> 5;
-  const bool dyn = queue != nullptr;
-  int ticket_ahead = 0;
-  if (dyn) {
-    if (tid == 0) {
-      s_next[0] = (int)atomicAdd(queue, 1u);
-      ticket_ahead = (int)atomicAdd(queue, 1u);
-    }
-  } else if (tid == 0) {
-    s_next[0] = (int)blockIdx.x;
-  }
+  TicketLoop tk(reinterpret_cast<int*>(smem), queue, ntiles);
   for (int i = tid; i < NOUT; i += 256) Bs[i] = bias[i];
   __syncthreads();
-  int tile = __builtin_amdgcn_readfirstlane(s_next[0]);
+  int tile = tk.first_tile();
   if (tile >= ntiles) return;
 
   const uint32_t lane16 = (uint32_t)lane * 16u;
@@ -97,7 +51,7 @@ __global__ __launch_bounds__(256) void gemm_t_kernel(const float* __restrict__ A
     const int row = 8 * w + r;
     int64_t grow = (int64_t)t * 32 + row;
     grow = grow < M ? grow : M - 1;
-    dma_half(Ab + grow * (KIN * 4), lane16, as_lds + (uint32_t)((b * 32 + row) * LDA * 4));
+    dma_part<true>(Ab + grow * (KIN * 4), lane16, as_lds + (uint32_t)((b * 32 + row) * LDA * 4));
   };
 #pragma unroll
   for (int r = 0; r < 8; ++r) issue_req(tile, 0, r);
@@ -176,29 +130,14 @@ __global__ __launch_bounds__(256) void gemm_t_kernel(const float* __restrict__ A
         res[4 * nt + jj] = (f32x4){acc[nt][4 * jj], acc[nt][4 * jj + 1], acc[nt][4 * jj + 2], acc[nt][4 * jj + 3]};
     pbase = obase;
     poff = eoff;
-    if constexpr (!HN) static_for<NS>([&](auto J) { store_piece(pbase, poff, J); });
-    if constexpr (HN) wait_vm1<HP ? NS : 0>(ticket_ahead);      // the next tile's rows (this wave's requests) are in
+    if constexpr (!HN) {
+      tk.retire<HP ? NS : 0>();      // the ticket nobody will use is back: its register stays its own until here
+      static_for<NS>([&](auto J) { store_piece(pbase, poff, J); });
+    }
+    if constexpr (HN) tk.wait<HP ? NS : 0>();      // the next tile's rows (this wave's requests) are in
   };
 
-  bool first = true;
-  while (true) {
-    if (dyn && tid == 0) s_next[buf ^ 1] = ticket_ahead;      // the ticket AFTER the next one, requested a tile ago
-    __syncthreads();      // every wave's rows of `tile` are in LDS; everyone is through with the other buffer
-    const int next = dyn ? __builtin_amdgcn_readfirstlane(s_next[buf ^ 1]) : tile + (int)gridDim.x;
-    if (dyn && tid == 0)
-      asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(ticket_ahead) : "v"(0u), "v"(1u), "s"(queue) : "memory");
-    if (next < ntiles) {
-      if (first) body(std::true_type{}, std::false_type{}, next);
-      else body(std::true_type{}, std::true_type{}, next);
-      first = false;
-      tile = next;
-      buf ^= 1;
-    } else {
-      if (first) body(std::false_type{}, std::false_type{}, next);
-      else body(std::false_type{}, std::true_type{}, next);
-      break;
-    }
-  }
+  tk.run(tile, buf, body);
 }
 
 }  // namespace

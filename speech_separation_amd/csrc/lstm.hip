@@ -20,14 +20,6 @@
 
 #include "lstm.h"
 
-template <int OFF>
-DEV void glds16_off(const float* gsrc, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, OFF, 0);
-}
-// ReLU in ONE instruction on a value that comes from memory (fmaxf would canonicalise first)
-DEV float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-
 template <bool STAMP, bool SAVE, bool RELU>
 __global__ __launch_bounds__(256) void lstm_recurrence_kernel(const float* __restrict__ pre,
                                                                const float* __restrict__ whh_f,

@@ -25,21 +25,6 @@
 
 #include "lstm16.h"
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// LDS-DMA with an immediate offset (applied to the global AND the LDS address)
-template <int OFF>
-DEV void glds16_off(const float* gsrc, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, OFF, 0);
-}
-
-// ReLU in ONE instruction (v_max_i32 on the bit pattern: negative floats are negative integers): fmaxf on a value
-// that comes from memory costs a canonicalising v_max_f32 first
-DEV float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-
-
 // STAMP: diagnostic build, per-wave s_memtime sums of [init, MFMA block (with the interleaved cell update), exposed
 // cell update, barrier] go to stamps[dir][tile][wave][4].  DIAG (timing-only ablations, results are wrong):
 // bit 0 no LDS-DMA, bit 1 no h stores, bit 3 identity activations.

@@ -22,9 +22,6 @@
 #include "lstm.h"
 #include "lstm16.h"
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int LDB = L16_H + 8;                         // bf16 row stride (272 bytes): conflict-free ds_read_b128 fragments
@@ -32,13 +29,6 @@ constexpr int HB_ELEMS = 2 * 16 * LDB;                 // one bf16 image, double
 
 
 DEV f32x4v mfma_bf16(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-template <int OFF>
-DEV void glds16_off(const float* gsrc, float* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, OFF, 0);
-}
-DEV float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
 template <bool RELU>
 __global__ __launch_bounds__(256) void lstm16s_kernel(const float* __restrict__ pre, const float* __restrict__ whh_f,
@@ -216,12 +206,6 @@ __global__ __launch_bounds__(256) void lstm16s_kernel(const float* __restrict__ 
 constexpr int LDB32 = LSTM_H + 8;
 constexpr int HB32_ELEMS = 2 * 32 * LDB32;
 constexpr size_t LDS32_BYTES = LSTM_LDS_BYTES + sizeof(__bf16) * 2 * HB32_ELEMS;
-
-DEV f32x16 mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x16 c) {
-  c = mfma32_bf16(ah, bh, c);
-  c = mfma32_bf16(ah, bl, c);
-  return mfma32_bf16(al, bh, c);
-}
 
 template <bool RELU>
 __global__ __launch_bounds__(256) void lstm32s_kernel(const float* __restrict__ pre, const float* __restrict__ whh_f,

@@ -18,10 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lstm16.h"
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-static __device__ __forceinline__ f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-static __device__ __forceinline__ float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
+#include "vmem_asm.h"
 
 namespace {
 
@@ -264,15 +261,6 @@ constexpr int X128_XS_FLOATS = 16 * 128;                       // one step's inp
 constexpr size_t X128_LDS_BYTES = sizeof(float) * (X128_WL_FLOATS + L16_HS_FLOATS + 2 * X128_XS_FLOATS);
 static_assert(X128_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-template <class F, int... I>
-static __device__ __forceinline__ void x16_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N_, class F>
-static __device__ __forceinline__ void x16_static_for(F&& f) {
-  x16_static_for_impl(f, std::make_integer_sequence<int, N_>{});
-}
-
 template <bool RELU>
 __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ wih_f,
                                                           const float* __restrict__ wih_b, const float* __restrict__ bih_f,
@@ -366,16 +354,14 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
     const int64_t tokb = seq_token_base(g, q < g.nseq ? q : g.nseq - 1);
     xp[i] = (unsigned)(((tokb + (int64_t)t0 * tstride) * ldx + 4 * ((lane & 31) ^ (row & 15))) * 4);
   }
-  // Issued as inline assembly ON PURPOSE (fcln.hip has the long version): through __builtin_amdgcn_global_load_lds the compiler knows
-  // that memory -> LDS traffic is outstanding and, unable to tell the buffers apart, puts s_waitcnt vmcnt(0) in front of the NEXT LDS
-  // access -- here the a_next fragment read eleven instructions behind the request, so every step sat out the round trip of the rows
-  // it had just asked for (rounds 4's kernel: line `s_waitcnt vmcnt(0)` right behind the two requests).  The one wait
-  // this traffic needs is written by hand at the end of the step.
-  const uint32_t xs_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)Xs;
+  // Hand-issued (vmem_asm.h): through the builtin the compiler put s_waitcnt vmcnt(0) in front of the NEXT LDS access -- here the
+  // a_next fragment read eleven instructions behind the request, so every step sat out the round trip of the rows it had just asked
+  // for.  The one wait this traffic needs is written by hand at the end of the step.
+  const uint32_t xs_lds = lds_addr(Xs);
   auto dma_x = [&](int s, int buf, int i) {        // x_s -> Xs[buf], this wave's request i
     const unsigned adv = (unsigned)(s < g.len ? s : g.len - 1) * xstep;
     const uint32_t dst = xs_lds + (uint32_t)((buf * X128_XS_FLOATS + (2 * w + i) * 256) * 4);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(xp[i] + adv), "s"(x) : "memory", "m0");
+    dma_part<false>(x, xp[i] + adv, dst);
   };
   dma_x(0, 0, 0); dma_x(0, 0, 1);
   dma_x(1, 1, 0); dma_x(1, 1, 1);
@@ -450,7 +436,7 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
     };
     request(std::integral_constant<int, 0>{}, fa[0], wl_lds);
     float4 xa_next = xa;
-    x16_static_for<16>([&](auto CH) {
+    static_for<16>([&](auto CH) {
       constexpr int ch = decltype(CH)::value, p0 = 32 + 2 * ch, m = p0 >> 3;
       if constexpr ((p0 & 7) == 0 && m + 1 < 8) xa_next = *reinterpret_cast<const float4*>(xrow + 16 * (((m + 1) & 3) ^ xq) + 64 * ((m + 1) >> 2));
       // this pair's sets have landed (nothing else of this wave is outstanding on the LDS counter that is younger)

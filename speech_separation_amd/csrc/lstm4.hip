@@ -27,10 +27,6 @@
 
 #include "lstm16.h"
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-DEV float relu1_l4(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
-
 template <int ABID>
 DEV f32x4v mfma4(float a, float b, f32x4v c) {
   return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, ABID, 0);
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(256) void lstm4_kernel(const float* __restrict__ pr
       hnext[h_off] = cu.h.x;
       hnext[h_off + 16 * 8] = cu.h.y;
       // h_t leaves for HBM from the registers (position t of the lane's two sequences)
-      const float o0 = RELU ? relu1_l4(cu.h.x) : cu.h.x, o1 = RELU ? relu1_l4(cu.h.y) : cu.h.y;
+      const float o0 = RELU ? relu1(cu.h.x) : cu.h.x, o1 = RELU ? relu1(cu.h.y) : cu.h.y;
       *reinterpret_cast<float*>(hcb + soff[0]) = o0;
       *reinterpret_cast<float*>(hcb + soff[1]) = o1;
       soff[0] += sstep;

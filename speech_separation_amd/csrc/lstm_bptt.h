@@ -4,6 +4,26 @@
 #include "lstm.h"
 #include "lstm16.h"
 
+// d tanh-free pieces of the cell backward for TWO accumulator slots (packed fp32), shared by both tile sizes
+struct Bptt2 {
+  f32x2 dpi, dpf, dpg, dpo, dc_next;
+};
+DEV Bptt2 bptt_cell2(f32x2 dh, f32x2 dc_in, f32x2 i, f32x2 f, f32x2 g, f32x2 o, f32x2 c, f32x2 cprev) {
+  // tanh(c) = 2 / (1 + 2^(-2 log2e c)) - 1
+  const f32x2 e = exp2_2(c * -2.8853900817779268f);
+  const f32x2 tc = 2.0f * rcp_2(1.0f + e) - 1.0f;
+  const f32x2 dho = dh * o;
+  const f32x2 dc = dc_in + dho * (1.0f - tc * tc);
+  Bptt2 r;
+  r.dpo = dh * tc * (o - o * o);
+  const f32x2 dci = dc * i;
+  r.dpi = dc * g * (i - i * i);
+  r.dpf = dc * cprev * (f - f * f);
+  r.dpg = dci - dci * g * g;
+  r.dc_next = dc * f;
+  return r;
+}
+
 constexpr int BPTT_LDP = 512 + 4;
 constexpr size_t BPTT_LDS_BYTES = sizeof(float) * 2 * 32 * BPTT_LDP;
 

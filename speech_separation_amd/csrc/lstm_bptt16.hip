@@ -18,28 +18,6 @@
 
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-DEV f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// the cell backward for TWO slots (packed fp32) -- identical to lstm_bptt.hip
-struct Bptt2 {
-  f32x2 dpi, dpf, dpg, dpo, dc_next;
-};
-DEV Bptt2 bptt_cell2(f32x2 dh, f32x2 dc_in, f32x2 i, f32x2 f, f32x2 g, f32x2 o, f32x2 c, f32x2 cprev) {
-  const f32x2 e = exp2_2(c * -2.8853900817779268f);
-  const f32x2 tc = 2.0f * rcp_2(1.0f + e) - 1.0f;
-  const f32x2 dho = dh * o;
-  const f32x2 dc = dc_in + dho * (1.0f - tc * tc);
-  Bptt2 r;
-  r.dpo = dh * tc * (o - o * o);
-  const f32x2 dci = dc * i;
-  r.dpi = dc * g * (i - i * i);
-  r.dpf = dc * cprev * (f - f * f);
-  r.dpg = dci - dci * g * g;
-  r.dc_next = dc * f;
-  return r;
-}
-
 __global__ __launch_bounds__(256) void lstm_bptt16_kernel(const float* __restrict__ tape_gates,
                                                            const float* __restrict__ tape_c,
                                                            const float* __restrict__ whh_f,

@@ -8,7 +8,11 @@ code (hipcc cross-compiles gfx950 without a GPU):
     register (v_readlane of a spilled SGPR, v_readfirstlane): the statement cannot know what the allocator put in front of it, so
     every such statement starts with s_nop 4 (round 5, dgrad_r.hip: a request with a stale base = memory access fault);
   * dgrad_t.hip loads its weights into AGPRs by loads the compiler does not count: a register copy (v_accvgpr_*) or a spill
-    (scratch_*) anywhere in the kernel could read them before they have arrived.
+    (scratch_*) anywhere in the kernel could read them before they have arrived;
+  * the tile-ticket atomic of dgrad_t / dgrad_r / gemm_t (vmem_asm.h, TicketLoop) returns into a VGPR the compiler does not know
+    to be pending: on every path from the atomic to the kernel's end no other instruction may write that register before a
+    s_waitcnt vmcnt(n) that covers the atomic (n <= the vector-memory operations issued behind it on that path) -- a late return
+    would overwrite lane 0 of whatever value the allocator had put there.
     python3 tools/asm_hazards.py        exit code 1 and a list when something is found"""
 import os
 import re
@@ -20,6 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "speech_separation_amd", "csrc")
 FILES = ["dgrad_t.hip", "dgrad_r.hip", "gemm_t.hip", "attn_block2.hip", "lstm16x.hip", "fcln.hip"]
 NO_VGPR_FORM = {"dgrad_r.hip"}
+TICKET_LOOP = {"dgrad_t.hip", "dgrad_r.hip", "gemm_t.hip"}
+VMEM = re.compile(r"(global|buffer|scratch|flat)_(load|store|atomic)")
 
 
 def asm_of(src):
@@ -31,6 +37,110 @@ def asm_of(src):
         if r.returncode != 0:
             raise SystemExit(f"{src}: hipcc failed\n{r.stderr[-2000:]}")
         return [ln.strip() for ln in open(out) if ln.strip() and not ln.strip().startswith(";") or ln.strip().startswith(";;#")]
+
+
+def vgprs_written(ln):
+    """numbers of the VGPRs an instruction writes (its leading register operands, where the mnemonic has a vector destination)"""
+    m = re.match(r"(\S+)\s+(.*)", ln)
+    if not m or ln.startswith((";", ".")):
+        return set()
+    op, ops = m.group(1), [o.strip() for o in m.group(2).split(",")]
+    if op.startswith("s_") or "_store" in op or op.startswith("global_load_lds") or ("_atomic" in op and " sc0" not in ln and " glc" not in ln):
+        return set()
+    if op.startswith("ds_") and not any(k in op for k in ("read", "rtn", "permute", "swizzle")):
+        return set()
+    out = set()
+    for o in ops[:2 if "swap" in op else 1]:
+        r = re.match(r"^v(\d+)$", o) or re.match(r"^v\[(\d+):(\d+)\]$", o)
+        if r:
+            out.update(range(int(r.group(1)), int(r.groups()[-1]) + 1))
+    return out
+
+
+def sregs(operand):
+    r = re.match(r"^s(\d+)$", operand) or re.match(r"^s\[(\d+):(\d+)\]$", operand)
+    return set(range(int(r.group(1)), int(r.groups()[-1]) + 1)) if r else set()
+
+
+def ticket_register_hazards(src, lines):
+    """Every hand-issued returning global_atomic_add: walk all paths from it (see the module's docstring).  The four-way dispatch
+    of the tile loop is compiled into flags -- s_mov_b64 s[a:b], 0 / -1, tested by s_and_b64 / s_andn2_b64 vcc, exec, s[a:b] and
+    s_cbranch_vccz / vccnz -- so the walk carries what a path knows about such pairs (constants, and the outcome of an earlier test
+    of the same pair) and does not follow a branch that contradicts it; everything else it does not understand it follows both ways."""
+    bad, n = set(), 0
+    label_at = {m.group(1): i for i, ln in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", ln)] if m}
+    in_asm = False
+    for start, ln in enumerate(lines):
+        in_asm = ln.startswith(";;#ASMSTART") or (in_asm and not ln.startswith(";;#ASMEND"))
+        m = re.match(r"global_atomic_add v(\d+),.* sc0", ln)
+        if not (in_asm and m):
+            continue
+        n += 1
+        dst = int(m.group(1))
+        seen, work = set(), [(start + 1, 0, frozenset(), None)]      # line, operations behind the atomic, {(pair, truth)}, vcc
+        while work:
+            i, younger, known, vcc = work.pop()      # vcc: True / False (nonzero or not), or (pair, negated) of an unknown pair
+            known = dict(known)
+            while i < len(lines):
+                state = (i, younger, frozenset(known.items()), vcc)
+                if state in seen:
+                    break
+                seen.add(state)
+                cur = lines[i]
+                op, _, rest = cur.partition(" ")
+                ops = [o.strip() for o in rest.split(",")]
+                w = re.match(r"s_waitcnt .*vmcnt\((\d+)\)", cur)
+                if (w and int(w.group(1)) <= younger) or op in ("s_endpgm", "s_setpc_b64", "s_swappc_b64"):
+                    break      # covered, or the kernel's end
+                if dst in vgprs_written(cur):
+                    bad.add(f"{src}: v{dst}, the destination of the ticket atomic in line {start}, is written before a wait covers it: {cur}")
+                    break
+                if VMEM.match(cur):
+                    younger = min(younger + 1, 64)
+                b = re.match(r"s_(c?)branch(_\w+)?\s+(\.LBB\d+_\d+)", cur)
+                if b and not b.group(1):
+                    i = label_at[b.group(3)]
+                    continue
+                if b:
+                    take = [True, False]
+                    if b.group(2) in ("_vccz", "_vccnz") and vcc is not None:
+                        if isinstance(vcc, bool):
+                            take = [vcc == (b.group(2) == "_vccnz")]
+                        else:      # both ways, each with what it says about the pair
+                            pair, neg = vcc
+                            for t in take:
+                                nonzero = t == (b.group(2) == "_vccnz")
+                                k2 = dict(known)
+                                k2[pair] = nonzero != neg
+                                if t:
+                                    work.append((label_at[b.group(3)], younger, frozenset(k2.items()), nonzero))
+                                else:
+                                    known, vcc = k2, nonzero
+                            i += 1
+                            continue
+                    if True in take:
+                        work.append((label_at[b.group(3)], younger, frozenset(known.items()), vcc))
+                    if False not in take:
+                        break
+                    i += 1
+                    continue
+                # what the instruction does to the flags
+                if op in ("s_and_b64", "s_andn2_b64") and ops[0] == "vcc" and ops[1] == "exec":
+                    v = known.get(ops[2])
+                    neg = op == "s_andn2_b64"
+                    vcc = (v != neg) if v is not None else ((ops[2], neg) if sregs(ops[2]) else None)
+                elif ops and (ops[0] == "vcc" or ops[0].startswith("vcc_")):
+                    vcc = None
+                elif ops and sregs(ops[0]) and not op.startswith(("s_cmp", "s_bitcmp", "s_waitcnt", "s_nop")):
+                    hit = sregs(ops[0])
+                    const = known.get(ops[1]) if op == "s_mov_b64" and len(ops) > 1 and sregs(ops[1]) else {"0": False, "-1": True}.get(ops[1]) if op == "s_mov_b64" else None
+                    known = {k: v for k, v in known.items() if not (sregs(k) & hit)}
+                    if not isinstance(vcc, bool) and vcc is not None and sregs(vcc[0]) & hit:
+                        vcc = None      # the pair changes between the test and the branch: nothing to learn from it
+                    if const is not None:
+                        known[ops[0]] = const
+                i += 1
+    return n, sorted(bad)
 
 
 def main():
@@ -73,7 +183,12 @@ def main():
             for pat in ("v_accvgpr_", "scratch_"):
                 if pat in body:
                     bad.append(f"{src}: {body.count(pat)} x {pat} (weights loaded by uncounted loads must not be copied or spilled)")
-        print(f"{src}: {n_dma} hand-issued LDS-DMA requests, {n_store} hand-issued wide stores, {n_sbase} scalar-base operands checked")
+        n_ticket = 0
+        if src in TICKET_LOOP:
+            n_ticket, found = ticket_register_hazards(src, lines)
+            bad += found
+        print(f"{src}: {n_dma} hand-issued LDS-DMA requests, {n_store} hand-issued wide stores, {n_sbase} scalar-base operands checked"
+              + (f", {n_ticket} ticket atomics followed to the kernel's end" if src in TICKET_LOOP else ""))
     for b in bad:
         print("HAZARD:", b)
     print(f"{len(bad)} hazards")
