@@ -308,6 +308,13 @@ int dptnav_dropout_mask(dptnav_handle h, int block, int path, int B, int S, floa
  *   "attn_v2" (0/1, default 1): the fused attention block of the inference forward (num_features = 128) in the form with both
  *                 LayerNorms in fragment space and the FFN prologue's rows by LDS-DMA (attn_block2.hip); 0 = round 2-4's kernel
  *                 (attn_block.hip, kept for same-process A/B).  Same results up to the grouping of the LayerNorm sums (> 100 dB).
+ *   "attn_persist" (n >= 0, default 1): the launches of that block that carry the FFN prologue (every path but the first) as
+ *                 PERSISTENT workgroups: a workgroup takes sequences by ticket until none is left, sets up its constants once
+ *                 and requests the next sequence's first block of h rows while it works on the current one.  0 = one workgroup
+ *                 per sequence; 1 = min(sequences, CUs) workgroups for the launches with more sequences than CUs (the others keep
+ *                 one workgroup per sequence: nothing to loop over, measured 1 % slower at bs = 1); n >= 2 = min(sequences, n)
+ *                 workgroups whatever the size (tests, experiments).  Same results bit for bit: the arithmetic of a sequence does
+ *                 not depend on who runs it.  At B = 16: 28.06 -> 27.75 ms per forward (profiles/attn_persistent_ab.txt).
  *   "dgrad_t" (0/1, default 1): training backward, num_features = 128 -- the K = 512 data gradient of the LSTM's input product
  *                 (d y1 = dz + dG W_ih, dptn.py:48) and the K = 384 one of the attention in-projection (dptn.py:46) by dgrad_t.hip
  *                 (transposed product, rows by LDS-DMA) instead of the GEMM engine; 0 = the engine (kept for same-process A/B).

@@ -37,6 +37,9 @@ int attn_block_launch(void* stream, const float* x, const float* w_in, const flo
 
 // attn_block2.hip (round 5): the same block with both LayerNorms in fragment space and the prologue's h rows by LDS-DMA; fp32,
 // packed weights only.  Same arguments, same results up to the grouping of the LayerNorm sums.
+// queue != null, persist_grid > 0 and a prologue: the persistent form -- min(g.nseq, persist_grid) workgroups take sequences by
+// ticket from *queue (a device counter that is zero when the kernel starts); same results bit for bit.
 size_t attn_block2_lds_bytes(int nkb, bool pro);
 int attn_block2_launch(void* stream, const float* x, const float* b_in, const float* b_o, const float* gamma, const float* beta,
-                       float* y1, const SeqGeom& g, const AttnFfnPrologue* pro, const float* wpack);
+                       float* y1, const SeqGeom& g, const AttnFfnPrologue* pro, const float* wpack, unsigned* queue = nullptr,
+                       int persist_grid = 0);

@@ -21,7 +21,8 @@
 //   * the h rows of the prologue arrive by LDS-DMA (global_load_lds_dwordx4: 1 KiB = one row per wave instruction, two blocks in
 //     flight, no registers, no ds_write), the residual rows as fragment loads in inline assembly, all of it counted by hand
 //     (s_waitcnt vmcnt(12)): the compiler does not know those requests exist and therefore does not wait for them anywhere else.
-// LDS: token rows 84.5 KB + two h blocks 66.6 KB (the O^T exchange reuses the first) + statistics 1 KB + constants 3 KB.
+// LDS: token rows 84.5 KB + two h blocks 66.6 KB (the O^T exchange reuses the first) + statistics 1 KB + constants 3 KB + 16 B of
+// sequence tickets (the persistent form below).
 // Rounding differs from attn_block.hip in the LayerNorm statistics only (grouping of the sums); both are exact fp32 FMA chains.
 #include <hip/hip_runtime.h>
 
@@ -84,41 +85,66 @@ DEV unsigned long long ab_now() {
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
   return t;
 }
-#define AB_DECL unsigned long long ab_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ab_last = ab_now();
+#define AB_DECL unsigned long long ab_t[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ab_seqs = 0; unsigned long long ab_last = ab_now();
+#define AB_SEQ ++ab_seqs;
 #define AB_MARK(i) { const unsigned long long ab_n = ab_now(); ab_t[i] += ab_n - ab_last; ab_last = ab_n; }
 #define AB_KEEP(x) asm volatile("" :: "v"(x));
 #define AB_END                                                                                      \
   if ((threadIdx.x & 63) == 0) {                                                                    \
-    for (int ab_i = 0; ab_i < 12; ++ab_i) atomicAdd(&g_ab2_stamps[ab_i], ab_t[ab_i]);               \
-    atomicAdd(&g_ab2_stamps[12], 1ull);                                                             \
+    for (int ab_i = 0; ab_i < 13; ++ab_i) atomicAdd(&g_ab2_stamps[ab_i], ab_t[ab_i]);               \
+    atomicAdd(&g_ab2_stamps[15], ab_seqs);      /* wave-sequences (a persistent workgroup: several) */ \
   }
 #else
 #define AB_DECL
+#define AB_SEQ
 #define AB_MARK(i)
 #define AB_KEEP(x)
 #define AB_END
 #endif
 
-template <int NKB, bool PRO>
-__global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restrict__ x, const float* __restrict__ wp_in,
-                                                          const float* __restrict__ b_in, const float* __restrict__ wp_o,
+// (the one-sequence form has no tickets: the same statements on a type without state)
+struct NoTickets {
+  struct StaticFirst {};
+  DEV NoTickets(int*, unsigned*, int, StaticFirst) {}
+  DEV int next_tile(int, int) {
+    __syncthreads();
+    return 0;
+  }
+  template <int KEEP>
+  DEV void wait() {}
+  template <int KEEP>
+  DEV void retire() const {}
+};
+
+// PERSIST (PRO only; option attn_persist): a workgroup takes sequences until none is left -- TicketLoop of vmem_asm.h, one
+// counter per launch, the first sequence its own number; the hand-over (publish, barrier, read, request) rides on the barrier
+// between the prologue and phase 1, so the id of the NEXT sequence is known from phase 1 on -- and requests the next sequence's
+// first h block while the current one is in phase 1.  No barrier of its own between two sequences: in front of block 0's barrier
+// a sequence writes no LDS (its D(0) went out a sequence ago, into a buffer nobody has read since the prologue), and behind that
+// barrier every wave is through with the previous sequence.  What the sequence loop carries: the ticket register, `seq`, the
+// parity of the ticket slot and `fetched0`; everything else is set up again per sequence or once per workgroup (the constants in
+// LDS).  Measured: profiles/attn_persistent_ab.txt.
+// The arithmetic of a sequence is the one-sequence form's, statement by statement: the results are bit-identical.
+template <int NKB, bool PRO, bool PERSIST>
+__global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restrict__ x_, const float* __restrict__ wp_in_,
+                                                          const float* __restrict__ b_in_, const float* __restrict__ wp_o_,
                                                           const float* __restrict__ b_o, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float* __restrict__ y1, SeqGeom g,
-                                                          float scale_log2e, FfnPro2 pro) {
+                                                          const float* __restrict__ beta, float* __restrict__ y1_, SeqGeom g,
+                                                          float scale_log2e, FfnPro2 pro_, unsigned* queue) {
+  static_assert(PRO || !PERSIST, "the persistent form exists with the FFN prologue only");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Xs = smem;                                   // [NKB*32][LDX]  the sequence's token rows (rows >= len repeat the last one)
   float* Hs = smem + NKB * 32 * LDX;                  // PRO: [2][32][LDHC] h blocks (DMA targets)
   float* Ob = Hs;                                     // phase 2: [4 heads][4][64 lanes][4]  O^T tiles of one query block
   float* Red = Hs + (PRO ? 2 * 32 * LDHC : OB_FLOATS);  // [2][32 tokens][4 waves][2]  (mean_w, M2_w)
   float* Cst = Red + 512;                             // b_o | gamma | beta | (PRO) b_f | g2 | b2, 128 floats each
+  int* Tks = reinterpret_cast<int*>(Cst + 6 * 128);   // PERSIST: [2] sequence tickets
   const int tid = threadIdx.x;
   const int h = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave = head (attention) = column tile (token-wise products)
   const int lane = tid & 63, c = lane & 31, hh = lane >> 5;
-  const int seq = blockIdx.x, len = g.len;
-  const int64_t tok0 = seq_token_base(g, seq);
+  const int len = g.len;
   const int tstride = seq_token_stride(g);
   const unsigned rs_y = (unsigned)tstride * 512u;        // bytes between consecutive positions in x / y1 [M][128]
-  char* const ybase = reinterpret_cast<char*>(y1) + tok0 * 512;
   auto row_off = [&](int row, unsigned rstride, bool clamp) -> unsigned {      // row = uniform part + lane part, < 2^24
     if (clamp) row = row < len ? row : len - 1;
     return (unsigned)__umul24((unsigned)row, rstride);
@@ -129,7 +155,7 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
   // per-column constants of the two LayerNorms -> LDS (read back as 16-byte fragments where they are used)
   if (tid < (PRO ? 192 : 96)) {
     const int which = tid >> 5, q4 = tid & 31;
-    const float* src = which == 0 ? b_o : which == 1 ? gamma : which == 2 ? beta : which == 3 ? pro.bf : which == 4 ? pro.g2 : pro.b2;
+    const float* src = which == 0 ? b_o : which == 1 ? gamma : which == 2 ? beta : which == 3 ? pro_.bf : which == 4 ? pro_.g2 : pro_.b2;
     *reinterpret_cast<float4*>(&Cst[which * 128 + 4 * q4]) = ldg4(src + 4 * q4);
   }
   auto cst16 = [&](int which, f32x16& d) {      // d[4 j + t] = constant[32 h + 8 j + 4 hh + t]
@@ -149,6 +175,22 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
     return ln_merge(a, b, mu_w, delta);
   };
 
+  using Tickets = std::conditional_t<PERSIST, TicketLoop, NoTickets>;
+  Tickets tk(Tks, queue, g.nseq, typename Tickets::StaticFirst{});
+  int seq = blockIdx.x;                        // (the grid is at most the number of sequences)
+  int tkbuf = 0;
+  bool fetched0 = false;                       // PERSIST: the previous sequence of this workgroup has requested this one's first h block
+  for (;;) {
+  AB_SEQ
+  // Base pointers, per sequence.  PERSIST: opaque at the top of every iteration -- as loop invariants, every 64-bit address derived
+  // from them is hoisted out of the sequence loop and kept across a body that has no register to spare (276 B of scratch per lane
+  // in <5, true>); behind this statement they are formed again where they are used, as in the one-sequence form.
+  const float *x = x_, *wp_in = wp_in_, *b_in = b_in_, *wp_o = wp_o_;
+  float* y1 = y1_;
+  FfnPro2 pro = pro_;
+  if constexpr (PERSIST) asm volatile("" : "+s"(x), "+s"(wp_in), "+s"(wp_o), "+s"(y1), "+s"(b_in), "+s"(pro.hc), "+s"(pro.wf));
+  const int64_t tok0 = seq_token_base(g, seq);
+  char* const ybase = reinterpret_cast<char*>(y1) + tok0 * 512;
   float wkf[64], wvf[64];
   auto fetch_wkv1 = [&](int m) {      // k-chunk m of this head's W_k / W_v fragments
     const float* wk = wp_in + ((1 * 4 + h) * 16 * 64 + lane) * 4;   // packed: [sel][head][m][lane][4]
@@ -167,16 +209,6 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
     // counted by the compiler, their wait (vmcnt(0) in its book) would also sit out the first two blocks requested behind them.
     f32x4 wf4[32];
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    {
-      const char* wb = reinterpret_cast<const char*>(pro.wf + h * 32 * 64 * 4);        // packed: [head][m][lane][4]
-      static_for<8>([&](auto MQ) {
-        constexpr int mq = decltype(MQ)::value;
-        ldg4_uncounted_a<0>(wf4[4 * mq + 0], wb + mq * 4096, lane16);
-        ldg4_uncounted_a<1024>(wf4[4 * mq + 1], wb + mq * 4096, lane16);
-        ldg4_uncounted_a<2048>(wf4[4 * mq + 2], wb + mq * 4096, lane16);
-        ldg4_uncounted_a<3072>(wf4[4 * mq + 3], wb + mq * 4096, lane16);
-      });
-    }
     const uint32_t hs_lds = lds_addr(Hs);
     const char* const hbase = reinterpret_cast<const char*>(pro.hc) + tok0 * 1024;      // wave-uniform: row pointers stay in SGPRs
     const uint32_t rs_h = (uint32_t)tstride * 1024u;                                     // bytes between consecutive positions in hc
@@ -186,12 +218,18 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
     // blocks: 33 792 bytes for 33 280), free until block NKB - 2 is normalised -- so D(b) goes out TWO blocks ahead, behind the
     // barrier that opens block b - 2 (its buffer's last reader, block b - 3, is through by then).  Measured with two buffers and
     // one barrier per block the request had one block (~9 k cycles) and the wait for it was 2 k cycles per block, as run.
+    // PERSIST: the two h buffers change places (SW), so that block 0 of EVERY sequence lives in the second one -- idle from the
+    // end of the prologue on (the O^T exchange of phase 2 reuses the first) and therefore free to take the next sequence's block 0
+    // while this one is in phase 1 / 2.
     constexpr bool TRI = NKB >= 4;
+    constexpr int SW = PERSIST ? 1 : 0;
     auto hbuf_lds = [&](int b) -> uint32_t {      // LDS byte address of the buffer of block b
-      if (TRI) return (b % 3) == 2 ? lds_addr(Xs) + (uint32_t)((NKB - 2) * 32 * LDX * 4) : hs_lds + (uint32_t)((b % 3) * 32 * LDHC * 4);
-      return hs_lds + (uint32_t)((b & 1) * 32 * LDHC * 4);
+      if (TRI) return (b % 3) == 2 ? lds_addr(Xs) + (uint32_t)((NKB - 2) * 32 * LDX * 4) : hs_lds + (uint32_t)(((b % 3) ^ SW) * 32 * LDHC * 4);
+      return hs_lds + (uint32_t)(((b & 1) ^ SW) * 32 * LDHC * 4);
     };
-    auto hbuf = [&](int b) -> const float* { return TRI ? ((b % 3) == 2 ? Xs + (NKB - 2) * 32 * LDX : Hs + (b % 3) * 32 * LDHC) : Hs + (b & 1) * 32 * LDHC; };
+    auto hbuf = [&](int b) -> const float* {
+      return TRI ? ((b % 3) == 2 ? Xs + (NKB - 2) * 32 * LDX : Hs + ((b % 3) ^ SW) * 32 * LDHC) : Hs + ((b & 1) ^ SW) * 32 * LDHC;
+    };
     f32x4 res[2][4];
     // one request of block rb: k = 0..7 DMA row 8 h + k, k = 8..11 residual fragment k - 8 (k is a constant after unrolling)
     auto issue_d1 = [&](auto RB, int i) {
@@ -220,12 +258,32 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
     };
     // issue order: W_f | D(0) R(0) | inside block 0: R(1) D(1) [D(2)] | inside block rb >= 1: R(rb + 1), then D(rb + AHEAD)
     // (AHEAD = 2 with three buffers, else 1; the first fetch of a sequence is 44 requests back to back -- D(1) is not one of them)
+    // PERSIST, per sequence: D(0) (a workgroup's first sequence only) | W_f | R(0) | the blocks as above | behind the last hand-counted
+    // wait of the sequence: [ticket atomic, one lane], then in phase 1 D(0) of the NEXT sequence (if there is one).  Everything a
+    // sequence leaves in flight -- that prefetch, its y1 stores -- is older than the next sequence's W_f and so covered by the
+    // wait for it; block 0's own wait (vmcnt(0)) is the one the prefetched rows are read behind.
     constexpr int AHEAD = TRI ? 2 : 1;
-    issue_d(std::integral_constant<int, 0>{});
+    // (a workgroup's first sequence: nobody has requested its D(0).  It goes out in FRONT of W_f so that the wait for W_f keeps one
+    // count for both cases; block 0 waits for all of it right behind that wait anyway)
+    if constexpr (PERSIST) {
+      if (!fetched0) issue_d(std::integral_constant<int, 0>{});
+    }
+    {
+      const char* wb = reinterpret_cast<const char*>(pro.wf + h * 32 * 64 * 4);        // packed: [head][m][lane][4]
+      static_for<8>([&](auto MQ) {
+        constexpr int mq = decltype(MQ)::value;
+        ldg4_uncounted_a<0>(wf4[4 * mq + 0], wb + mq * 4096, lane16);
+        ldg4_uncounted_a<1024>(wf4[4 * mq + 1], wb + mq * 4096, lane16);
+        ldg4_uncounted_a<2048>(wf4[4 * mq + 2], wb + mq * 4096, lane16);
+        ldg4_uncounted_a<3072>(wf4[4 * mq + 3], wb + mq * 4096, lane16);
+      });
+    }
+    if constexpr (!PERSIST) issue_d(std::integral_constant<int, 0>{});
     issue_r(std::integral_constant<int, 0>{}, res[0]);
-    constexpr int BEHIND_WF = 12;                      // requests behind the W_f loads
+    constexpr int BEHIND_WF = PERSIST ? 4 : 12;        // requests behind the W_f loads: R(0), and D(0) in the one-sequence form
     wait_vm_a16<BEHIND_WF>(wf4);                       // W_f is in; the first two blocks stay in flight
     wait_vm_a16<BEHIND_WF>(wf4 + 16);
+    tk.template wait<BEHIND_WF>();                     // ... and the ticket requested a sequence ago (or in the kernel's prologue), older than W_f
     AB_MARK(0)
     // One barrier per block: B(rb) publishes the block's h rows AND the LayerNorm statistics of block rb - 1, whose merge /
     // normalise / x -> LDS then runs beside the 128 MFMAs of block rb (it reads LDS and has two dependent chains; alone it waits
@@ -255,7 +313,7 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
       constexpr int KEEP = (AHEAD == 2 && rb >= 1 && rb + 1 < NKB) ? 8 : 0;
       wait_vm<KEEP>(res[rb & 1]);
       __syncthreads();
-      AB_MARK(1)
+      AB_MARK(PERSIST && rb == 0 ? 12 : 1)
       // The next requests -- R(rb + 1), then D(rb + AHEAD): the order the waits above count on -- go out ONE AT A TIME between the
       // MFMAs of the first three quarters of the block (behind every second k-chunk): issued back to back, twelve requests cost
       // 1.5-2.4 k cycles of a wave that has nothing else to issue (measured: profiles/r05_attn_block2_experiments.txt), beside
@@ -341,8 +399,11 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < NLD; ++i) *reinterpret_cast<float4*>(&Xs[(i * 8 + (tid >> 5)) * LDX + 4 * (tid & 31)]) = st[i];
   }
-  __syncthreads();
-  AB_MARK(5)
+  // PERSIST: the hand-over of TicketLoop on this barrier -- publish the ticket that has come back, barrier, read the id of the next
+  // sequence, request the ticket after it (uncounted; covered by the next sequence's wait for W_f, or retired below)
+  const int next = tk.next_tile(seq, tkbuf);
+  const bool has_next = PERSIST && next < g.nseq;
+  AB_MARK(PERSIST ? 11 : 5)
 
   // W_q fragments (A operand of the Q^T tiles, parked in AGPRs): requested here, they arrive behind phase 1
   float wqf[64];
@@ -364,8 +425,23 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
       const float4 t = ldg4(b_in + N + h * DH + 8 * j + 4 * hh);
       bk[4 * j + 0] = t.x; bk[4 * j + 1] = t.y; bk[4 * j + 2] = t.z; bk[4 * j + 3] = t.w;
     }
-#pragma unroll
-    for (int rb = 0; rb < NKB; ++rb) {
+    // PERSIST: D(0) of the NEXT sequence -- this wave's 8 rows of its first h block, by LDS-DMA into the second h buffer, whose
+    // last reader (a prologue block of this sequence) is two barriers back -- one request behind every second k-chunk of key
+    // block 0 (back to back they would cost a wave that has nothing else to issue 1.5-2.4 k cycles, see the prologue).  A
+    // workgroup's last sequence requests nothing.  Sequences own disjoint token rows and hc is only read in this launch, so a
+    // row fetched early can never be one that a store of the same launch changes.
+    const char* hnext = nullptr;
+    if constexpr (PERSIST) {
+      if (has_next) hnext = reinterpret_cast<const char*>(pro.hc) + seq_token_base(g, next) * 1024;
+    }
+    auto prefetch1 = [&](int k) {
+      int row = 8 * h + k;
+      if (NKB == 1) row = row < len ? row : len - 1;
+      dma_part<false>(hnext + (uint32_t)row * ((uint32_t)tstride * 1024u), (uint32_t)lane * 16u,
+                      lds_addr(Hs) + (uint32_t)((32 + 8 * h + k) * LDHC * 4));
+    };
+    auto kv_block = [&](auto RB, auto PF) {
+      constexpr int rb = decltype(RB)::value;
       const float* xr = &Xs[(rb * 32 + c) * LDX + 4 * hh];
       f32x16 ka = zero16(), va = zero16();
 #pragma unroll
@@ -381,6 +457,13 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
             ka = mfma32(wkf[4 * (m0 + m) + t], xa[t], ka);
             va = mfma32(xa[t], wvf[4 * (m0 + m) + t], va);
           }
+          if constexpr (decltype(PF)::value) {
+            if ((m0 + m) & 1) {
+              __builtin_amdgcn_sched_barrier(0);
+              prefetch1((m0 + m) >> 1);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
         }
       }
 #pragma unroll
@@ -392,7 +475,15 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
 #pragma unroll
       for (int r = 0; r < 16; ++r) asm volatile("" : "+a"(kt[rb][r]), "+a"(vv[rb][r]));
       __builtin_amdgcn_sched_barrier(0);
-    }
+    };
+    static_for<NKB>([&](auto RB) {
+      if constexpr (PERSIST && decltype(RB)::value == 0) {
+        if (has_next) kv_block(RB, std::true_type{});
+        else kv_block(RB, std::false_type{});
+      } else {
+        kv_block(RB, std::false_type{});
+      }
+    });
   }
 
   AB_MARK(6)
@@ -607,35 +698,48 @@ __global__ __launch_bounds__(256) void attn_block2_kernel(const float* __restric
     AB_KEEP(qa[15]) AB_KEEP(qb_[15])
     AB_MARK(10)
   }
+  if constexpr (!PERSIST) {
+    break;
+  } else {
+    if (!has_next) {
+      tk.template retire<0>();      // the ticket nobody will use is back (a sequence old: the wait costs nothing but the last stores)
+      break;
+    }
+    seq = next;
+    tkbuf ^= 1;
+    fetched0 = true;
+  }
+  }      // sequences of this workgroup
   AB_END
 }
 
 }  // namespace
 
 size_t attn_block2_lds_bytes(int nkb, bool pro) {
-  return sizeof(float) * ((size_t)nkb * 32 * LDX + (pro ? 2 * 32 * LDHC : OB_FLOATS) + 512 + 6 * 128);
+  return sizeof(float) * ((size_t)nkb * 32 * LDX + (pro ? 2 * 32 * LDHC : OB_FLOATS) + 512 + 6 * 128 + 4);
 }
 
 int attn_block2_launch(void* stream, const float* x, const float* b_in, const float* b_o, const float* gamma, const float* beta,
-                       float* y1, const SeqGeom& g, const AttnFfnPrologue* pro, const float* wpack) {
+                       float* y1, const SeqGeom& g, const AttnFfnPrologue* pro, const float* wpack, unsigned* queue, int persist_grid) {
   using Kern = void (*)(const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*,
-                        SeqGeom, float, FfnPro2);
+                        SeqGeom, float, FfnPro2, unsigned*);
   const int nkb = (g.len + 31) / 32;
   if (nkb < 1 || nkb > 5 || !wpack) return (int)hipErrorInvalidValue;
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)DH);
   const int dev = current_hip_device();
   Kern kern;
   const bool p = pro != nullptr;
+  const bool persist = p && queue != nullptr && persist_grid > 0;      // the form without the prologue keeps one workgroup per sequence
   switch (nkb) {
-    case 1: kern = p ? attn_block2_kernel<1, true> : attn_block2_kernel<1, false>; break;
-    case 2: kern = p ? attn_block2_kernel<2, true> : attn_block2_kernel<2, false>; break;
-    case 3: kern = p ? attn_block2_kernel<3, true> : attn_block2_kernel<3, false>; break;
-    case 4: kern = p ? attn_block2_kernel<4, true> : attn_block2_kernel<4, false>; break;
-    default: kern = p ? attn_block2_kernel<5, true> : attn_block2_kernel<5, false>; break;
+    case 1: kern = persist ? attn_block2_kernel<1, true, true> : p ? attn_block2_kernel<1, true, false> : attn_block2_kernel<1, false, false>; break;
+    case 2: kern = persist ? attn_block2_kernel<2, true, true> : p ? attn_block2_kernel<2, true, false> : attn_block2_kernel<2, false, false>; break;
+    case 3: kern = persist ? attn_block2_kernel<3, true, true> : p ? attn_block2_kernel<3, true, false> : attn_block2_kernel<3, false, false>; break;
+    case 4: kern = persist ? attn_block2_kernel<4, true, true> : p ? attn_block2_kernel<4, true, false> : attn_block2_kernel<4, false, false>; break;
+    default: kern = persist ? attn_block2_kernel<5, true, true> : p ? attn_block2_kernel<5, true, false> : attn_block2_kernel<5, false, false>; break;
   }
   const size_t lds = attn_block2_lds_bytes(nkb, p);
-  static PerDeviceOnce ready_all[2][6];
-  PerDeviceOnce* ready = ready_all[p ? 1 : 0];
+  static PerDeviceOnce ready_all[3][6];
+  PerDeviceOnce* ready = ready_all[persist ? 2 : p ? 1 : 0];
   if (!ready[nkb].done(dev)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
@@ -643,8 +747,9 @@ int attn_block2_launch(void* stream, const float* x, const float* b_in, const fl
   }
   FfnPro2 fp{};
   if (p) fp = FfnPro2{pro->hc, pro->wf, pro->bf, pro->g2, pro->b2};
-  hipLaunchKernelGGL(kern, dim3(g.nseq), dim3(256), lds, static_cast<hipStream_t>(stream), x, wpack, b_in, wpack + ATTN_PACK_IN,
-                     b_o, gamma, beta, y1, g, scale_log2e, fp);
+  const int grid = persist ? (g.nseq < persist_grid ? g.nseq : persist_grid) : g.nseq;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), x, wpack, b_in, wpack + ATTN_PACK_IN,
+                     b_o, gamma, beta, y1, g, scale_log2e, fp, persist ? queue : nullptr);
   return (int)hipGetLastError();
 }
 

@@ -108,6 +108,8 @@ struct dptnav_ctx {
   bool opt_dgrad_r = true;          // training: the K = 128 data gradients with weight-gradient riders by dgrad_r.hip instead of the GEMM engine
   bool opt_dgrad_t = true;          // training: the K = 512 data gradient (d P W_ih) by dgrad_t.hip instead of the GEMM engine
   bool opt_attn_v2 = true;          // ... in the form with both LayerNorms in fragment space and h rows by LDS-DMA (attn_block2.hip)
+  int opt_attn_persist = 1;         // ... its launches with the FFN prologue as persistent workgroups that take sequences by ticket and request the next
+                                    // sequence's first h block ahead: 0 one workgroup per sequence, 1 min(sequences, CUs) workgroups where sequences > CUs, n >= 2 at most n (tests)
   bool opt_fold_tail = true;        // inference: post-processing conv + skip + decoder taps as one folded contraction
   bool opt_wgrad_ride = true;       // training: out-projection / ffn weight gradients formed inside their data-gradient GEMMs
   bool opt_wgrad2 = true;           // training: LSTM W_ih / W_hh gradients in one pass over dP (wgrad2_kernel)
@@ -783,8 +785,15 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
       wpack = pk;
       if (chain & CHAIN_PRO) pro.wf = pk - ATTN_PACK_FLOATS + ATTN_PACK_IN + ATTN_PACK_OUT;   // previous path's ffn.1 segment
     }
+    unsigned* seq_queue = nullptr;      // persistent form: one sequence-ticket counter of the pass (zeroed with the GEMM engine's, begin_run)
+    // (1: only where a workgroup gets more than one sequence -- measured equal at best below that)
+    if (c->opt_attn_v2 && !c->opt_split_bf16 && (chain & CHAIN_PRO) && (c->opt_attn_persist > 1 || (c->opt_attn_persist == 1 && geom.nseq > c->num_cus))) {
+      if (run.slot + 1 > QUEUE_SLOTS) return c->fail(DPTNAV_ERR_INVALID, "attention block: ticket counters exhausted");
+      seq_queue = run.take_queue(1);
+    }
     const int rc = (c->opt_attn_v2 && !c->opt_split_bf16)
-                       ? attn_block2_launch(st, x_in, w.in_b, w.out_b, w.ln1_w, w.ln1_b, y1, geom, (chain & CHAIN_PRO) ? &pro : nullptr, wpack)
+                       ? attn_block2_launch(st, x_in, w.in_b, w.out_b, w.ln1_w, w.ln1_b, y1, geom, (chain & CHAIN_PRO) ? &pro : nullptr, wpack, seq_queue,
+                                            c->opt_attn_persist == 1 ? c->num_cus : c->opt_attn_persist)
                        : attn_block_launch(st, x_in, w.in_w, w.in_b, w.out_w, w.out_b, w.ln1_w, w.ln1_b, y1, geom, c->opt_split_bf16,
                                            (chain & CHAIN_PRO) ? &pro : nullptr, wpack);
     if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention block: %s", hipGetErrorString((hipError_t)rc));
@@ -2859,6 +2868,7 @@ int dptnav_set_option(dptnav_handle h, const char* key, int value) {
   }
   else if (k == "fuse_attn") h->opt_fuse_attn = value != 0;
   else if (k == "attn_v2") h->opt_attn_v2 = value != 0;
+  else if (k == "attn_persist" && value >= 0) h->opt_attn_persist = value;
   else if (k == "dgrad_t") h->opt_dgrad_t = value != 0;
   else if (k == "dgrad_r") h->opt_dgrad_r = value != 0;
   else if (k == "gemm_t") h->opt_gemm_t = value != 0;

@@ -116,10 +116,11 @@ struct TicketLoop {
   unsigned* queue;
   int ntiles;
   bool dyn;            // queue != nullptr, wave-uniform (a kernel argument)
+  int base;            // added to a ticket where it is published: 0, or the grid where the first tiles are not drawn (StaticFirst)
 
   // Prologue: thread 0 takes the first two tickets (counted: nothing hand-issued is in flight yet).  The caller may stage what it
   // likes behind it; first_tile() comes after the caller's barrier.
-  DEV TicketLoop(int* s_next_, unsigned* queue_, int ntiles_) : ticket_ahead(0), s_next(s_next_), queue(queue_), ntiles(ntiles_), dyn(queue_ != nullptr) {
+  DEV TicketLoop(int* s_next_, unsigned* queue_, int ntiles_) : ticket_ahead(0), s_next(s_next_), queue(queue_), ntiles(ntiles_), dyn(queue_ != nullptr), base(0) {
     if (dyn) {
       if (threadIdx.x == 0) {
         s_next[0] = (int)atomicAdd(queue, 1u);
@@ -129,13 +130,27 @@ struct TicketLoop {
       s_next[0] = (int)blockIdx.x;
     }
   }
+  // ... for a kernel whose tiles are long and whose grid is the chip (attn_block2.hip: a sequence is ~90 us): a workgroup's FIRST
+  // tile is its own number, the counter hands out tiles gridDim.x, gridDim.x + 1, ...  Drawn, the first tickets of a launch are
+  // two atomics per workgroup on one address in the same microsecond; they are served one after the other, and the last workgroup
+  // had its first tile ~30 us after the launch (measured: + 1.06 ms on a 4.0 ms forward of 33 launches with <= 150 workgroups each).
+  // The one request left in the prologue is uncounted like the loop's and covered like it: by the first wait of the first tile
+  // that names the ticket.
+  struct StaticFirst {};
+  DEV TicketLoop(int* s_next_, unsigned* queue_, int ntiles_, StaticFirst)
+      : ticket_ahead(0), s_next(s_next_), queue(queue_), ntiles(ntiles_), dyn(queue_ != nullptr), base(queue_ != nullptr ? (int)gridDim.x : 0) {
+    if (threadIdx.x == 0) {
+      s_next[0] = (int)blockIdx.x;
+      if (dyn) asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(ticket_ahead) : "v"(0u), "v"(1u), "s"(queue) : "memory");
+    }
+  }
   DEV int first_tile() const { return __builtin_amdgcn_readfirstlane(s_next[0]); }
 
   // One step of the protocol, at the top of tile `tile` (its rows in buffer `buf`): publish, barrier, read the next tile, ask for
   // the one after it.  A result >= ntiles: `tile` is this workgroup's last.
   DEV int next_tile(int tile, int buf) {
     const int tid = threadIdx.x;
-    if (dyn && tid == 0) s_next[buf ^ 1] = ticket_ahead;
+    if (dyn && tid == 0) s_next[buf ^ 1] = ticket_ahead + base;
     __syncthreads();      // every wave's rows of `tile` are in LDS; everyone is through with the other buffer
     const int next = dyn ? __builtin_amdgcn_readfirstlane(s_next[buf ^ 1]) : tile + (int)gridDim.x;
     if (dyn && tid == 0)

@@ -39,11 +39,18 @@ NAMES = {0: ["PRO: first fetch", "PRO: stage h rows + barrier", "PRO: 128 MFMAs 
          # attn_block2.hip: the marks sit at the same places of the new structure
          1: ["PRO: first fetch", "PRO: wait for the block's DMA + barrier", "PRO: 128 MFMAs per block", "PRO: + bias + residual, group statistics, exchange barrier",
              "PRO: merge, normalise, x -> LDS (+ next DMA issue)", "K/V weights (+ x staging) + barrier", "phase 1: K^T / V tiles", "phase-2 constants + first Q tile",
-             "softmax loop", "O^T exchange + out-projection + statistics + barrier", "normalise + store beside the next Q tile"]}
-ideal = [0, 0, 5 * 128 * 64, 0, 0, 0, 5 * 128 * 64, 64 * 64, 5 * 160 * 64, 5 * 64 * 64, 4 * 64 * 64]
-variants = [int(a) for a in sys.argv[1:]] or [1, 0]
-for v2 in variants:
+             "softmax loop", "O^T exchange + out-projection + statistics + barrier", "normalise + store beside the next Q tile",
+             # persistent form (option attn_persist): the barrier in front of phase 1 with the ticket hand-over on it (instead of slot 5;
+             # the requests for the next sequence's rows ride between the MFMAs of phase 1 and are charged there), and block 0's
+             # wait + barrier (instead of its share of slot 1)
+             "persistent: ticket + prefetch issue (hand-over barrier)", "persistent: wait for prefetched rows + barrier"]}
+ideal = [0, 0, 5 * 128 * 64, 0, 0, 0, 5 * 128 * 64, 64 * 64, 5 * 160 * 64, 5 * 64 * 64, 4 * 64 * 64, 0, 0]
+# arguments: 1 = attn_block2.hip as launched by default, 10 = the same with attn_persist = 0, 0 = attn_block.hip
+variants = [int(a) for a in sys.argv[1:]] or [1, 10, 0]
+for var in variants:
+    v2, persist = int(var != 0), int(var == 1)
     eng.set_option("attn_v2", v2)
+    eng.set_option("attn_persist", persist)
     fn = lib.dptnav_debug_attn2_stamps if v2 else lib.dptnav_debug_attn_stamps
     for overlap in (1, 0):
         eng.set_option("overlap", overlap)
@@ -55,9 +62,9 @@ for v2 in variants:
         eng.forward(*args)
         fn(buf, 0)
         v = list(buf)
-        n = max(v[12], 1)
-        print(f"attn_v2={v2} ({'attn_block2.hip' if v2 else 'attn_block.hip'}) overlap={overlap}: {n} wave-sequences; cycles per sequence and wave "
+        n = max(v[15] if v2 else v[12], 1)      # attn_block2.hip counts wave-SEQUENCES (a persistent workgroup runs several)
+        print(f"attn_v2={v2} attn_persist={persist} ({'attn_block2.hip' if v2 else 'attn_block.hip'}) overlap={overlap}: {n} wave-sequences; cycles per sequence and wave "
               f"(MFMA issue cycles of the phase in brackets)")
         for k, nm in enumerate(NAMES[v2]):
             print(f"  {nm:62s} {v[k] / n:9.0f}  [{ideal[k]}]")
-        print(f"  {'total':62s} {sum(v[:11]) / n:9.0f}  [{sum(ideal)}]")
+        print(f"  {'total':62s} {sum(v[:len(NAMES[v2])]) / n:9.0f}  [{sum(ideal)}]")
