@@ -4,7 +4,7 @@ from .spec import DPRNN_AUDIO, DPRNN_AV, DPTN_AUDIO, DPTN_AV, DPTN_MASK, DPTNCon
 __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "DPRNN_AV", "DPRNNEncDec", "DPRNNAVEncDec", "state_dict_spec", "synthetic_state_dict", "synthetic_inputs",
            "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
            "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss", "MAEWavLoss",
-           "MSEWavLoss"]
+           "MSEWavLoss", "STOIMetric", "SISDRMetric"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
@@ -20,7 +20,7 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
     if name in ("FusedAdamW", "clip_grad_norm_"):
         from . import optim
         return getattr(optim, name)
-    if name in ("SiSNRWavLoss", "MAEWavLoss", "MSEWavLoss"):
+    if name in ("SiSNRWavLoss", "MAEWavLoss", "MSEWavLoss", "STOIMetric", "SISDRMetric"):
         from . import metrics
         return getattr(metrics, name)
     raise AttributeError(name)

@@ -79,6 +79,7 @@ CTTRAIN_ABI_VERSION = 1
 DCTTRAIN_ABI_VERSION = 1
 DAVTRAIN_ABI_VERSION = 1
 WAVLOSS_ABI_VERSION = 1
+WAVMETRIC_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -158,6 +159,17 @@ WAVLOSS_SYMBOLS = {
     "wavloss_pit_loss": (_i, [_i, _i, _fp, _fp, _fp, _fp, _i, _i64, C.c_float, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
 }
 
+#: every symbol include/wavmetric.h declares (evaluation metrics: SI-SDR, stateless; STOI / ESTOI behind a handle)
+WAVMETRIC_SYMBOLS = {
+    "wavmetric_abi_version": (_i, []),
+    "wavmetric_strerror": (C.c_char_p, [_i]),
+    "wavmetric_sisdr_pairs": (_i, [_fp, _fp, _fp, _fp, _i, _i64, _fp, _vp]),
+    "wavmetric_stoi_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "wavmetric_stoi_destroy": (None, [_vp]),
+    "wavmetric_stoi_scratch_bytes": (_sz, [_vp, _i, _i64]),
+    "wavmetric_stoi_pairs": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i64, _fp, _vp, _vp, _sz, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -177,7 +189,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
-                              + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())):
+                              + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
+                              + list(WAVMETRIC_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -190,7 +203,8 @@ def load() -> C.CDLL:
                             (lib.cttrain_abi_version, CTTRAIN_ABI_VERSION, "cttrain"),
                             (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain"),
                             (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain"),
-                            (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss")):
+                            (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss"),
+                            (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

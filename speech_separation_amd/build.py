@@ -41,11 +41,14 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            "ctasnet.hip": _GEMM_ENGINE_FLAGS, "deepctasnet.hip": _GEMM_ENGINE_FLAGS, "ctasnet_train.hip": _GEMM_ENGINE_FLAGS,
            "deepctasnet_train.hip": _GEMM_ENGINE_FLAGS,
            # wavloss.hip: the waveform criteria (MAE / MSE / SI-SNR, batch or utterance PIT), plain VALU
-           "wavloss.hip": []}
+           "wavloss.hip": [],
+           # wavmetric.hip: SI-SDR and STOI / ESTOI evaluation metrics; the DFT of the STOI runs on fp32 MFMA, accumulators in
+           # architectural VGPRs (their squares are taken with plain VALU instructions)
+           "wavmetric.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h")]
 
 
 def source_digest() -> str:

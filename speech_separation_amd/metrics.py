@@ -1,10 +1,12 @@
-"""Waveform criteria (forward + backward) and SI-SNR(i) metrics computed on the GPU.
+"""Waveform criteria (forward + backward) and the SI-SNR(i), SI-SDR and STOI / ESTOI metrics computed on the GPU.
 
 Mirrors (does not import) the reference interfaces that consume the model's outputs:
   * ``SiSNRWavLoss()(**batch) -> {"loss": tensor}``          src/loss/ss_losses.py:117-130 (+ BaseSSLoss :21-26)
   * ``MAEWavLoss()`` / ``MSEWavLoss()``, same call            src/loss/ss_losses.py:65-93   (+ BaseSSLoss :21-26)
   * ``SISNRiMetric(name=..., device=...)(**batch) -> value``  src/metrics/si_snri.py:7-30
   * ``SISNRMetric(name=..., device=...)(**batch) -> value``   src/metrics/si_snr.py:6-12
+  * ``SISDRMetric(name=..., device=...)(**batch) -> value``   src/metrics/si_sdr.py
+  * ``STOIMetric(fs, extended, name=..., device=...)(**batch) -> value``   src/metrics/stoi.py
 All resolve the speaker permutation at BATCH level by default (compare the two batch means), exactly as the reference
 does (ss_losses.py:21-25, base_metric.py:57-60) -- this is not per-utterance PIT.  The three criteria take
 ``pit="utterance"`` for per-utterance PIT (include/wavloss.h: the reference's class on every item alone, averaged); the
@@ -203,3 +205,107 @@ class SISNRiMetric(SISNRMetric):
 
     def __call__(self, s1_pred, s2_pred, s1, s2, mix, **batch):
         return self.resolve(self.enqueue(s1_pred, s2_pred, s1, s2, mix).cpu())
+
+
+_STOI_HANDLES: Dict[tuple, int] = {}                 # (device, fs, extended) -> wavmetric_stoi handle (kept for the process)
+
+
+def _pair_device(ts):
+    dev = ts[0].device
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def sisdr_pairs(s1_pred, s2_pred, s1, s2) -> torch.Tensor:
+    """wavmetric_sisdr_pairs (include/wavmetric.h) on the inputs' device and the current stream -> [B, 4] device tensor, the
+    SI-SDR in dB of the pairs (p1,s1) (p1,s2) (p2,s1) (p2,s2); no synchronisation."""
+    from . import _lib
+    ts = _wav_inputs(s1_pred, s2_pred, s1, s2)
+    lib = _lib.load()
+    B, T = ts[0].shape
+    dev = _pair_device(ts)
+    with torch.cuda.device(dev):
+        out = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        rc = lib.wavmetric_sisdr_pairs(*[t.data_ptr() for t in ts], B, T, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise RuntimeError(f"wavmetric_sisdr_pairs(B={B}, T={T}): {lib.wavmetric_strerror(rc).decode()}")
+    return out
+
+
+def stoi_pairs(s1_pred, s2_pred, s1, s2, fs: int = 16000, extended: bool = False):
+    """wavmetric_stoi_pairs (include/wavmetric.h) on the inputs' device and the current stream
+    -> ([B, 4] STOI (ESTOI if `extended`) of the pairs (p1,s1) (p1,s2) (p2,s1) (p2,s2), [B, 2] int32 frames kept under
+    target s1 / s2); both on the device, no synchronisation; scratch and outputs come from torch's allocator."""
+    import ctypes
+    from . import _lib
+    ts = _wav_inputs(s1_pred, s2_pred, s1, s2)
+    lib = _lib.load()
+    B, T = ts[0].shape
+    dev = _pair_device(ts)
+    key = (dev, int(fs), bool(extended))
+    with torch.cuda.device(dev):
+        if key not in _STOI_HANDLES:
+            h = ctypes.c_void_p()
+            rc = lib.wavmetric_stoi_create(int(fs), int(bool(extended)), ctypes.byref(h))
+            if rc:
+                raise (ValueError if rc == 1 else RuntimeError)(f"wavmetric_stoi_create(fs={fs}): {lib.wavmetric_strerror(rc).decode()}")
+            _STOI_HANDLES[key] = h.value
+        h = _STOI_HANDLES[key]
+        out = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        kept = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.wavmetric_stoi_scratch_bytes(h, max(B, 1), max(T, 1))), dtype=torch.uint8, device=dev)
+        rc = lib.wavmetric_stoi_pairs(h, *[t.data_ptr() for t in ts], B, T, out.data_ptr(), kept.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise RuntimeError(f"wavmetric_stoi_pairs(fs={fs}, B={B}, T={T}): {lib.wavmetric_strerror(rc).decode()}")
+    return out, kept
+
+
+class _PairMetric:
+    """SS2BaseMetric.forward (src/metrics/base_metric.py) over four per-item pair values computed on the device: batch
+    means, then the batch-level permutation ``pick((m11 + m22) / 2, (m12 + m21) / 2)``.  ``metric(**batch)`` returns a
+    Python float as the reference does (one device->host copy); ``enqueue(**batch)`` launches and returns the four batch
+    means as a DEVICE tensor without synchronising, ``resolve(means.cpu())`` finishes on the host
+    (evaluate.run_inference reads all batches' means once, at the end)."""
+
+    def __init__(self, name=None, device="cuda", lower_better=False, *args, **kwargs):
+        self.name = name if name is not None else type(self).__name__
+        self.pick = min if lower_better else max
+
+    def pairs(self, s1_pred, s2_pred, s1, s2) -> torch.Tensor:
+        raise NotImplementedError
+
+    def enqueue(self, s1_pred, s2_pred, s1, s2, **batch) -> torch.Tensor:
+        return self.pairs(s1_pred, s2_pred, s1, s2).double().mean(0)
+
+    def resolve(self, means: torch.Tensor) -> float:
+        m = means
+        return self.pick(float((m[0] + m[3]) / 2), float((m[1] + m[2]) / 2))
+
+    def __call__(self, s1_pred, s2_pred, s1, s2, **batch):
+        return self.resolve(self.enqueue(s1_pred, s2_pred, s1, s2).cpu())
+
+
+class SISDRMetric(_PairMetric):
+    """The reference's SISDRMetric (src/metrics/si_sdr.py): torchmetrics' ScaleInvariantSignalDistortionRatio() defaults
+    (no mean removal), one launch."""
+
+    def pairs(self, s1_pred, s2_pred, s1, s2):
+        return sisdr_pairs(s1_pred, s2_pred, s1, s2)
+
+
+class STOIMetric(_PairMetric):
+    """The reference's STOIMetric (src/metrics/stoi.py): STOI, or ESTOI with ``extended=True``, of signals sampled at
+    ``fs`` = 8000, 10000 or 16000 Hz, in three or four launches instead of four pystoi calls per item on the host.  The
+    definition is the project's fp64 restatement of pystoi's algorithm.  ``self.last_kept`` keeps
+    the latest call's [B, 2] device tensor of frames kept under each target."""
+
+    def __init__(self, fs=16000, extended=False, name=None, device="cuda", lower_better=False, *args, **kwargs):
+        super().__init__(name, device, lower_better, *args, **kwargs)
+        if int(fs) not in (8000, 10000, 16000):
+            raise ValueError(f"fs must be 8000, 10000 or 16000, got {fs!r}")
+        self.fs, self.extended = int(fs), bool(extended)
+        self.last_kept = None
+
+    def pairs(self, s1_pred, s2_pred, s1, s2):
+        out, self.last_kept = stoi_pairs(s1_pred, s2_pred, s1, s2, self.fs, self.extended)
+        return out
