@@ -169,8 +169,12 @@ int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float
  *   parameter into the buffers bound with dptnav_bind_grads.  The loss itself (src/loss/ss_losses.py), gradient
  *   clipping and the optimizer stay the reference's own PyTorch code (speech_separation_amd/model.py wraps these two
  *   calls in a torch.autograd.Function).  Train-mode attention dropout: options dropout_ppm / dropout_seed below.
- *   Limit of the training step (not of inference): Tv <= 256 video frames per mixture (> 10 s of 25 fps lip embeddings);
- *   the size queries return 0 and dptnav_train_forward fails with DPTNAV_ERR_INVALID BEFORE launching anything. */
+ *   Limits of the training step (not of inference): Tv <= 256 video frames per mixture (> 10 s of 25 fps lip embeddings),
+ *   and with DPTN blocks (arch = 0) S = dptnav_chunks(T) <= 256 chunks per mixture (the inter-chunk attention's sequence
+ *   length: the tape and the attention backward hold one sequence of at most 256 positions; about 7.3 s of audio in the
+ *   default configuration; DPRNN blocks have no attention and no such limit).  The size queries return 0 and
+ *   dptnav_train_forward / dptnav_train_backward fail with DPTNAV_ERR_INVALID BEFORE launching anything; the path-level
+ *   entry points refuse path 1 with S > 256 in the same way (path 0 attends over the K <= 256 positions of a chunk). */
 size_t dptnav_train_tape_bytes(dptnav_handle h, int B, int64_t T, int Tv);
 size_t dptnav_train_workspace_bytes(dptnav_handle h, int B, int64_t T, int Tv);
 int dptnav_train_forward(dptnav_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,

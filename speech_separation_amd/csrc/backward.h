@@ -63,8 +63,22 @@ struct ALoadSeqShift {
 };
 static inline ALoadSeqShift make_seq_shift(const float* A, int64_t M, int lda, int col0, int bm, int shift, const SeqGeom& g) {
   ALoadSeqShift l{A, M, lda, col0, bm, shift, g, 0u, 0};
-  l.magK = g.K > 1 ? (unsigned)((1ull << 32) / (unsigned)g.K) + 1u : 0u;   // K == 1: x / 1 is not a multiply-high; rejected by the caller
-  l.sstride = shift * (g.mode == 0 ? 1 : g.K);
+  // K == 1 (chunks of one frame): x / 1 is not a multiply-high (2^32 + 1 does not fit magK), so the geometry is restated
+  // here, on the host, in a form the loaders divide correctly.  The inter-chunk view of K = 1 is token = b * S + s, which is
+  // the intra-chunk view with S in the place of K; the intra-chunk view of K = 1 has one position per sequence, so every
+  // shifted row lies outside it: len = 0 makes both loaders return zeros for every row (with magK = 0 the position that
+  // load4z computes is merely the row inside the tile, and no position passes p2 < 0).
+  if (g.K == 1) {
+    if (g.mode == 1 && g.S > 1) {
+      l.g.mode = 0;
+      l.g.K = g.S;
+    } else {
+      l.g.mode = 0;
+      l.g.len = 0;
+    }
+  }
+  l.magK = l.g.K > 1 ? (unsigned)((1ull << 32) / (unsigned)l.g.K) + 1u : 0u;
+  l.sstride = shift * (l.g.mode == 0 ? 1 : l.g.K);
   return l;
 }
 

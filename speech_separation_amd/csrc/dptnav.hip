@@ -2515,6 +2515,16 @@ int dptnav_bind_grads(dptnav_handle h, float* const* dev_ptrs, int n) {
   h->gptr.assign(dev_ptrs, dev_ptrs + n);
   return DPTNAV_OK;
 }
+// The training step's attention (softmax / bit-mask tape of attention_kernel, attention_bwd_kernel) holds one sequence of at
+// most 256 positions.  The intra-chunk sequence is a chunk (chunk_size <= 256, dptnav_create); the inter-chunk one is the S
+// chunks of a mixture.  Checked by the size queries and at the top of every training entry point, before anything is
+// launched: the streaming kernel that inference uses beyond 256 writes no tape.
+static int train_chunk_limit(dptnav_handle h, int64_t S) {
+  if (h->cfg.arch == 0 && S > 256)
+    return h->fail(DPTNAV_ERR_INVALID, "training step: at most 256 chunks per mixture with DPTN blocks (S=%lld: the inter-chunk "
+                   "attention's sequence length); inference has no such limit", (long long)S);
+  return DPTNAV_OK;
+}
 size_t dptnav_train_path_tape_bytes(dptnav_handle h, int B, int S) {
   if (!h) return 0;
   PathTape t;
@@ -2532,6 +2542,8 @@ int dptnav_train_path_forward(dptnav_handle h, int block, int path, const float*
   if (!h) return DPTNAV_ERR_INVALID;
   if (block < 0 || block >= h->cfg.num_blocks || (path != 0 && path != 1) || !x_in || !x_out || !tape)
     return h->fail(DPTNAV_ERR_INVALID, "train_path_forward: bad argument");
+  if (path == 1)
+    if (int rc = train_chunk_limit(h, S)) return rc;
   PathTape tp;
   make_path_tape(h, B, S, &tp);
   if (tape_bytes < tp.total * sizeof(float)) return h->fail(DPTNAV_ERR_WORKSPACE, "tape too small");
@@ -2555,6 +2567,8 @@ int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float
     return h->fail(DPTNAV_ERR_INVALID, "train_path_backward: bad argument");
   if (h->opt_train_fuse_probe)
     return h->fail(DPTNAV_ERR_INVALID, "train_path_backward: option train_fuse_probe is set (measurement only: the forward wrote no tape)");
+  if (path == 1)
+    if (int rc = train_chunk_limit(h, S)) return rc;
   PathTape tp;
   make_path_tape(h, B, S, &tp);
   BwdPlan bp;
@@ -2573,6 +2587,7 @@ static int train_shapes(dptnav_handle h, int B, int64_t T, int Tv, Plan* pl, Mod
   if ((h->cfg.num_features != 128 || h->cfg.arch != 0) && !h->opt_ln_tape)
     return h->fail(DPTNAV_ERR_INVALID, "training step of this configuration needs option ln_tape = 1");
   if (int rc = make_plan(h, B, T, Tv, pl)) return rc;
+  if (int rc = train_chunk_limit(h, pl->S)) return rc;
   make_model_tape(h, B, pl->L, (int)pl->S, Tv, mt);
   make_bwd_plan(h, B, (int)pl->S, bp, pl->L, Tv);
   return DPTNAV_OK;

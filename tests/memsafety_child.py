@@ -61,6 +61,13 @@ VARIANTS = {
     "split_bf16": (_cfg(DPTN_AV, num_blocks=2), {"split_bf16": 1}, 5, 8000, 13, 0),
     "ragged": (_cfg(DPTN_AV, num_blocks=1, chunk_size=50, step_size=25, kernel_size_enc=5), {}, 3, 3001, 5, 2),
     "full": (_cfg(DPTN_AV), {}, 16, 32000, 50, 16),
+    # train-mode attention dropout (the default training configuration; every variant above runs the training step with
+    # dropout off): the keep mask is a pure function of (seed, token, head, key), so every check holds unchanged
+    "dptn128_drop": (_cfg(DPTN_AV, num_blocks=2, dropout=0.1), {"dropout_ppm": 100000, "dropout_seed": 2024}, 5, 8000, 13, 3),
+    # ... and 256 positions per chunk, 4 chunks: eight 32-key blocks on the intra-chunk path, where the bit-mask tape of the
+    # last (sequence, head, query block) ends with its allocation
+    "dptn64_drop256": (_cfg(DPTN_AUDIO, num_blocks=1, chunk_size=256, step_size=128, dropout=0.1),
+                       {"dropout_ppm": 100000, "dropout_seed": 2024}, 3, 2000, 1, 2),
 }
 
 

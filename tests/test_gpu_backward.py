@@ -477,6 +477,79 @@ def test_training_rejects_long_video_before_launching_anything(dev):
     assert torch.isfinite(s1).all() and torch.isfinite(s2).all()
 
 
+def _chunk_limit_cfg(features):
+    """chunk_size 20, step 10 (the smallest tests/test_gpu_fuzz.py draws), one block: T = 7714 samples are 256 chunks, 7744 are 257."""
+    from speech_separation_amd.spec import DPTN_AUDIO
+    cfg = DPTNConfig(**{**(DPTN_AV if features == 128 else DPTN_AUDIO).to_dict(), "num_blocks": 1, "dropout": 0.0,
+                        "chunk_size": 20, "step_size": 10})
+    assert cfg.chunks(cfg.frames(7714)) == 256 and cfg.chunks(cfg.frames(7744)) == 257
+    return cfg
+
+
+@pytest.mark.parametrize("features", [128, 64])
+@pytest.mark.parametrize("dropout_ppm", [0, 100000])
+def test_training_rejects_more_than_256_chunks_before_launching_anything(dev, dropout_ppm, features):
+    """The training step's attention (tape and backward) holds sequences of at most 256 positions; the inter-chunk sequence is
+    the S chunks of a mixture.  S = 257 used to reach the streaming inference kernel (no tape) and fail in stage 9 of the
+    backward with dropout off, or in the middle of the forward's chain with dropout on; now the size queries,
+    dptnav_train_forward and the path-level entry points refuse it up front.  Inference takes the same clip."""
+    from speech_separation_amd.engine import DptnEngine, params_to_device
+    from speech_separation_amd.spec import synthetic_inputs
+    cfg = _chunk_limit_cfg(features)
+    eng = DptnEngine(cfg, dev)
+    eng.bind(params_to_device(synthetic_state_dict(cfg, seed=1), dev))
+    eng.bind_grads()
+    eng.set_option("dropout_ppm", dropout_ppm)
+    eng.set_option("dropout_seed", 7)
+    B, T = 2, 7744
+    assert eng.chunks(T) == 257
+    t = {k: torch.from_numpy(v).to(dev) for k, v in synthetic_inputs(cfg, B=B, T=T, Tv=9, seed=2).items()}
+    args = (t["mix"], t.get("s1_embedding"), t.get("s2_embedding"))
+    with pytest.raises(RuntimeError, match="at most 256 chunks"):
+        eng.train_forward(*args)
+    x = torch.randn(1, 257, cfg.chunk_size, cfg.num_features, device=dev)
+    with pytest.raises(RuntimeError, match="at most 256 chunks"):
+        eng.train_path_forward(0, 1, x)
+    s1, s2 = eng.forward(*args)
+    torch.cuda.synchronize()
+    assert torch.isfinite(s1).all() and torch.isfinite(s2).all()
+
+
+@pytest.mark.parametrize("features", [128, 64])
+def test_whole_model_backward_at_256_chunks_matches_autograd(dev, features):
+    """S = 256, the longest inter-chunk sequence the training step takes (eight full 32-key blocks), B = 2: d loss / d every
+    parameter against fp64 autograd on the stock composition, to the floor of test_whole_model_backward_matches_autograd.
+    (Input seeds: the smallest ReLU input of the fp64 run is 1.6e-7 / 1.5e-7 -- with 5 million of them none stays above
+    4e-7, and below ~1e-7 the sign of one is not defined in fp32; see test_path_backward_matches_autograd.)"""
+    from speech_separation_amd.engine import DptnEngine, params_to_device
+    from speech_separation_amd.spec import synthetic_inputs
+    from tests.test_gpu_fuzz import stock_gradients
+    cfg = _chunk_limit_cfg(features)
+    sd = synthetic_state_dict(cfg, seed=2)
+    eng = DptnEngine(cfg, dev)
+    eng.bind(params_to_device(sd, dev))
+    grads = eng.bind_grads()
+    B, T = 2, 7714
+    assert eng.chunks(T) == 256
+    inp = synthetic_inputs(cfg, B=B, T=T, Tv=9, seed=8 if features == 128 else 30)
+    t = {k: torch.from_numpy(v).to(dev) for k, v in inp.items()}
+    rng = np.random.default_rng(3)
+    d1 = rng.standard_normal((B, T)).astype(np.float32)
+    d2 = rng.standard_normal((B, T)).astype(np.float32)
+    args = (t["mix"], t.get("s1_embedding"), t.get("s2_embedding"))
+    s1, s2, tape = eng.train_forward(*args)
+    eng.train_backward(*args, torch.from_numpy(d1).to(dev), torch.from_numpy(d2).to(dev), tape)
+    torch.cuda.synchronize()
+    want = stock_gradients(cfg, sd, inp, d1, d2)
+    kink = want.pop("__smallest_relu_input__")
+    assert kink > 1e-7, kink
+    missing = [k for k in grads if k not in want]
+    assert not missing, missing
+    worst = min((O.agreement_db(grads[k].cpu().numpy(), want[k].numpy().reshape(grads[k].shape)), k) for k in grads)
+    print(f"{features} features, S = 256: worst parameter {worst[1]} {worst[0]:.1f} dB (smallest ReLU input {kink:.1e})")
+    assert worst[0] > 60, worst
+
+
 @pytest.mark.parametrize("features", [64, 128])
 @pytest.mark.parametrize("path", [0, 1])
 def test_dprnn_path_backward_matches_autograd(dev, path, features):
