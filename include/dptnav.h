@@ -174,7 +174,10 @@ int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float
  *   length: the tape and the attention backward hold one sequence of at most 256 positions; about 7.3 s of audio in the
  *   default configuration; DPRNN blocks have no attention and no such limit).  The size queries return 0 and
  *   dptnav_train_forward / dptnav_train_backward fail with DPTNAV_ERR_INVALID BEFORE launching anything; the path-level
- *   entry points refuse path 1 with S > 256 in the same way (path 0 attends over the K <= 256 positions of a chunk). */
+ *   entry points refuse path 1 with S > 256 in the same way (path 0 attends over the K <= 256 positions of a chunk).
+ *   Option "train_long_seq" = 1 (below) lifts the limit on S: beyond 256 chunks the inter-chunk attention of the training
+ *   step runs a streaming forward with tape and a tiled backward (csrc/attn_long_train.h), for any S the 32-bit token
+ *   indexing allows.  The limits on Tv and on chunk_size stay. */
 size_t dptnav_train_tape_bytes(dptnav_handle h, int B, int64_t T, int Tv);
 size_t dptnav_train_workspace_bytes(dptnav_handle h, int B, int64_t T, int Tv);
 int dptnav_train_forward(dptnav_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,
@@ -329,6 +332,14 @@ int dptnav_dropout_mask(dptnav_handle h, int block, int path, int B, int S, floa
  *   "gemm_t" (0/1, default 1): training forward, num_features = 128 -- the attention in-projection qkv = x W_in^T + b_in
  *                 (dptn.py:16-21, 46) by gemm_t.hip (transposed product, accumulators started from the bias); 0 = the GEMM engine.
  *                 Same sums in another association: outputs and gradients agree to fp32 rounding.
+ *   "train_long_seq" (0/1/2, default 0): training step with DPTN blocks on more than 256 chunks per mixture.  0: refused
+ *                 (see "Limits of the training step").  1: the size queries, dptnav_train_forward / _backward and the path-level
+ *                 entry points take S > 256; attention sequences longer than 256 positions -- tape or dropout -- go to the
+ *                 streaming forward and the tiled two-launch backward of csrc/attn_long_train.h (keep decisions re-hashed, no
+ *                 bit-mask tape for them); sequences of at most 256 positions keep the on-chip kernels, so results up to 256
+ *                 chunks do not change.  2: TEST / MEASUREMENT ONLY -- the streaming trio at every length on both paths
+ *                 (tests/test_gpu_train_long.py, tools/train_long_ab.py compare it with the on-chip trio on identical inputs).
+ *                 Set it before the size queries: the tape has no bit-mask words for an inter-chunk sequence beyond 256.
  *   "train_fuse_probe" (0/1, default 0): MEASUREMENT ONLY (tools/train_fuse_probe.py) -- the training forward runs the inference
  *                 attention block: no qkv / attention / LayerNorm tape is written and no dropout is applied.  While it is set
  *                 dptnav_train_backward and dptnav_train_path_backward return DPTNAV_ERR_INVALID. */

@@ -11,6 +11,7 @@
 
 #include "../../include/dptnav.h"
 #include "attention.h"
+#include "attn_long_train.h"
 #include "attn_block.h"
 #include "attn_block64.h"
 #include "common.h"
@@ -118,6 +119,7 @@ struct dptnav_ctx {
   int opt_lstm_diag = 0;
   int opt_inject_fail = 0;          // > 0: the n-th GEMM-engine / fcln launch from now on returns an error (tests)
   bool opt_debug_sync = false;      // debugging aid: name every launch class on stderr and synchronise behind it
+  int opt_train_long_seq = 0;   // training attention beyond 256 positions (attn_long_train.h).  0: refused (train_chunk_limit); 1: the streaming trio for len > 256; 2: TEST / MEASUREMENT ONLY, the streaming trio at every length
   bool opt_train_fuse_probe = false;   // MEASUREMENT ONLY (no tape is written: dptnav_train_backward / _path_backward refuse while it is set) (tools/train_fuse_probe.py): the training forward runs the inference attention block
                                        // (no qkv / att / LayerNorm tape: a backward after it is garbage) -- the upper bound of a fused front half
   int opt_dropout_ppm = 0;          // train-mode attention dropout probability x 1e6 (0 = off)
@@ -454,6 +456,15 @@ int launch_attn_nkb(dptnav_ctx* c, const float* qkv, float* att, int N, const Se
 template <int DH>
 int launch_attn(dptnav_ctx* c, const float* qkv, float* att, int N, const SeqGeom& g, int heads, hipStream_t st,
                 DropCfg drop = DropCfg{0u, 0u, 1.0f}, float2* stats = nullptr, unsigned long long* mask = nullptr) {
+  // training forward (a tape to write, or dropout) under option train_long_seq: the streaming kernel with tape and dropout.
+  // It re-hashes the keep decisions, as its backward does: the bit-mask tape stays unwritten.
+  if ((stats != nullptr || drop.thresh != 0u) && (c->opt_train_long_seq == 2 || (c->opt_train_long_seq == 1 && g.len > 256))) {
+    ProfScope ps(c, CAT_ATTN, st);
+    hipLaunchKernelGGL(attention_long_train_kernel<DH>, dim3(g.nseq, heads), dim3(256), 0, st, qkv, att, N, heads, g,
+                       1.4426950408889634f / sqrtf((float)DH), drop, stats);
+    LAUNCH_CHECK(c, "attention (long, training)");
+    return DPTNAV_OK;
+  }
   switch ((g.len + 31) / 32) {
     case 1: return launch_attn_nkb<DH, 1>(c, qkv, att, N, g, heads, st, drop, stats, mask);
     case 2: return launch_attn_nkb<DH, 2>(c, qkv, att, N, g, heads, st, drop, stats, mask);
@@ -465,7 +476,7 @@ int launch_attn(dptnav_ctx* c, const float* qkv, float* att, int N, const SeqGeo
     case 8: return launch_attn_nkb<DH, 8>(c, qkv, att, N, g, heads, st, drop, stats, mask);
   }
   // longer sequences (inter-chunk path of utterances beyond ~7 s): streaming-softmax kernel, inference only
-  if (drop.thresh != 0u) return c->fail(DPTNAV_ERR_INVALID, "attention: dropout needs sequence length <= 256 (got %d)", g.len);
+  if (drop.thresh != 0u) return c->fail(DPTNAV_ERR_INVALID, "attention: dropout needs sequence length <= 256 (got %d) unless option train_long_seq is set", g.len);
   {
     ProfScope ps(c, CAT_ATTN, st);
     hipLaunchKernelGGL(attention_long_kernel<DH>, dim3(g.nseq, heads), dim3(256), 0, st, qkv, att, N, g,
@@ -1178,7 +1189,8 @@ int make_path_tape(dptnav_ctx* c, int B, int S, PathTape* t) {
   t->cst = take((size_t)2 * nst * 128 * 32);
   t->astats = take(dptn ? (size_t)M * g.num_heads * 2 : 0);
   {   // 2 floats per word; the larger of the two paths' (sequences x blocks^2)
-    const int64_t nk = (K + 31) / 32, ns = (S + 31) / 32;
+    // (an inter-chunk sequence beyond 256 positions -- option train_long_seq -- re-hashes its decisions: no words for it)
+    const int64_t nk = (K + 31) / 32, ns = (S > 256 && c->opt_train_long_seq != 0) ? 0 : (S + 31) / 32;
     const int64_t words = std::max((int64_t)B * S * nk * nk, (int64_t)B * K * ns * ns) * g.num_heads * 16;
     t->amask = take(dptn ? (size_t)words * 2 : 0);
   }
@@ -1819,6 +1831,14 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
       return DPTNAV_OK;
     };
     int rc = DPTNAV_OK;
+    if (c->opt_train_long_seq == 2 || (c->opt_train_long_seq == 1 && nkb > 8)) {   // tiles of fixed size, any length (attn_long_train.h)
+      ProfScope ps(c, CAT_ATTN, st);
+      const DropCfg drop = c->drop_cfg(block, path, true, br.half);
+      const dim3 grid(geom.nseq, g.num_heads, (nkb + 3) / 4);
+      hipLaunchKernelGGL(attention_long_bwd_a_kernel<DH>, grid, dim3(256), 0, st, qkv, att, DATT, DQKV, stats, g.num_heads, N, geom, scale,
+                         drop, reinterpret_cast<const float2*>(tape + tp.astats));
+      hipLaunchKernelGGL(attention_long_bwd_b_kernel<DH>, grid, dim3(256), 0, st, qkv, DATT, DQKV, stats, g.num_heads, N, geom, scale, drop);
+    } else
     switch (nkb) {
       case 1: rc = launch(attention_bwd_kernel<DH, 1, 0>, attention_bwd_kernel<DH, 1, 1>, 64); break;
       case 2: rc = launch(attention_bwd_kernel<DH, 2, 0>, attention_bwd_kernel<DH, 2, 1>, 128); break;
@@ -2518,11 +2538,12 @@ int dptnav_bind_grads(dptnav_handle h, float* const* dev_ptrs, int n) {
 // The training step's attention (softmax / bit-mask tape of attention_kernel, attention_bwd_kernel) holds one sequence of at
 // most 256 positions.  The intra-chunk sequence is a chunk (chunk_size <= 256, dptnav_create); the inter-chunk one is the S
 // chunks of a mixture.  Checked by the size queries and at the top of every training entry point, before anything is
-// launched: the streaming kernel that inference uses beyond 256 writes no tape.
+// launched: the streaming kernel that inference uses beyond 256 writes no tape.  Option train_long_seq = 1 lifts the limit on
+// the inter-chunk sequence: beyond 256 positions the forward and backward take the streaming trio of attn_long_train.h.
 static int train_chunk_limit(dptnav_handle h, int64_t S) {
-  if (h->cfg.arch == 0 && S > 256)
+  if (h->cfg.arch == 0 && S > 256 && h->opt_train_long_seq == 0)
     return h->fail(DPTNAV_ERR_INVALID, "training step: at most 256 chunks per mixture with DPTN blocks (S=%lld: the inter-chunk "
-                   "attention's sequence length); inference has no such limit", (long long)S);
+                   "attention's sequence length) unless option train_long_seq = 1; inference has no such limit", (long long)S);
   return DPTNAV_OK;
 }
 size_t dptnav_train_path_tape_bytes(dptnav_handle h, int B, int S) {
@@ -2902,6 +2923,7 @@ int dptnav_set_option(dptnav_handle h, const char* key, int value) {
   else if (k == "lstm_diag") h->opt_lstm_diag = (int)value;
   else if (k == "inject_fail") h->opt_inject_fail = value;
   else if (k == "debug_sync") h->opt_debug_sync = value != 0;
+  else if (k == "train_long_seq" && value >= 0 && value <= 2) h->opt_train_long_seq = value;
   else if (k == "train_fuse_probe") h->opt_train_fuse_probe = value != 0;
   else return h->fail(DPTNAV_ERR_INVALID, "unknown option '%s'", key);
   return DPTNAV_OK;

@@ -114,7 +114,26 @@ class _SeparateFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(outs)
 
 
-class _DPTNBase(nn.Module):
+class _LongTrainingKeyword(type):
+    """``Model(..., long_training=True)`` for the classes that set ``_long_training_keyword``: the keyword is taken off by the
+    class call and kept as an attribute, so every ``__init__`` keeps exactly the reference's parameters and defaults (the
+    drop-in contract; tests/test_mask_variant_host.py pins it) and a Hydra user still writes ``+model.long_training=true``."""
+
+    def __call__(cls, *args, **kwargs):
+        if not cls._long_training_keyword:
+            return super().__call__(*args, **kwargs)
+        long_training = bool(kwargs.pop("long_training", False))
+        module = super().__call__(*args, **kwargs)
+        module.long_training = long_training
+        return module
+
+
+class _DPTNBase(nn.Module, metaclass=_LongTrainingKeyword):
+    # DPTN blocks only: the training step on clips of more than 256 chunks (library option train_long_seq = 1, set on every
+    # engine _get_engine makes).  DPRNN blocks have no such limit and take no keyword.
+    _long_training_keyword = False
+    long_training = False
+
     def __init__(self, cfg: DPTNConfig):
         super().__init__()
         self.cfg = cfg
@@ -142,6 +161,8 @@ class _DPTNBase(nn.Module):
         eng = self._engine
         if eng is None or eng.device != device:
             eng = DptnEngine(self.cfg, device)
+            if self.long_training:
+                eng.set_option("train_long_seq", 1)
             self._engine = eng
         params = self._params()
         for k, p in params.items():
@@ -195,7 +216,9 @@ class _DPTNBase(nn.Module):
 
 
 class DPTNAVWavEncDec(_DPTNBase):
-    """Audio-visual DPTN (BASELINE configs 3/4) -- same constructor as the reference class of that name."""
+    """Audio-visual DPTN (BASELINE configs 3/4) -- same constructor as the reference class of that name, plus the keyword
+    ``long_training`` (training step beyond 256 chunks per mixture)."""
+    _long_training_keyword = True
 
     def __init__(self, num_features=64, video_emb_size=1024, hidden_video=128, kernel_size_enc=2, hidden_dim=32,
                  num_blocks=6, chunk_size=10, step_size=5, num_heads=4, dropout=0.1, bidir=True):
@@ -210,7 +233,9 @@ class DPTNAVWavEncDec(_DPTNBase):
 
 
 class DPTNWavEncDec(_DPTNBase):
-    """Audio-only DPTN (BASELINE config 2) -- same constructor as the reference class of that name."""
+    """Audio-only DPTN (BASELINE config 2) -- same constructor as the reference class of that name, plus the keyword
+    ``long_training`` (training step beyond 256 chunks per mixture)."""
+    _long_training_keyword = True
 
     def __init__(self, num_features=64, kernel_size_enc=2, hidden_dim=32, num_blocks=6, chunk_size=10, step_size=5,
                  num_heads=4, dropout=0.1, bidir=True):
@@ -226,7 +251,9 @@ class DPTNWavEncDec(_DPTNBase):
 class DPTNEncDec(_DPTNBase):
     """Audio-only masked DPTN (src/configs/model/dptn.yaml) -- same constructor as the reference class of that name
     (dptn.py:154-165).  Same blocks and separation conv as DPTNWavEncDec; per speaker the tail is
-    ReLU(tanh(output(u)) * sigmoid(output_gate(u))) * encoded instead of postprocessing(u) + encoded (dptn.py:141,189)."""
+    ReLU(tanh(output(u)) * sigmoid(output_gate(u))) * encoded instead of postprocessing(u) + encoded (dptn.py:141,189).
+    Plus the keyword ``long_training`` (training step beyond 256 chunks per mixture)."""
+    _long_training_keyword = True
 
     def __init__(self, num_features=64, kernel_size_enc=2, hidden_dim=32, num_blocks=6, chunk_size=10, step_size=5,
                  num_heads=4, dropout=0.1, bidir=True):
