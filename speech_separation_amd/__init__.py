@@ -4,7 +4,7 @@ from .spec import DPRNN_AUDIO, DPRNN_AV, DPTN_AUDIO, DPTN_AV, DPTN_MASK, DPTNCon
 __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "DPRNN_AV", "DPRNNEncDec", "DPRNNAVEncDec", "state_dict_spec", "synthetic_state_dict", "synthetic_inputs",
            "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
            "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss", "MAEWavLoss",
-           "MSEWavLoss", "STOIMetric", "SISDRMetric"]
+           "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "init_lipreader", "VideoSSModel", "make_embeddings"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
@@ -23,4 +23,7 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
     if name in ("SiSNRWavLoss", "MAEWavLoss", "MSEWavLoss", "STOIMetric", "SISDRMetric"):
         from . import metrics
         return getattr(metrics, name)
+    if name in ("LipreadingEngine", "Lipreading", "init_lipreader", "VideoSSModel", "make_embeddings"):
+        from . import lipreader
+        return getattr(lipreader, name)
     raise AttributeError(name)

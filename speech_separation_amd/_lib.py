@@ -80,6 +80,7 @@ DCTTRAIN_ABI_VERSION = 1
 DAVTRAIN_ABI_VERSION = 1
 WAVLOSS_ABI_VERSION = 1
 WAVMETRIC_ABI_VERSION = 1
+LIPFE_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -170,6 +171,23 @@ WAVMETRIC_SYMBOLS = {
     "wavmetric_stoi_pairs": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i64, _fp, _vp, _vp, _sz, _vp]),
 }
 
+#: every symbol include/lipfe.h declares (lip-reading front end: mouth video -> embeddings)
+LIPFE_SYMBOLS = {
+    "lipfe_abi_version": (_i, []),
+    "lipfe_create": (_i, [C.POINTER(_vp), _i]),
+    "lipfe_destroy": (None, [_vp]),
+    "lipfe_last_error": (C.c_char_p, [_vp]),
+    "lipfe_num_weights": (_i, [_vp]),
+    "lipfe_weight_name": (C.c_char_p, [_vp, _i]),
+    "lipfe_weight_numel": (_i64, [_vp, _i]),
+    "lipfe_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "lipfe_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "lipfe_forward": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, _fp, _vp, _sz, _vp]),
+    "lipfe_flops_per_stream": (C.c_double, [_i, _i, _i]),
+    "lipfe_min_bytes_per_stream": (C.c_double, [_i, _i, _i]),
+    "lipfe_weight_pack_bytes": (_sz, [_vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -190,7 +208,7 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
-                              + list(WAVMETRIC_SYMBOLS.items())):
+                              + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -204,7 +222,8 @@ def load() -> C.CDLL:
                             (lib.dcttrain_abi_version, DCTTRAIN_ABI_VERSION, "dcttrain"),
                             (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain"),
                             (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss"),
-                            (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric")):
+                            (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric"),
+                            (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -44,11 +44,14 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            "wavloss.hip": [],
            # wavmetric.hip: SI-SDR and STOI / ESTOI evaluation metrics; the DFT of the STOI runs on fp32 MFMA, accumulators in
            # architectural VGPRs (their squares are taken with plain VALU instructions)
-           "wavmetric.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+           "wavmetric.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+           # lipfe.hip: the lip-reading front end (Conv3d stem + ResNet-18 trunk); its convs are implicit GEMMs on fp32 MFMA with
+           # one accumulator tile per wave, BN / residual / activation applied to it with plain VALU instructions
+           "lipfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h")]
 
 
 def source_digest() -> str:
