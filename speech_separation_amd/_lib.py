@@ -81,6 +81,7 @@ DAVTRAIN_ABI_VERSION = 1
 WAVLOSS_ABI_VERSION = 1
 WAVMETRIC_ABI_VERSION = 1
 LIPFE_ABI_VERSION = 1
+SPECFE_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -188,6 +189,20 @@ LIPFE_SYMBOLS = {
     "lipfe_weight_pack_bytes": (_sz, [_vp]),
 }
 
+#: every symbol include/specfe.h declares (spectral front end: STFT, inverse STFT, their adjoints, log-mel; behind a handle)
+SPECFE_SYMBOLS = {
+    "specfe_abi_version": (_i, []),
+    "specfe_strerror": (C.c_char_p, [_i]),
+    "specfe_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "specfe_create_mel": (_i, [_i, _i, _i, _i, C.POINTER(_vp)]),
+    "specfe_destroy": (None, [_vp]),
+    "specfe_stft": (_i, [_vp, _fp, _i, _i64, _fp, _vp]),
+    "specfe_stft_backward": (_i, [_vp, _fp, _i, _i64, _fp, _vp]),
+    "specfe_istft": (_i, [_vp, _fp, _i, _i64, _i64, _fp, _vp]),
+    "specfe_istft_backward": (_i, [_vp, _fp, _i, _i64, _i64, _fp, _vp]),
+    "specfe_logmel": (_i, [_vp, _fp, _i, _i64, _fp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -208,7 +223,8 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SYMBOLS.items()) + list(CTASNET_SYMBOLS.items()) + list(DCTASNET_SYMBOLS.items())
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
-                              + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())):
+                              + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())
+                              + list(SPECFE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -223,7 +239,8 @@ def load() -> C.CDLL:
                             (lib.davtrain_abi_version, DAVTRAIN_ABI_VERSION, "davtrain"),
                             (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss"),
                             (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric"),
-                            (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe")):
+                            (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe"),
+                            (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -47,11 +47,14 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            "wavmetric.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # lipfe.hip: the lip-reading front end (Conv3d stem + ResNet-18 trunk); its convs are implicit GEMMs on fp32 MFMA with
            # one accumulator tile per wave, BN / residual / activation applied to it with plain VALU instructions
-           "lipfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+           "lipfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+           # specfe.hip: the spectral front end (STFT, inverse STFT, their adjoints, log-mel); the DFT runs on fp32 MFMA, accumulators
+           # in architectural VGPRs (the log-mel epilogue squares them with plain VALU instructions)
+           "specfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h", "specfe.h")]
 
 
 def source_digest() -> str:

@@ -108,7 +108,7 @@ def load_audio(path: str, target_sr: Optional[int] = None) -> torch.Tensor:
 def load_item(entry: Mapping[str, Optional[str]], target_sr: Optional[int] = None) -> Dict[str, object]:
     """One dataset element from its index entry, the parts of BaseDataset.__getitem__ (base_dataset.py:56-135) this path
     consumes: mix / s1 / s2 waveforms, the two lip embeddings, audio_path.  Spectrogram keys are not produced (the
-    separator ignores them, dptn_wav.py:171; they need torchaudio)."""
+    separator ignores them, dptn_wav.py:171): spectral.add_spectrogram_keys computes them for a whole batch on the device."""
     g = lambda k: entry.get(k)
     item: Dict[str, object] = {"mix": load_audio(entry["mix_wav_path"], target_sr), "s1": None, "s2": None, "s1_video": None,
                                "s2_video": None, "s1_embedding": None, "s2_embedding": None,

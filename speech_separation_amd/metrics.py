@@ -3,6 +3,7 @@
 Mirrors (does not import) the reference interfaces that consume the model's outputs:
   * ``SiSNRWavLoss()(**batch) -> {"loss": tensor}``          src/loss/ss_losses.py:117-130 (+ BaseSSLoss :21-26)
   * ``MAEWavLoss()`` / ``MSEWavLoss()``, same call            src/loss/ss_losses.py:65-93   (+ BaseSSLoss :21-26)
+  * ``MSESpecLoss()`` / ``L1SpecLoss()`` on spectrograms      src/loss/ss_losses.py:29-62   (+ BaseSSLoss :21-26)
   * ``SISNRiMetric(name=..., device=...)(**batch) -> value``  src/metrics/si_snri.py:7-30
   * ``SISNRMetric(name=..., device=...)(**batch) -> value``   src/metrics/si_snr.py:6-12
   * ``SISDRMetric(name=..., device=...)(**batch) -> value``   src/metrics/si_sdr.py
@@ -157,6 +158,35 @@ class MAEWavLoss(_PitWavLoss):
 class MSEWavLoss(_PitWavLoss):
     """The reference's PIT MSE loss on waveforms (ss_losses.py:80-93), or its per-utterance variant (``pit="utterance"``)."""
     kind = "mse"
+
+
+class _PitSpecLoss(_PitWavLoss):
+    """``Loss(pit="batch")(s1_spec_pred=..., s2_spec_pred=..., s1_spec_true=..., s2_spec_true=..., **batch)``: the MAE /
+    MSE criterion of include/wavloss.h on the [B, F * T] view of four spectrograms of one shape (a view, not a copy, for the
+    contiguous tensors the models and add_spectrogram_keys produce); the mean over every element is the reference's
+    ``reduction="mean"``.  Everything else -- ``{"loss": 0-dim device tensor}``, ``last``, ``last_perm``, ``pit=`` -- as
+    the waveform classes."""
+
+    def forward(self, s1_spec_pred, s2_spec_pred, s1_spec_true, s2_spec_true, **batch):
+        named = (("s1_spec_pred", s1_spec_pred), ("s2_spec_pred", s2_spec_pred), ("s1_spec_true", s1_spec_true),
+                 ("s2_spec_true", s2_spec_true))
+        for n, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{n}: expected a torch.Tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(s1_spec_pred.shape) or t.dim() < 2:
+                raise ValueError(f"{n}: shape {tuple(t.shape)} does not match s1_spec_pred's {tuple(s1_spec_pred.shape)}; the "
+                                 f"criterion takes four [batch, ...] spectrograms of one shape")
+        return super().forward(*[t.reshape(t.shape[0], -1) for _, t in named])
+
+
+class MSESpecLoss(_PitSpecLoss):
+    """The reference's PIT MSE loss on spectrograms (ss_losses.py:29-44), or its per-utterance variant (``pit="utterance"``)."""
+    kind = "mse"
+
+
+class L1SpecLoss(_PitSpecLoss):
+    """The reference's PIT L1 loss on spectrograms (ss_losses.py:47-62), or its per-utterance variant (``pit="utterance"``)."""
+    kind = "mae"
 
 
 class SiSNRWavLoss(_PitWavLoss):
