@@ -5,7 +5,8 @@ __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "D
            "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
            "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss", "MAEWavLoss",
            "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "init_lipreader", "VideoSSModel", "make_embeddings",
-           "STFT", "LogMelSpectrogram", "add_spectrogram_keys", "MSESpecLoss", "L1SpecLoss"]
+           "STFT", "LogMelSpectrogram", "add_spectrogram_keys", "MSESpecLoss", "L1SpecLoss",
+           "VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
@@ -30,4 +31,7 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
     if name in ("STFT", "LogMelSpectrogram", "add_spectrogram_keys"):
         from . import spectral
         return getattr(spectral, name)
+    if name in ("VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude"):
+        from . import voicefilter
+        return getattr(voicefilter, name)
     raise AttributeError(name)

@@ -82,6 +82,7 @@ WAVLOSS_ABI_VERSION = 1
 WAVMETRIC_ABI_VERSION = 1
 LIPFE_ABI_VERSION = 1
 SPECFE_ABI_VERSION = 1
+VFILT_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -203,6 +204,22 @@ SPECFE_SYMBOLS = {
     "specfe_logmel": (_i, [_vp, _fp, _i, _i64, _fp, _vp]),
 }
 
+#: every symbol include/vfilt.h declares (VoiceFilter separator: magnitude spectrogram + lip embeddings -> two masked spectrograms)
+VFILT_SYMBOLS = {
+    "vfilt_abi_version": (_i, []),
+    "vfilt_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "vfilt_destroy": (None, [_vp]),
+    "vfilt_last_error": (C.c_char_p, [_vp]),
+    "vfilt_num_weights": (_i, [_vp]),
+    "vfilt_weight_name": (C.c_char_p, [_vp, _i]),
+    "vfilt_weight_numel": (_i64, [_vp, _i]),
+    "vfilt_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "vfilt_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vfilt_forward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "vfilt_flops_per_item": (C.c_double, [_vp, _i, _i]),
+    "vfilt_min_bytes_per_item": (C.c_double, [_vp, _i, _i]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -224,7 +241,7 @@ def load() -> C.CDLL:
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
                               + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())
-                              + list(SPECFE_SYMBOLS.items())):
+                              + list(SPECFE_SYMBOLS.items()) + list(VFILT_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -240,7 +257,8 @@ def load() -> C.CDLL:
                             (lib.wavloss_abi_version, WAVLOSS_ABI_VERSION, "wavloss"),
                             (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric"),
                             (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe"),
-                            (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe")):
+                            (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe"),
+                            (lib.vfilt_abi_version, VFILT_ABI_VERSION, "vfilt")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

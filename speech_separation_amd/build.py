@@ -50,11 +50,14 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            "lipfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # specfe.hip: the spectral front end (STFT, inverse STFT, their adjoints, log-mel); the DFT runs on fp32 MFMA, accumulators
            # in architectural VGPRs (the log-mel epilogue squares them with plain VALU instructions)
-           "specfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+           "specfe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+           # vfilt.hip: the VoiceFilter separator; its 64 -> 64 convs run on lipfe's implicit-GEMM kernel and its dense products
+           # on a strided GEMM of the same tile shape, both with VALU epilogues on the accumulators
+           "vfilt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h", "specfe.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h", "specfe.h", "vfilt.h")]
 
 
 def source_digest() -> str:

@@ -180,10 +180,10 @@ int launch_conv(lipfe_ctx* c, hipStream_t st, const ConvDesc& d, const float* fo
   a.slope = d.slope >= 0 ? c->w[d.slope] : nullptr;
   a.res = res;  a.out = out;
   a.M = N * Ho * Wo;
-  a.Hi = Hi;  a.Wi = Wi;  a.Ho = Ho;  a.Wo = Wo;  a.Cin = d.cin;  a.Cout = d.cout;  a.stride = d.stride;  a.act = act;
+  a.Hi = Hi;  a.Wi = Wi;  a.Ho = Ho;  a.Wo = Wo;  a.Cin = d.cin;  a.Cout = d.cout;  a.stride = d.stride;  a.act = act;  a.dil = 1;
   const dim3 grid((unsigned)((a.M + LF_BM - 1) / LF_BM), (unsigned)(d.cout / LF_BN));
-  if (d.taps == 9) hipLaunchKernelGGL(lipfe_conv_kernel<3>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(lipfe_conv_kernel<1>, grid, dim3(256), 0, st, a);
+  if (d.taps == 9) hipLaunchKernelGGL((lipfe_conv_kernel<3, 3>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((lipfe_conv_kernel<1, 1>), grid, dim3(256), 0, st, a);
   LF_LAUNCH_CHECK(c, "lipfe conv");
   return LIPFE_OK;
 }

@@ -193,17 +193,19 @@ struct LfConvArgs {
   float* out;            // [M][Cout]
   long long M;
   int Hi, Wi, Ho, Wo, Cin, Cout, stride, act;
+  int dil;               // row dilation (the taps of a column are dil rows apart); columns are never dilated
 };
 
-// KS = 3 (pad 1) or 1 (pad 0).  grid (ceil(M / 64), Cout / 64), block 256: wave w owns the 32 x 32 sub-tile (w & 1, w >> 1).
+// KH x KW taps, zero padding (KH / 2) * dil rows and KW / 2 columns: 3 x 3 and 1 x 1 here, 7 x 1 and dilated 5 x 5 in
+// vfilt.hip.  grid (ceil(M / 64), Cout / 64), block 256: wave w owns the 32 x 32 sub-tile (w & 1, w >> 1).
 // One K step is 32 input channels of one tap: the next step's global loads are in flight while this one's MFMAs run.
 // Each step's 32 products are summed on their own and then added to the running total: with K up to 4608 one running
 // fp32 sum would carry about sqrt(K / 24) ulp of rounding error, the two levels about a quarter of that.
-template <int KS>
+template <int KH, int KW>
 __global__ void __launch_bounds__(256) lipfe_conv_kernel(LfConvArgs p) {
   __shared__ float As[LF_KC][LF_LDA];
   __shared__ __attribute__((aligned(16))) float Bs[LF_KC][LF_BN];
-  constexpr int PAD = KS / 2;
+  constexpr int PADY = KH / 2, PADX = KW / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 31, hh = lane >> 5, wm = wave & 1, wn = wave >> 1;
   const long long m0 = (long long)blockIdx.x * LF_BM;
@@ -220,8 +222,8 @@ __global__ void __launch_bounds__(256) lipfe_conv_kernel(LfConvArgs p) {
       const int ox = (int)(m % p.Wo);  m /= p.Wo;
       const int oy = (int)(m % p.Ho);  m /= p.Ho;
       a_base[j] = m * p.Hi * p.Wi * p.Cin;
-      a_y[j] = oy * p.stride - PAD;
-      a_x[j] = ox * p.stride - PAD;
+      a_y[j] = oy * p.stride - PADY * p.dil;
+      a_x[j] = ox * p.stride - PADX;
     } else {
       a_base[j] = 0;
       a_y[j] = -(1 << 20);
@@ -231,14 +233,14 @@ __global__ void __launch_bounds__(256) lipfe_conv_kernel(LfConvArgs p) {
   // B loader: thread -> rows bk + 16 j, columns 4 bq .. 4 bq + 3
   const int bk = tid >> 4, bq = tid & 15;
 
-  const int csteps = p.Cin / LF_KC, nsteps = KS * KS * csteps;
+  const int csteps = p.Cin / LF_KC, nsteps = KH * KW * csteps;
   float4 ra[2], rb[2];
   auto fetch = [&](int step) {
     const int tap = step / csteps, c0 = (step - tap * csteps) * LF_KC;
-    const int ky = tap / KS, kx = tap - ky * KS;
+    const int ky = tap / KW, kx = tap - ky * KW;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int iy = a_y[j] + ky, ix = a_x[j] + kx;
+      const int iy = a_y[j] + ky * p.dil, ix = a_x[j] + kx;
       ra[j] = (iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi)
                   ? ldg4(p.in + a_base[j] + ((long long)iy * p.Wi + ix) * p.Cin + c0 + 4 * aq)
                   : make_float4(0.f, 0.f, 0.f, 0.f);

@@ -1,0 +1,300 @@
+"""VoiceFilter on libdptnav (include/vfilt.h): the mixture's magnitude spectrogram and one lip-embedding sequence per speaker
+-> one masked spectrogram per speaker.  Replaces the reference's VoiceFilter (src/model/voicefilter.py) in eval mode and
+its dataset's get_magnitude (src/datasets/base_dataset.py:167-180).  Inference only.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Mapping, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from .engine import DptnEngine, _ConvTasNetEngineBase
+
+EMBED_SIZES = (512, 1024)
+MAX_INPUT_SIZE = 257
+_HIDDEN, _FC = 400, 600
+# the lip reader's test-time preprocessing (src/lipreader/lipreading/dataloaders.py:13-29)
+VIDEO_CROP, VIDEO_MEAN, VIDEO_STD = (88, 88), 0.421, 0.165
+# (index of the Conv2d in the reference's nn.Sequential, index of its BatchNorm2d, out, in, kernel rows, kernel columns)
+_CNN = ((1, 2, 64, 1, 1, 7), (5, 6, 64, 64, 7, 1), (9, 10, 64, 64, 5, 5), (13, 14, 64, 64, 5, 5), (17, 18, 64, 64, 5, 5),
+        (21, 22, 64, 64, 5, 5), (25, 26, 64, 64, 5, 5), (28, 29, 8, 64, 1, 1))
+
+
+def voicefilter_state_dict_spec(input_size: int, embed_size: int = 1024) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """[(key, shape, kind)] of VoiceFilter.state_dict() without the lip reader: the reference's 82 keys in its order.
+    kind: "param", "buffer" (running_mean / running_var) or "count" (the int64 num_batches_tracked)."""
+    F, E = int(input_size), int(embed_size)
+    spec = []
+    for layer in range(2):
+        for suffix in ("", "_reverse"):
+            s = f"_l{layer}{suffix}"
+            spec += [(f"gru.weight_ih{s}", (3 * F, E if layer == 0 else 2 * F), "param"), (f"gru.weight_hh{s}", (3 * F, F), "param"),
+                     (f"gru.bias_ih{s}", (3 * F,), "param"), (f"gru.bias_hh{s}", (3 * F,), "param")]
+    spec += [("fc_dvector.weight", (F, 2 * F), "param"), ("fc_dvector.bias", (F,), "param")]
+    for ci, bi, cout, cin, kh, kw in _CNN:
+        spec += [(f"cnn_layers.{ci}.weight", (cout, cin, kh, kw), "param"), (f"cnn_layers.{ci}.bias", (cout,), "param"),
+                 (f"cnn_layers.{bi}.weight", (cout,), "param"), (f"cnn_layers.{bi}.bias", (cout,), "param"),
+                 (f"cnn_layers.{bi}.running_mean", (cout,), "buffer"), (f"cnn_layers.{bi}.running_var", (cout,), "buffer"),
+                 (f"cnn_layers.{bi}.num_batches_tracked", (), "count")]
+    spec += [("lstm.weight_ih_l0", (4 * _HIDDEN, 9 * F), "param"), ("lstm.weight_hh_l0", (4 * _HIDDEN, _HIDDEN), "param"),
+             ("lstm.bias_ih_l0", (4 * _HIDDEN,), "param"), ("lstm.bias_hh_l0", (4 * _HIDDEN,), "param"),
+             ("fc.1.weight", (_FC, _HIDDEN), "param"), ("fc.1.bias", (_FC,), "param"),
+             ("fc.4.weight", (F, _FC), "param"), ("fc.4.bias", (F,), "param")]
+    return spec
+
+
+def _check_sizes(input_size: int, embed_size: int):
+    if not 1 <= int(input_size) <= MAX_INPUT_SIZE:
+        raise ValueError(f"input_size must be in [1, {MAX_INPUT_SIZE}], got {input_size}")
+    if int(embed_size) not in EMBED_SIZES:
+        raise ValueError(f"embed_size must be one of {EMBED_SIZES}, got {embed_size}")
+
+
+class VoiceFilterEngine(_ConvTasNetEngineBase):
+    """The VoiceFilter separator's forward (include/vfilt.h).  Same conventions as the other engines: borrowed weights
+    (bind / bound_to), a cached workspace taken through the optional `alloc` hook, work on the caller's current stream.
+    The library derives its weight copies in every forward, so nothing bound goes stale.  Of the base class only the
+    handle, binding and workspace duties apply: this ABI counts cost per item of (W, Tv)."""
+
+    def __init__(self, input_size: int, embed_size: int = 1024, device: torch.device | str = "cuda:0", alloc=None):
+        _check_sizes(input_size, embed_size)
+        self.input_size, self.embed_size = int(input_size), int(embed_size)
+        spec = [(k, s) for k, s, kind in voicefilter_state_dict_spec(input_size, embed_size) if kind != "count"]
+        super().__init__("vfilt", "VoiceFilter", spec, device, alloc, self.input_size, self.embed_size)
+        for i, (k, s) in enumerate(spec):
+            if int(self.lib.vfilt_weight_numel(self._h, i)) != math.prod(s):
+                raise RuntimeError(f"libdptnav's VoiceFilter disagrees on the size of {k}")
+
+    def workspace_bytes(self, B: int, W: int, Tv: int) -> int:
+        n = int(self.lib.vfilt_workspace_bytes(self._h, B, W, Tv))
+        if n == 0:
+            raise RuntimeError(f"unsupported shape: {self.lib.vfilt_last_error(self._h).decode()}")
+        return n
+
+    def flops_per_item(self, W: int, Tv: int) -> float:
+        return float(self.lib.vfilt_flops_per_item(self._h, W, Tv))
+
+    def min_bytes_per_item(self, W: int, Tv: int) -> float:
+        return float(self.lib.vfilt_min_bytes_per_item(self._h, W, Tv))
+
+    def _input(self, t, name, shape):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(t.shape)}")
+        if t.device != self.device:
+            raise ValueError(f"{name}: lives on {t.device}, engine is on {self.device}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected float32, got {t.dtype}")
+        return t.detach().contiguous()
+
+    def forward(self, mix_magnitude: torch.Tensor, s1_embedding: torch.Tensor, s2_embedding: torch.Tensor,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ws: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mix_magnitude (B, F, W), s1/s2_embedding (B, Tv, E) -> (s1_spec_pred, s2_spec_pred), each (B, F, W), enqueued on
+        the current stream.  `out` / `ws`: caller-provided results and workspace (workspace_bytes(B, W, Tv) bytes, uint8,
+        256-byte aligned)."""
+        if not isinstance(mix_magnitude, torch.Tensor) or mix_magnitude.dim() != 3:
+            raise ValueError("mix_magnitude: expected a (B, F, W) tensor")
+        if not isinstance(s1_embedding, torch.Tensor) or s1_embedding.dim() != 3:
+            raise ValueError("s1_embedding: expected a (B, Tv, E) tensor")
+        B, F, W = (int(d) for d in mix_magnitude.shape)
+        Tv = int(s1_embedding.shape[1])
+        if F != self.input_size:
+            raise ValueError(f"mix_magnitude: expected {self.input_size} frequency bins, got {F}")
+        mix = self._input(mix_magnitude, "mix_magnitude", (B, F, W))
+        e1 = self._input(s1_embedding, "s1_embedding", (B, Tv, self.embed_size))
+        e2 = self._input(s2_embedding, "s2_embedding", (B, Tv, self.embed_size))
+        self._need_bound("forward")
+        need = self.workspace_bytes(B, W, Tv)
+        if ws is None:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = self._alloc(need)
+            ws = self._ws
+        else:
+            DptnEngine._check_ws(self, ws, need)
+        if out is None:
+            o1, o2 = self._empty(B, F, W), self._empty(B, F, W)
+        else:
+            o1, o2 = out
+            for o in (o1, o2):
+                if (tuple(o.shape) != (B, F, W) or o.dtype != torch.float32 or o.device != self.device
+                        or not o.is_contiguous()):
+                    raise ValueError(f"out: expected two contiguous float32 ({B},{F},{W}) tensors on {self.device}")
+        rc = self.lib.vfilt_forward(self._h, mix.data_ptr(), e1.data_ptr(), e2.data_ptr(), B, W, Tv, o1.data_ptr(), o2.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), self._stream())
+        if rc:
+            self._raise(rc, "vfilt_forward")
+        return o1, o2
+
+
+class _Node(nn.Module):
+    """Container that only names a level of the state_dict keys."""
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("not callable: VoiceFilter runs on libdptnav")
+
+
+class VoiceFilter(nn.Module):
+    """The reference's VoiceFilter (src/model/voicefilter.py): same constructor arguments, same state_dict keys / shapes /
+    order, so the separator's 82 entries of its checkpoints load with strict=True (an attached lip reader adds its own
+    entries under `lipreader.`, in front, as in the reference; the reference's ShuffleNet lip reader is not built).
+    forward runs on libdptnav (include/vfilt.h) in eval mode; training (Dropout2d, BatchNorm statistics) is not built and
+    raises.  `embed_size` is the lip embedding's width: 1024 in the reference; this package's ResNet-18 lip reader gives 512.
+    `lipreader`: a module mapping (S, 1, T, H, W) to (S, T, embed_size); otherwise init_lipreader(lipreader_config,
+    lipreader_path) of this package when a config is given; otherwise none, and only forward_embeddings works."""
+
+    def __init__(self, input_size: int, lipreader_path: Optional[str] = None, lipreader_config: Optional[str] = None, *,
+                 embed_size: int = 1024, lipreader: Optional[nn.Module] = None):
+        super().__init__()
+        _check_sizes(input_size, embed_size)
+        self.input_size, self.embed_size = int(input_size), int(embed_size)
+        if lipreader is None and lipreader_config is not None:
+            from .lipreader import init_lipreader
+            lipreader = init_lipreader(lipreader_config, lipreader_path)
+        if lipreader is not None:
+            if getattr(lipreader, "backend_out", self.embed_size) != self.embed_size:
+                raise ValueError(f"the lip reader gives {lipreader.backend_out} values per frame: construct VoiceFilter with "
+                                 f"embed_size={lipreader.backend_out}")
+            self.lipreader = lipreader
+            for p in self.lipreader.parameters():
+                p.requires_grad = False
+            self.lipreader.eval()
+        else:
+            self.lipreader = None
+        self._spec = voicefilter_state_dict_spec(self.input_size, self.embed_size)
+        for key, shape, kind in self._spec:
+            parts = key.split(".")
+            node = self
+            for name in parts[:-1]:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            if kind == "param":
+                node.register_parameter(parts[-1], nn.Parameter(torch.empty(*shape)))
+            elif kind == "buffer":
+                node.register_buffer(parts[-1], torch.empty(*shape))
+            else:
+                node.register_buffer(parts[-1], torch.zeros((), dtype=torch.long))
+        self.reset_parameters()
+        self._engine: Optional[VoiceFilterEngine] = None
+
+    def reset_parameters(self):
+        """PyTorch's defaults for the reference's layers: GRU / LSTM U(+-1/sqrt(hidden)), Linear and Conv2d U(+-1/sqrt(fan_in)),
+        BatchNorm weight 1, bias 0, running statistics 0 / 1."""
+        with torch.no_grad():
+            for key, shape, kind in self._spec:
+                t = self._tensor(key)
+                if kind == "count" or key.endswith("running_mean"):
+                    t.zero_()
+                elif key.endswith("running_var"):
+                    t.fill_(1.0)
+                elif key.startswith("gru."):
+                    t.uniform_(-1.0, 1.0).mul_(1.0 / math.sqrt(self.input_size))
+                elif key.startswith("lstm."):
+                    t.uniform_(-1.0, 1.0).mul_(1.0 / math.sqrt(_HIDDEN))
+                elif len(shape) > 1:
+                    t.uniform_(-1.0, 1.0).mul_(1.0 / math.sqrt(math.prod(shape[1:])))
+                elif key.startswith("cnn_layers.") and int(key.split(".")[1]) in [b for _, b, *_ in _CNN]:
+                    t.fill_(1.0) if key.endswith("weight") else t.zero_()
+                else:    # bias of a Linear / Conv2d: the bound of its weight
+                    w = self._tensor(key[:-4] + "weight")
+                    t.uniform_(-1.0, 1.0).mul_(1.0 / math.sqrt(math.prod(w.shape[1:])))
+
+    def _tensor(self, key: str) -> torch.Tensor:
+        node = self
+        for name in key.split("."):
+            node = getattr(node, name)
+        return node
+
+    def _float_tensors(self) -> Dict[str, torch.Tensor]:
+        return {key: self._tensor(key) for key, _, kind in self._spec if kind != "count"}
+
+    def train(self, mode: bool = True):
+        """The lip reader stays in eval mode.  Returns self (the reference's override returns None)."""
+        super().train(mode)
+        if self.lipreader is not None:
+            self.lipreader.eval()
+        return self
+
+    def _get_engine(self, device: torch.device) -> VoiceFilterEngine:
+        if device.type != "cuda":
+            raise RuntimeError(f"VoiceFilter computes only on an AMD GPU through libdptnav (got a {device} tensor); there is no "
+                               f"CPU/PyTorch fallback")
+        eng = self._engine
+        if eng is None or eng.device != device:
+            eng = self._engine = VoiceFilterEngine(self.input_size, self.embed_size, device)
+        tensors = self._float_tensors()
+        for k, t in tensors.items():
+            if t.device != device:
+                raise RuntimeError(f"{k} is on {t.device} but the input is on {device}: call model.to(device)")
+        if not eng.bound_to(tensors):
+            eng.bind(tensors)
+        return eng
+
+    def _need_eval(self):
+        if self.training:
+            raise RuntimeError("VoiceFilter: the training step (Dropout2d, BatchNorm batch statistics, backward) is not built; "
+                               "call model.eval() for inference")
+
+    def forward_embeddings(self, mix_magnitude, s1_embedding, s2_embedding, out=None, ws=None):
+        """The separator alone: mix_magnitude (B, F, W), s1/s2_embedding (B, Tv, embed_size) -> {"s1_spec_pred", "s2_spec_pred"},
+        each (B, F, W), without grad."""
+        self._need_eval()
+        s1, s2 = self._get_engine(mix_magnitude.device).forward(mix_magnitude, s1_embedding, s2_embedding, out=out, ws=ws)
+        return {"s1_spec_pred": s1, "s2_spec_pred": s2}
+
+    def _embed(self, video: torch.Tensor) -> torch.Tensor:
+        """(S, Tv, H, W) raw mouth frames in [0, 255] -> (S, Tv, embed_size): the reference's test-time pipeline
+        (get_preprocessing_pipelines("video")["test"]: x / 255, CenterCrop(88, 88), (x - 0.421) / 0.165) and the lip reader.
+        This package's Lipreading takes crop and affine inside its stem's load (forward_window: no cropped or normalised
+        copy); any other module gets the preprocessed tensor as (S, 1, Tv, 88, 88)."""
+        S, Tv, H, W = (int(d) for d in video.shape)
+        th, tw = VIDEO_CROP
+        if H < th or W < tw:
+            raise ValueError(f"s1_video / s2_video: {H} x {W} frames are smaller than the {th} x {tw} centre crop")
+        y0, x0 = (H - th) // 2, (W - tw) // 2
+        with torch.no_grad():
+            if hasattr(self.lipreader, "forward_window"):
+                return self.lipreader.forward_window(video, (y0, x0, th, tw), (1.0 / (255.0 * VIDEO_STD), -VIDEO_MEAN / VIDEO_STD))
+            x = ((video / 255.0)[:, :, y0:y0 + th, x0:x0 + tw] - VIDEO_MEAN) / VIDEO_STD
+            return self.lipreader(x.unsqueeze(1).contiguous(), lengths=[Tv] * S)
+
+    def forward(self, mix_magnitude, s1_video, s2_video, **batch):
+        """mix_magnitude (B, F, W); s1/s2_video (B, Tv, H, W'): RAW mouth frames in [0, 255], at least 88 x 88, as the
+        reference's datasets deliver them.  As in the reference, every video goes through the lip reader's test-time
+        pipeline (x / 255, centre crop to 88 x 88, (x - 0.421) / 0.165) before the lip reader; both speakers share one
+        lip-reader call.  For clips that are already cropped and normalised, compute the embeddings yourself and call
+        forward_embeddings."""
+        self._need_eval()
+        if self.lipreader is None:
+            raise RuntimeError(f"VoiceFilter was built without a lip reader (embed_size={self.embed_size}): pass lipreader= or "
+                               f"lipreader_config= (this package's ResNet-18 lip reader needs embed_size=512), or call "
+                               f"forward_embeddings(mix_magnitude, s1_embedding, s2_embedding) with precomputed embeddings")
+        if s1_video.dim() != 4 or s1_video.shape != s2_video.shape:
+            raise ValueError(f"s1_video / s2_video: expected two (B,Tv,H,W), got {tuple(s1_video.shape)} and {tuple(s2_video.shape)}")
+        B = int(s1_video.shape[0])
+        emb = self._embed(torch.cat([s1_video, s2_video], dim=0).float())
+        return self.forward_embeddings(mix_magnitude, emb[:B], emb[B:])
+
+
+def magnitude_from_stft(re: torch.Tensor, im: torch.Tensor):
+    """(Re S, Im S) -> (spec, phase) of the reference's get_magnitude: spec = clamp((20 log10(max(|S|, 1e-5)) - 20) / 100,
+    -1, 0) + 1, phase = angle(S).  Plain torch operators at the inputs' dtype and device."""
+    mag = torch.clamp(torch.sqrt(re * re + im * im), min=1e-5)
+    spec = torch.clamp((20.0 * torch.log10(mag) - 20.0) / 100.0, min=-1.0, max=0.0) + 1.0
+    return spec, torch.atan2(im, re)
+
+
+def voicefilter_magnitude(audio: torch.Tensor, n_fft: int = 400, hop_length: int = 100):
+    """The reference's get_magnitude (src/datasets/base_dataset.py:167-180) on the device: audio (B, T) or (T,) -> (spec, phase),
+    each (B, n_fft // 2 + 1, T // hop_length + 1) (no B for a 1-D input): spec = clamp((20 log10(max(|S|, 1e-5)) - 20) / 100,
+    -1, 0) + 1 in [0, 1], phase = angle(S), with S the Hann-window STFT of this package (spectral.STFT)."""
+    from .spectral import STFT
+    one = audio.dim() == 1
+    S = STFT(n_fft, hop_length).stft(audio.detach()[None] if one else audio.detach())     # [B, 2, frames, F]
+    spec, phase = (t.contiguous() for t in magnitude_from_stft(S[:, 0].transpose(1, 2), S[:, 1].transpose(1, 2)))
+    return (spec[0], phase[0]) if one else (spec, phase)
