@@ -4,7 +4,7 @@ from .spec import DPRNN_AUDIO, DPRNN_AV, DPTN_AUDIO, DPTN_AV, DPTN_MASK, DPTNCon
 __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "DPRNN_AV", "DPRNNEncDec", "DPRNNAVEncDec", "state_dict_spec", "synthetic_state_dict", "synthetic_inputs",
            "DptnEngine", "DPTNAVWavEncDec", "DPTNWavEncDec", "DPTNEncDec", "ConvTasNet", "ConvTasNetEngine", "TrainableConvTasNet", "ConvTasNetTrainEngine", "DeepConvTasNet", "DeepAVConvTasNet",
            "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss", "MAEWavLoss",
-           "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "init_lipreader", "VideoSSModel", "make_embeddings",
+           "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "ShuffleNetLipreadingEngine", "ShuffleNetLipreading", "init_lipreader", "VideoSSModel", "make_embeddings",
            "STFT", "LogMelSpectrogram", "add_spectrogram_keys", "MSESpecLoss", "L1SpecLoss",
            "VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude"]
 
@@ -25,7 +25,7 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
     if name in ("SiSNRWavLoss", "MAEWavLoss", "MSEWavLoss", "STOIMetric", "SISDRMetric", "MSESpecLoss", "L1SpecLoss"):
         from . import metrics
         return getattr(metrics, name)
-    if name in ("LipreadingEngine", "Lipreading", "init_lipreader", "VideoSSModel", "make_embeddings"):
+    if name in ("LipreadingEngine", "Lipreading", "ShuffleNetLipreadingEngine", "ShuffleNetLipreading", "init_lipreader", "VideoSSModel", "make_embeddings"):
         from . import lipreader
         return getattr(lipreader, name)
     if name in ("STFT", "LogMelSpectrogram", "add_spectrogram_keys"):

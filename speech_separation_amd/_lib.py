@@ -83,6 +83,7 @@ WAVMETRIC_ABI_VERSION = 1
 LIPFE_ABI_VERSION = 1
 SPECFE_ABI_VERSION = 1
 VFILT_ABI_VERSION = 1
+LIPSN_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -220,6 +221,24 @@ VFILT_SYMBOLS = {
     "vfilt_min_bytes_per_item": (C.c_double, [_vp, _i, _i]),
 }
 
+#: every symbol include/lipsn.h declares (ShuffleNet-v2 lip reader: mouth video -> 1024-wide embeddings)
+LIPSN_SYMBOLS = {
+    "lipsn_abi_version": (_i, []),
+    "lipsn_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "lipsn_destroy": (None, [_vp]),
+    "lipsn_last_error": (C.c_char_p, [_vp]),
+    "lipsn_num_weights": (_i, [_vp]),
+    "lipsn_weight_name": (C.c_char_p, [_vp, _i]),
+    "lipsn_weight_numel": (_i64, [_vp, _i]),
+    "lipsn_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "lipsn_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "lipsn_forward": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, C.c_float, _fp, _vp, _sz, _vp]),
+    "lipsn_launches_per_forward": (_i, []),
+    "lipsn_flops_per_stream": (C.c_double, [_i, _i, _i, _i]),
+    "lipsn_min_bytes_per_stream": (C.c_double, [_i, _i, _i, _i]),
+    "lipsn_weight_pack_bytes": (_sz, [_vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -241,7 +260,8 @@ def load() -> C.CDLL:
                       + list(CTTRAIN_SYMBOLS.items()) + list(DCTTRAIN_SYMBOLS.items())
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
                               + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())
-                              + list(SPECFE_SYMBOLS.items()) + list(VFILT_SYMBOLS.items())):
+                              + list(SPECFE_SYMBOLS.items()) + list(VFILT_SYMBOLS.items())
+                              + list(LIPSN_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -258,7 +278,8 @@ def load() -> C.CDLL:
                             (lib.wavmetric_abi_version, WAVMETRIC_ABI_VERSION, "wavmetric"),
                             (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe"),
                             (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe"),
-                            (lib.vfilt_abi_version, VFILT_ABI_VERSION, "vfilt")):
+                            (lib.vfilt_abi_version, VFILT_ABI_VERSION, "vfilt"),
+                            (lib.lipsn_abi_version, LIPSN_ABI_VERSION, "lipsn")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -1,6 +1,8 @@
-"""The lip-reading front end on libdptnav (include/lipfe.h): mouth video -> (S, T, 512) embeddings, the input of the
-audio-visual separators.  Replaces the reference's Lipreading(extract_feats=True) (src/lipreader/lipreading/model.py:141-273),
-init_lipreader (src/utils/init_utils.py:168-207), profiler.py's VideoSSModel and make_embeddings.py.  Inference only.
+"""The lip-reading front ends on libdptnav: mouth video -> per-frame embeddings, the input of the audio-visual separators.
+Lipreading is the ResNet-18 lip reader (include/lipfe.h, (S, T, 512)), ShuffleNetLipreading the ShuffleNet-v2 one
+(include/lipsn.h, (S, T, 1024): the lip reader of the reference's VoiceFilter).  Replaces the reference's
+Lipreading(extract_feats=True) (src/lipreader/lipreading/model.py:141-273), init_lipreader (src/utils/init_utils.py:168-207),
+profiler.py's VideoSSModel and make_embeddings.py.  Inference only.
 """
 from __future__ import annotations
 
@@ -17,8 +19,11 @@ import torch.nn as nn
 from . import _lib
 from .engine import DptnEngine, _ConvTasNetEngineBase
 
-RELU_TYPES = {"relu": 0, "prelu": 1, "swish": 2}   # LIPFE_RELU / LIPFE_PRELU / LIPFE_SWISH
+RELU_TYPES = {"relu": 0, "prelu": 1, "swish": 2}   # LIPFE_RELU / LIPFE_PRELU / LIPFE_SWISH, and the same of LIPSN_*
 _PLANES = (64, 128, 256, 512)
+SHUFFLENET_WIDTHS = {0.5: (48, 96, 192), 1.0: (116, 232, 464)}   # width_mult -> stage widths (width_x2 of lipsn_create: 1, 2)
+_SN_REPEATS = (4, 8, 4)
+_SN_STEM, _SN_EMBED = 24, 1024
 
 
 def lipreader_state_dict_spec(relu_type: str = "swish") -> List[Tuple[str, Tuple[int, ...], str]]:
@@ -53,39 +58,87 @@ def lipreader_state_dict_spec(relu_type: str = "swish") -> List[Tuple[str, Tuple
     return spec
 
 
+def _shufflenet_width(width_mult) -> float:
+    try:
+        w = float(width_mult)
+    except (TypeError, ValueError):
+        w = None
+    if w not in SHUFFLENET_WIDTHS:
+        raise NotImplementedError(f"ShuffleNet lip reader: width_mult={width_mult!r} is not built (0.5 or 1.0; no lip-reader "
+                                  f"config of the reference uses 1.5 or 2.0)")
+    return w
+
+
+def shufflenet_state_dict_spec(relu_type: str = "prelu", width_mult: float = 1.0) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """[(key, shape, kind)] of the reference's Lipreading(backbone_type="shufflenet").state_dict() without tcn.*: the trunk
+    Sequential(features, conv_last, globalpool) is registered before the stem.  kind as lipreader_state_dict_spec."""
+    if relu_type not in RELU_TYPES:
+        raise ValueError(f"relu_type must be one of {sorted(RELU_TYPES)}, got {relu_type!r}")
+    stages = SHUFFLENET_WIDTHS[_shufflenet_width(width_mult)]
+
+    def conv_bn(p, i, shape):
+        q = f"{p}{i + 1}."
+        C_ = shape[0]
+        return [(f"{p}{i}.weight", shape, "param"), (q + "weight", (C_,), "param"), (q + "bias", (C_,), "param"),
+                (q + "running_mean", (C_,), "buffer"), (q + "running_var", (C_,), "buffer"), (q + "num_batches_tracked", (), "count")]
+
+    spec, inp, bi = [], _SN_STEM, 0
+    for width, repeats in zip(stages, _SN_REPEATS):
+        ch = width // 2
+        for r in range(repeats):
+            p = f"trunk.0.{bi}."
+            if r == 0:   # the stride-2 form: both branches read the whole input
+                spec += conv_bn(p + "banch1.", 0, (inp, 1, 3, 3)) + conv_bn(p + "banch1.", 2, (ch, inp, 1, 1))
+            spec += conv_bn(p + "banch2.", 0, (ch, inp if r == 0 else ch, 1, 1))
+            spec += conv_bn(p + "banch2.", 3, (ch, 1, 3, 3)) + conv_bn(p + "banch2.", 5, (ch, ch, 1, 1))
+            inp = width
+            bi += 1
+    spec += conv_bn("trunk.1.", 0, (_SN_EMBED, inp, 1, 1))
+    spec += conv_bn("frontend3D.", 0, (_SN_STEM, 1, 5, 7, 7))
+    if relu_type == "prelu":
+        spec.append(("frontend3D.2.weight", (_SN_STEM,), "param"))
+    return spec
+
+
 class LipreadingEngine(_ConvTasNetEngineBase):
     """The lip-reading front end's forward (include/lipfe.h).  Same conventions as the other engines: borrowed weights
     (bind / bound_to), a cached workspace taken through the optional `alloc` hook, work on the caller's current stream.
     The library derives its weight copies in every forward, so nothing bound goes stale.  Of the base class only the
     handle, binding and workspace duties apply: this ABI has no frame arithmetic and counts cost per stream, not per mixture."""
 
+    embed = 512          # values per frame
+    _cost_args = ()      # what <prefix>_flops_per_stream / _min_bytes_per_stream take in front of (T, H, W)
+
     def __init__(self, device: torch.device | str = "cuda:0", relu_type: str = "swish", alloc=None):
         self.relu_type = relu_type
         spec = [(k, s) for k, s, kind in lipreader_state_dict_spec(relu_type) if kind != "count"]
-        super().__init__("lipfe", "lip-reading front end", spec, device, alloc, RELU_TYPES[relu_type])
+        self._create("lipfe", "lip-reading front end", spec, device, alloc, RELU_TYPES[relu_type])
+
+    def _create(self, prefix, what, spec, device, alloc, *create_args):
+        _ConvTasNetEngineBase.__init__(self, prefix, what, spec, device, alloc, *create_args)
         for i, (k, s) in enumerate(spec):
-            if int(self.lib.lipfe_weight_numel(self._h, i)) != math.prod(s):
-                raise RuntimeError(f"libdptnav's lip-reading front end disagrees on the size of {k}")
+            if int(self._fn("weight_numel")(self._h, i)) != math.prod(s):
+                raise RuntimeError(f"libdptnav's {what} disagrees on the size of {k}")
 
     def workspace_bytes(self, S: int, T: int, H: int, W: int) -> int:
-        n = int(self.lib.lipfe_workspace_bytes(self._h, S, T, H, W))
+        n = int(self._fn("workspace_bytes")(self._h, S, T, H, W))
         if n == 0:
-            raise RuntimeError(f"unsupported shape: {self.lib.lipfe_last_error(self._h).decode()}")
+            raise RuntimeError(f"unsupported shape: {self._fn('last_error')(self._h).decode()}")
         return n
 
     def weight_pack_bytes(self) -> int:
-        return int(self.lib.lipfe_weight_pack_bytes(self._h))
+        return int(self._fn("weight_pack_bytes")(self._h))
 
     def flops_per_stream(self, T: int, H: int, W: int) -> float:
-        return float(self.lib.lipfe_flops_per_stream(T, H, W))
+        return float(self._fn("flops_per_stream")(*self._cost_args, T, H, W))
 
     def min_bytes_per_stream(self, T: int, H: int, W: int) -> float:
-        return float(self.lib.lipfe_min_bytes_per_stream(T, H, W))
+        return float(self._fn("min_bytes_per_stream")(*self._cost_args, T, H, W))
 
     def forward(self, x: torch.Tensor, window: Optional[Tuple[int, int, int, int]] = None,
                 affine: Tuple[float, float] = (1.0, 0.0), out: Optional[torch.Tensor] = None,
                 ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x (S, 1, T, Hin, Win) or (S, T, Hin, Win) -> (S, T, 512), enqueued on the current stream.  window = (y0, x0, H, W)
+        """x (S, 1, T, Hin, Win) or (S, T, Hin, Win) -> (S, T, embed), enqueued on the current stream.  window = (y0, x0, H, W)
         inside the Hin x Win frame (default: all of it); affine = (a, b): the network sees a * x + b.  `out` / `ws`:
         caller-provided result and workspace (workspace_bytes(S, T, H, W) bytes, uint8, 256-byte aligned)."""
         if not isinstance(x, torch.Tensor):
@@ -110,16 +163,33 @@ class LipreadingEngine(_ConvTasNetEngineBase):
             ws = self._ws
         else:
             DptnEngine._check_ws(self, ws, need)
+        E = self.embed
         if out is None:
-            out = self._empty(S, T, 512)
-        elif (tuple(out.shape) != (S, T, 512) or out.dtype != torch.float32 or out.device != self.device
+            out = self._empty(S, T, E)
+        elif (tuple(out.shape) != (S, T, E) or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
-            raise ValueError(f"out: expected a contiguous float32 ({S},{T},512) tensor on {self.device}")
-        rc = self.lib.lipfe_forward(self._h, x.data_ptr(), S, T, Hin, Win, y0, x0, H, W, float(affine[0]), float(affine[1]),
-                                    out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+            raise ValueError(f"out: expected a contiguous float32 ({S},{T},{E}) tensor on {self.device}")
+        rc = self._fn("forward")(self._h, x.data_ptr(), S, T, Hin, Win, y0, x0, H, W, float(affine[0]), float(affine[1]),
+                                 out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         if rc:
-            self._raise(rc, "lipfe_forward")
+            self._raise(rc, f"{self._prefix}_forward")
         return out
+
+
+class ShuffleNetLipreadingEngine(LipreadingEngine):
+    """The ShuffleNet-v2 lip reader's forward (include/lipsn.h): x -> (S, T, 1024) for 65 <= H, W <= 160.  Conventions and
+    methods as LipreadingEngine; one forward is `launches_per_forward()` kernel launches, one of them per InvertedResidual."""
+
+    embed = _SN_EMBED
+
+    def __init__(self, device: torch.device | str = "cuda:0", relu_type: str = "prelu", width_mult: float = 1.0, alloc=None):
+        self.relu_type, self.width_mult = relu_type, _shufflenet_width(width_mult)
+        self._cost_args = (int(round(2 * self.width_mult)),)
+        spec = [(k, s) for k, s, kind in shufflenet_state_dict_spec(relu_type, self.width_mult) if kind != "count"]
+        self._create("lipsn", "ShuffleNet lip reader", spec, device, alloc, RELU_TYPES[relu_type], self._cost_args[0])
+
+    def launches_per_forward(self) -> int:
+        return int(self.lib.lipsn_launches_per_forward())
 
 
 class _Node(nn.Module):
@@ -129,29 +199,12 @@ class _Node(nn.Module):
         raise RuntimeError("not callable: Lipreading runs on libdptnav")
 
 
-class Lipreading(nn.Module):
-    """The reference's Lipreading as a feature extractor (src/lipreader/lipreading/model.py:141-273): same constructor
-    keywords, same state_dict keys / shapes / order minus the tcn.* back end, which extract_feats=True never runs and which
-    is not built here.  forward runs on libdptnav (include/lipfe.h); inference only: train() behaves as eval() and the
-    output carries no grad."""
+class _LipreaderModule(nn.Module):
+    """What the two lip readers share: the reference's state_dict entries as bare tensors (`_build`), its initialisation, and
+    a forward on libdptnav through an engine bound to those tensors.  Inference only: train() behaves as eval()."""
 
-    def __init__(self, modality="video", hidden_dim=256, backbone_type="resnet", num_classes=500, relu_type="prelu",
-                 tcn_options={}, densetcn_options={}, width_mult=1.0, use_boundary=False, extract_feats=False):
-        super().__init__()
-        if modality != "video":
-            raise NotImplementedError(f"Lipreading: modality={modality!r} is not built (only 'video')")
-        if backbone_type != "resnet":
-            raise NotImplementedError(f"Lipreading: backbone_type={backbone_type!r} is not built (only 'resnet')")
-        if relu_type not in RELU_TYPES:
-            raise NotImplementedError(f"Lipreading: relu_type={relu_type!r} is not built (one of {sorted(RELU_TYPES)})")
-        if use_boundary:
-            raise NotImplementedError("Lipreading: use_boundary=True is not built")
-        if not extract_feats:
-            raise NotImplementedError("Lipreading: extract_feats=False is not built (the TCN back end); pass extract_feats=True")
-        self.modality, self.backbone_type, self.relu_type = modality, backbone_type, relu_type
-        self.use_boundary, self.extract_feats = use_boundary, extract_feats
-        self.frontend_nout, self.backend_out = 64, 512
-        self._spec = lipreader_state_dict_spec(relu_type)
+    def _build(self, spec):
+        self._spec = spec
         for key, shape, kind in self._spec:
             parts = key.split(".")
             node = self
@@ -198,13 +251,16 @@ class Lipreading(nn.Module):
     def train(self, mode: bool = True):
         return super().train(False)
 
+    def _make_engine(self, device: torch.device) -> LipreadingEngine:
+        raise NotImplementedError
+
     def _get_engine(self, device: torch.device) -> LipreadingEngine:
         if device.type != "cuda":
-            raise RuntimeError(f"Lipreading computes only on an AMD GPU through libdptnav (got a {device} tensor); there is no "
-                               f"CPU/PyTorch fallback")
+            raise RuntimeError(f"{type(self).__name__} computes only on an AMD GPU through libdptnav (got a {device} tensor); "
+                               f"there is no CPU/PyTorch fallback")
         eng = self._engine
         if eng is None or eng.device != device:
-            eng = self._engine = LipreadingEngine(device, self.relu_type)
+            eng = self._engine = self._make_engine(device)
         tensors = self._float_tensors()
         for k, t in tensors.items():
             if t.device != device:
@@ -214,7 +270,8 @@ class Lipreading(nn.Module):
         return eng
 
     def forward(self, x, lengths=None, boundaries=None):
-        """x (S, 1, T, H, W) -> (S, T, 512).  `lengths` is accepted and unused, as in the reference with extract_feats=True."""
+        """x (S, 1, T, H, W) -> (S, T, backend_out).  `lengths` is accepted and unused, as in the reference with
+        extract_feats=True."""
         return self._get_engine(x.device).forward(x)
 
     def forward_window(self, x, window, affine=(1.0, 0.0)):
@@ -223,13 +280,77 @@ class Lipreading(nn.Module):
         return self._get_engine(x.device).forward(x, window=window, affine=affine)
 
 
-def init_lipreader(config, path) -> Lipreading:
+class Lipreading(_LipreaderModule):
+    """The reference's Lipreading as a feature extractor (src/lipreader/lipreading/model.py:141-273): same constructor
+    keywords, same state_dict keys / shapes / order minus the tcn.* back end, which extract_feats=True never runs and which
+    is not built here.  forward runs on libdptnav (include/lipfe.h); inference only: train() behaves as eval() and the
+    output carries no grad."""
+
+    def __init__(self, modality="video", hidden_dim=256, backbone_type="resnet", num_classes=500, relu_type="prelu",
+                 tcn_options={}, densetcn_options={}, width_mult=1.0, use_boundary=False, extract_feats=False):
+        super().__init__()
+        if modality != "video":
+            raise NotImplementedError(f"Lipreading: modality={modality!r} is not built (only 'video')")
+        if backbone_type != "resnet":
+            raise NotImplementedError(f"Lipreading: backbone_type={backbone_type!r} is not built (only 'resnet'; "
+                                      f"ShuffleNetLipreading is the 'shufflenet' one)")
+        if relu_type not in RELU_TYPES:
+            raise NotImplementedError(f"Lipreading: relu_type={relu_type!r} is not built (one of {sorted(RELU_TYPES)})")
+        if use_boundary:
+            raise NotImplementedError("Lipreading: use_boundary=True is not built")
+        if not extract_feats:
+            raise NotImplementedError("Lipreading: extract_feats=False is not built (the TCN back end); pass extract_feats=True")
+        self.modality, self.backbone_type, self.relu_type = modality, backbone_type, relu_type
+        self.use_boundary, self.extract_feats = use_boundary, extract_feats
+        self.frontend_nout, self.backend_out = 64, 512
+        self._build(lipreader_state_dict_spec(relu_type))
+
+    def _make_engine(self, device):
+        return LipreadingEngine(device, self.relu_type)
+
+
+class ShuffleNetLipreading(_LipreaderModule):
+    """The reference's Lipreading(backbone_type="shufflenet") as a feature extractor (src/lipreader/lipreading/model.py:141-273,
+    models/shufflenetv2.py): the lip reader its VoiceFilter is written for (lrw_snv1x_tcn1x.json).  Same constructor keywords,
+    same state_dict keys / shapes / order minus the tcn.* back end, which extract_feats=True never runs.  width_mult 0.5 or
+    1.0; relu_type is the stem's activation (the trunk is ReLU).  forward runs on libdptnav (include/lipsn.h) for frames of
+    65 .. 160 pixels a side; inference only: train() behaves as eval() and the output carries no grad."""
+
+    def __init__(self, modality="video", hidden_dim=256, backbone_type="shufflenet", num_classes=500, relu_type="prelu",
+                 tcn_options={}, densetcn_options={}, width_mult=1.0, use_boundary=False, extract_feats=False):
+        super().__init__()
+        if modality != "video":
+            raise NotImplementedError(f"ShuffleNetLipreading: modality={modality!r} is not built (only 'video')")
+        if backbone_type != "shufflenet":
+            raise NotImplementedError(f"ShuffleNetLipreading: backbone_type={backbone_type!r} is not built here (only "
+                                      f"'shufflenet'; Lipreading is the 'resnet' one)")
+        if relu_type not in RELU_TYPES:
+            raise NotImplementedError(f"ShuffleNetLipreading: relu_type={relu_type!r} is not built (one of {sorted(RELU_TYPES)})")
+        if use_boundary:
+            raise NotImplementedError("ShuffleNetLipreading: use_boundary=True is not built")
+        if not extract_feats:
+            raise NotImplementedError("ShuffleNetLipreading: extract_feats=False is not built (the TCN back end); pass "
+                                      "extract_feats=True")
+        self.width_mult = _shufflenet_width(width_mult)
+        self.modality, self.backbone_type, self.relu_type = modality, backbone_type, relu_type
+        self.use_boundary, self.extract_feats = use_boundary, extract_feats
+        self.frontend_nout, self.backend_out, self.stage_out_channels = _SN_STEM, _SN_EMBED, _SN_EMBED
+        self._build(shufflenet_state_dict_spec(relu_type, self.width_mult))
+
+    def _make_engine(self, device):
+        return ShuffleNetLipreadingEngine(device, self.relu_type, self.width_mult)
+
+
+def init_lipreader(config, path) -> _LipreaderModule:
     """The reference's init_lipreader (src/utils/init_utils.py:168-207): `config` is one of its lip-reader JSON files
-    (backbone_type, relu_type, ...), `path` a checkpoint with a "model_state_dict" entry, e.g. lrw_resnet18_mstcn_video.pth.
-    As there, entries the model does not have (tcn.*) or has in another shape are left out (strict=False)."""
+    (backbone_type, relu_type, width_mult, ...), `path` a checkpoint with a "model_state_dict" entry, e.g.
+    lrw_resnet18_mstcn_video.pth or lrw_snv1x_tcn1x.pth.  backbone_type "resnet" gives a Lipreading, "shufflenet" a
+    ShuffleNetLipreading.  As there, entries the model does not have (tcn.*) or has in another shape are left out
+    (strict=False)."""
     with open(config) as f:
         args = json.load(f)
-    model = Lipreading(modality="video", num_classes=args.get("num_classes", 500), tcn_options={}, densetcn_options={},
+    cls = ShuffleNetLipreading if args["backbone_type"] == "shufflenet" else Lipreading
+    model = cls(modality="video", num_classes=args.get("num_classes", 500), tcn_options={}, densetcn_options={},
                        backbone_type=args["backbone_type"], relu_type=args["relu_type"], width_mult=args.get("width_mult", 1.0),
                        use_boundary=args.get("use_boundary", False), extract_feats=True)
     if not os.path.isfile(path):
@@ -244,7 +365,7 @@ class VideoSSModel(nn.Module):
     """profiler.py's VideoSSModel: lip reader + audio-visual separator in one call.  The batch holds either `video`
     (2B, 1, Tv, H, W) -- the first B rows speaker 1, the next B speaker 2; profiler.py's form at B = 1 -- or `s1_video` /
     `s2_video` (B, Tv, H, W) each.  The lip reader runs once on all 2B streams; the separator gets s1_embedding /
-    s2_embedding (B, 512, Tv).  Returns the separator's dict with the two embeddings added."""
+    s2_embedding (B, E, Tv), E the lip reader's width (512 ResNet-18, 1024 ShuffleNet).  Returns the separator's dict with the two embeddings added."""
 
     def __init__(self, ss: nn.Module, lipreader: nn.Module):
         super().__init__()
@@ -273,10 +394,10 @@ class VideoSSModel(nn.Module):
         return out
 
 
-def make_embeddings(lipreader: Lipreading, mouths_dir: str, embeds_dir: str, crop: Tuple[int, int] = (88, 88),
+def make_embeddings(lipreader: _LipreaderModule, mouths_dir: str, embeds_dir: str, crop: Tuple[int, int] = (88, 88),
                     mean: float = 0.421, std: float = 0.165, streams_per_call: int = 16, device=None) -> List[str]:
     """make_embeddings.py of the reference: every file of `mouths_dir` holds np.load(f)["data"] (T, Hin, Win) in [0, 255];
-    its embedding goes to `embeds_dir` under the same name as np.savez_compressed(path, embedding=(512, T) float32), what
+    its embedding goes to `embeds_dir` under the same name as np.savez_compressed(path, embedding=(backend_out, T) float32), what
     io.load_object and the reference's datasets read.  The test-time pipeline x / 255 -> CenterCrop(crop) -> (x - mean) / std
     is the window and affine of the forward.  Clips of the same shape share a forward (up to `streams_per_call`), and
     each forward's results come back in one device-to-host copy.  Returns the written paths."""

@@ -141,9 +141,11 @@ class _Node(nn.Module):
 class VoiceFilter(nn.Module):
     """The reference's VoiceFilter (src/model/voicefilter.py): same constructor arguments, same state_dict keys / shapes /
     order, so the separator's 82 entries of its checkpoints load with strict=True (an attached lip reader adds its own
-    entries under `lipreader.`, in front, as in the reference; the reference's ShuffleNet lip reader is not built).
+    entries under `lipreader.`, in front, as in the reference: with the reference's lrw_snv1x_tcn1x.json that is this
+    package's ShuffleNetLipreading, 1024 wide; of a reference checkpoint only its lipreader.tcn.* entries have no place).
     forward runs on libdptnav (include/vfilt.h) in eval mode; training (Dropout2d, BatchNorm statistics) is not built and
-    raises.  `embed_size` is the lip embedding's width: 1024 in the reference; this package's ResNet-18 lip reader gives 512.
+    raises.  `embed_size` is the lip embedding's width: 1024 in the reference (its ShuffleNet lip reader); this package's
+    ResNet-18 lip reader gives 512.
     `lipreader`: a module mapping (S, 1, T, H, W) to (S, T, embed_size); otherwise init_lipreader(lipreader_config,
     lipreader_path) of this package when a config is given; otherwise none, and only forward_embeddings works."""
 
@@ -272,7 +274,7 @@ class VoiceFilter(nn.Module):
         self._need_eval()
         if self.lipreader is None:
             raise RuntimeError(f"VoiceFilter was built without a lip reader (embed_size={self.embed_size}): pass lipreader= or "
-                               f"lipreader_config= (this package's ResNet-18 lip reader needs embed_size=512), or call "
+                               f"lipreader_config= (a ShuffleNet config gives 1024 values per frame, a ResNet-18 one needs embed_size=512), or call "
                                f"forward_embeddings(mix_magnitude, s1_embedding, s2_embedding) with precomputed embeddings")
         if s1_video.dim() != 4 or s1_video.shape != s2_video.shape:
             raise ValueError(f"s1_video / s2_video: expected two (B,Tv,H,W), got {tuple(s1_video.shape)} and {tuple(s2_video.shape)}")
