@@ -291,6 +291,12 @@ int dptnav_dropout_mask(dptnav_handle h, int block, int path, int B, int S, floa
  *                 0 = never.  Measured at B = 16 x 4 s: the same step time as the pair (29.75 vs 29.75 ms), 1.7-2 %
  *                 faster from B = 24, and 32.8 GB per step less HBM traffic (52.1 -> 19.3 GB: the pre-activation tensor was
  *                 80 % of a forward's).
+ *   "lstm_sched" (0/1, default 1): the step loop of lstm16x128_kernel (the "fuse_pre128" recurrence).  1 = every LDS read of a
+ *                 step (h fragments, x fragments, the LDS-resident W_ih sets) is issued by hand a k-chunk / a pair of sets
+ *                 ahead of the MFMAs that use it and covered by one counted s_waitcnt lgkmcnt(n); 0 = the loop before
+ *                 that, where the compiler had sunk 18 of 29 such reads to within two MFMAs of their wait.  The same
+ *                 MFMAs per accumulator in the same order: bit-identical to 0.  Kept for same-process A/B
+ *                 (tools/ab_option.py lstm_sched 0 1; B = 16 x 4 s: 27.91 -> 27.43 ms, profiles/lstm16x_lds_sched_ab.txt).
  *   "fcln" (0/1/2, default 1): a Linear layer with its LayerNorm and residual by fcln.hip -- 16-token tiles fetched by LDS-DMA,
  *                 two or three workgroups per CU -- instead of the GEMM engine's 32- / 64-token tiles, one workgroup per CU (0):
  *                 (a) DPRNN blocks with num_features = 64 and two directions, inference: Linear(256 -> 64) + LayerNorm +

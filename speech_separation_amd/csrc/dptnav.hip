@@ -94,6 +94,7 @@ struct dptnav_ctx {
   int opt_fuse_pre128 = 1;          // the same for num_features = 128 (lstm16x128_kernel: W_ih split between LDS and VGPRs): 0 never, 2 always,
                                     // 1 (default) from B = 12: a fused launch is 1.17 ms whatever its size -- below that the chip is not full
                                     // and the shorter K4 + recurrence chain wins (B = 8: 17.0 vs 18.0 ms; B = 16: equal; B = 24: 44.8 vs 44.0)
+  int opt_lstm_sched = 1;           // lstm16x128_kernel's step loop: 1 = LDS reads and waits issued by hand, 0 = the loop before that (A/B; bit-identical)
   bool fuse128_for(int B) const { return opt_fuse_pre128 == 2 || (opt_fuse_pre128 == 1 && B >= 12); }
   int opt_fcln = 1;                 // Linear + LayerNorm + residual on 16-token tiles, several workgroups per CU (fcln.hip) instead of the GEMM engine (0):
                                     // DPRNN fc (64 features, two directions, inference; 2 = two tiles ahead, two workgroups per CU) and the
@@ -922,7 +923,7 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
   if (usex) {
     ProfScope ps(c, CAT_LSTM, st);
     const int rc = lstm16x_launch(N, dptn, nst16, w.ndir, st, lstm_in, N, w.w_ih, w.b_ih, w.b_hh, w.w_hh, hc, w.ndir * LSTM_H,
-                                  M, geom);
+                                  M, geom, c->opt_lstm_sched);
     if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16x: %s", hipGetErrorString((hipError_t)rc));
   } else if (use16 && split) {
     ProfScope ps(c, CAT_LSTM, st);
@@ -2896,6 +2897,7 @@ int dptnav_set_option(dptnav_handle h, const char* key, int value) {
   else if (k == "fuse_pre") h->opt_fuse_pre = value != 0;
   else if (k == "fcln" && value >= 0 && value <= 2) h->opt_fcln = value;
   else if (k == "fuse_pre128" && value >= 0 && value <= 2) h->opt_fuse_pre128 = value;
+  else if (k == "lstm_sched" && value >= 0 && value <= 1) h->opt_lstm_sched = value;
   else if (k == "pack_whh") h->opt_pack_whh = value != 0;
   else if (k == "lstm16") h->opt_lstm16 = value != 0;
   else if (k == "lstm4") {

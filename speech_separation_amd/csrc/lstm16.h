@@ -60,6 +60,8 @@ int lstm4_pack_launch(void* stream, const float* const* src, int n, float* dst);
 // FUSED input projection (lstm16x.hip, num_features = 64): x_t W_ih^T + b is formed inside the recurrence (W_ih resident in
 // LDS), no pre-activation tensor in memory.  x: token-major [M][ldx]; wih / bih / bhh / whh: [direction] -> the nn.LSTM
 // tensors in their PyTorch layouts; hc addressed with 64-bit offsets (any launch size).  Inference only.
+// sched (num_features = 128 only): 1 = the step loop with its LDS reads and waits issued by hand, 0 = the loop before that
+// (the same arithmetic in the same order: bit-identical results; kept for same-process A/B).
 int lstm16x_launch(int nin, bool relu, int nst16, int ndir, void* stream, const float* x, int ldx, const float* const* wih,
                    const float* const* bih, const float* const* bhh, const float* const* whh, float* hc, int ldh,
-                   int64_t dump_row, const SeqGeom& g);
+                   int64_t dump_row, const SeqGeom& g, int sched = 1);

@@ -261,7 +261,24 @@ constexpr int X128_XS_FLOATS = 16 * 128;                       // one step's inp
 constexpr size_t X128_LDS_BYTES = sizeof(float) * (X128_WL_FLOATS + L16_HS_FLOATS + 2 * X128_XS_FLOATS);
 static_assert(X128_LDS_BYTES <= 160 * 1024, "LDS budget");
 
-template <bool RELU>
+// lstm_cell2 (common.h) with the one contraction its source leaves open written out: c_t = fma(f, c_{t-1}, i * g).  Under
+// -ffp-contract=fast `f * c + i * g` may become that or fma(i, g, f * c), which rounds differently; which one the compiler picks
+// depends on the code around it (this kernel's step loop came out with the first form for every slot, and with the second form
+// for accumulator rows 2, 3 once the same statement stood in a lambda).  Every step loop of lstm16x128_kernel computes the first.
+DEV LstmCell2 lstm_cell2_fc(f32x2 ai, f32x2 af, f32x2 ag, f32x2 ao, f32x2 c_prev) {
+  LstmCell2 r;
+  r.i = rcp_2(1.0f + exp2_2(ai));
+  r.f = rcp_2(1.0f + exp2_2(af));
+  r.g = 2.0f * rcp_2(1.0f + exp2_2(ag)) - 1.0f;
+  r.o = rcp_2(1.0f + exp2_2(ao));
+  const f32x2 ig = r.i * r.g;
+  r.c = (f32x2){__builtin_fmaf(r.f.x, c_prev.x, ig.x), __builtin_fmaf(r.f.y, c_prev.y, ig.y)};
+  const f32x2 th = 2.0f * rcp_2(1.0f + exp2_2(r.c * -2.8853900817779268f)) - 1.0f;
+  r.h = r.o * th;
+  return r;
+}
+
+template <bool RELU, int SCHED>
 __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ wih_f,
                                                           const float* __restrict__ wih_b, const float* __restrict__ bih_f,
                                                           const float* __restrict__ bih_b, const float* __restrict__ bhh_f,
@@ -454,54 +471,13 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
       if constexpr ((p0 & 7) == 6) xa = xa_next;      // last pair of the k-chunk
     });
   };
-  input_part(0);
-  __syncthreads();      // step 0 requests x_2 into the buffer of x_0
-
-  for (int step = 0; step < g.len; ++step) {
-    const float* hcur = Hs + (step & 1) * 16 * L16_LDH;
-    float* hnext = Hs + ((step + 1) & 1) * 16 * L16_LDH;
-    const float* arow = hcur + i16 * L16_LDH + 4 * ks;
-    // (the two h rows this lane stores: the second is read when the first has left -- one of them live at a time)
-    float4 hs = *reinterpret_cast<const float4*>(hcur + srow * L16_LDH + scol);
-    float4 a = *reinterpret_cast<const float4*>(arow);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) asm volatile("" : "+v"(acc[b]));
-    input_chunk0(x0.x, x0.y, 0);      // (this step's x_t, fragment read before the barrier)
-    __builtin_amdgcn_sched_barrier(0);  // (these 16 MFMAs FIRST: the h row store below was scheduled in front of them, with its wait)
-    const unsigned adv = step > 0 ? hstep : 0u;
-
-    // h_{t-1} W_hh^T, k-chunk by k-chunk, all eight blocks per chunk; one memory instruction per MFMA group in the first
-    // groups: the stores of h_{t-1}, the input rows of step + 2 to LDS, the requests for the rows of step + 3
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      float4 a_next = a;
-      if (m + 1 < 8) a_next = *reinterpret_cast<const float4*>(arow + 16 * (m + 1));
-      const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[b] = mfma16(av[tt], wf[b][4 * m + tt], acc[b]);
-        const int slot = 4 * m + tt;
-        if (slot < 2) {
-          asm volatile("" : "+v"(hs.x), "+v"(hs.y), "+v"(hs.z), "+v"(hs.w));
-          if (RELU) hs = make_float4(relu1(hs.x), relu1(hs.y), relu1(hs.z), relu1(hs.w));
-          *reinterpret_cast<float4*>(hcb + hp[slot]) = hs;
-          hp[slot] += adv;
-          if (slot == 0) hs = *reinterpret_cast<const float4*>(hcur + (srow + 2) * L16_LDH + scol);
-          __builtin_amdgcn_sched_barrier(0);
-        } else if (slot < 4) {
-          dma_x(step + 2, step & 1, slot - 2);    // x_{step+2} -> the buffer of x_step (last read before the previous barrier)
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      a = a_next;
-    }
-    // cell update of both unit halves (lane-local), h_t -> the other LDS buffer
+  // cell update of both unit halves (lane-local), h_t -> the other LDS buffer
+  auto cell_update = [&](float* hnext) {
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
 #pragma unroll
       for (int r = 0; r < 4; r += 2) {
-        const LstmCell2 u = lstm_cell2((f32x2){acc[hf][r], acc[hf][r + 1]}, (f32x2){acc[2 + hf][r], acc[2 + hf][r + 1]},
+        const LstmCell2 u = lstm_cell2_fc((f32x2){acc[hf][r], acc[hf][r + 1]}, (f32x2){acc[2 + hf][r], acc[2 + hf][r + 1]},
                                        (f32x2){acc[4 + hf][r], acc[4 + hf][r + 1]}, (f32x2){acc[6 + hf][r], acc[6 + hf][r + 1]},
                                        (f32x2){cst[hf][r], cst[hf][r + 1]});
         cst[hf][r] = u.c.x;
@@ -510,9 +486,227 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
         hnext[(4 * ks + r + 1) * L16_LDH + 32 * w + 16 * hf + i16] = u.h.y;
       }
     }
-    if (step + 1 < g.len) input_part((step + 1) & 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of x_{step+2} have landed (read behind the NEXT barrier)
-    __syncthreads();
+  };
+  // SCHED 0: the step loop as it was before the LDS schedule was written by hand (kept for same-process A/B, option "lstm_sched")
+  if constexpr (SCHED == 0) {
+    input_part(0);
+    __syncthreads();      // step 0 requests x_2 into the buffer of x_0
+
+    for (int step = 0; step < g.len; ++step) {
+      const float* hcur = Hs + (step & 1) * 16 * L16_LDH;
+      float* hnext = Hs + ((step + 1) & 1) * 16 * L16_LDH;
+      const float* arow = hcur + i16 * L16_LDH + 4 * ks;
+      // (the two h rows this lane stores: the second is read when the first has left -- one of them live at a time)
+      float4 hs = *reinterpret_cast<const float4*>(hcur + srow * L16_LDH + scol);
+      float4 a = *reinterpret_cast<const float4*>(arow);
+#pragma unroll
+      for (int b = 0; b < 8; ++b) asm volatile("" : "+v"(acc[b]));
+      input_chunk0(x0.x, x0.y, 0);      // (this step's x_t, fragment read before the barrier)
+      __builtin_amdgcn_sched_barrier(0);  // (these 16 MFMAs FIRST: the h row store below was scheduled in front of them, with its wait)
+      const unsigned adv = step > 0 ? hstep : 0u;
+
+      // h_{t-1} W_hh^T, k-chunk by k-chunk, all eight blocks per chunk; one memory instruction per MFMA group in the first
+      // groups: the stores of h_{t-1}, the input rows of step + 2 to LDS, the requests for the rows of step + 3
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        float4 a_next = a;
+        if (m + 1 < 8) a_next = *reinterpret_cast<const float4*>(arow + 16 * (m + 1));
+        const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+          for (int b = 0; b < 8; ++b) acc[b] = mfma16(av[tt], wf[b][4 * m + tt], acc[b]);
+          const int slot = 4 * m + tt;
+          if (slot < 2) {
+            asm volatile("" : "+v"(hs.x), "+v"(hs.y), "+v"(hs.z), "+v"(hs.w));
+            if (RELU) hs = make_float4(relu1(hs.x), relu1(hs.y), relu1(hs.z), relu1(hs.w));
+            *reinterpret_cast<float4*>(hcb + hp[slot]) = hs;
+            hp[slot] += adv;
+            if (slot == 0) hs = *reinterpret_cast<const float4*>(hcur + (srow + 2) * L16_LDH + scol);
+            __builtin_amdgcn_sched_barrier(0);
+          } else if (slot < 4) {
+            dma_x(step + 2, step & 1, slot - 2);    // x_{step+2} -> the buffer of x_step (last read before the previous barrier)
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        a = a_next;
+      }
+      cell_update(hnext);
+      if (step + 1 < g.len) input_part((step + 1) & 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of x_{step+2} have landed (read behind the NEXT barrier)
+      __syncthreads();
+    }
+  } else {
+    // ================================================================================================================
+    // SCHED 1: the step's LDS schedule, written down.  Every LDS read of the loop is issued by hand (vmem_asm.h:
+    // lds_read4_uncounted) and covered by ONE hand-counted wait that names its registers (wait_lds<KEEP>); every request +
+    // wait group stands between two sched_barrier(0), and so do the h row stores and the LDS-DMA requests.  The only
+    // compiler-counted LDS instructions left are the cell update's stores of h_t: they are OLDER than every read issued
+    // behind them, so no KEEP below has them among the instructions it leaves in flight, and the compiler's own
+    // lgkmcnt(0) in front of the barrier (the fence of __syncthreads) finds them long done.
+    //
+    // Issue order of one step and what each wait leaves outstanding (MFMA = number of the step's 512 MFMAs issued in
+    // front of the group; the LDS answers in order, so KEEP = the number of requests issued behind the wanted one):
+    //
+    //   MFMA  group                          requests issued               wait: registers          KEEP (left in flight)   lead
+    //      0  behind the barrier             hs0, hs1, a0                  -
+    //   0-15  input chunk 0, k = 0, 1 (x0: registers)
+    //     16  recurrent chunk 0              a1                            hs0, hs1, a0             1 (a1)                  16
+    //  24,32  (h row stores: registers have landed)  40, 48: the two LDS-DMA requests for x_{step+2} (vmcnt, not lgkmcnt)
+    //  16+32m recurrent chunk m = 1..6       a(m+1)                        a(m)                     1 (a(m+1))              32
+    //    240  recurrent chunk 7              x0', x1' (rows of step + 1)   a7                       2 (x0', x1')            32
+    //    272  behind the last recurrent MFMA -                             x0', x1'                 0 (nothing younger)     32
+    //         cell update (VALU; its stores of h_t are compiler-counted, older than everything below)
+    // 272-287 input chunk 0 of step + 1, k = 2, 3 (x0')
+    //    288  input chunk 1 (x1')            x2                            -
+    //    320  input chunk 2                  x3                            x2                       1 (x3)                  32
+    //    352  input chunk 3                  x4, w33                       x3                       2 (x4, w33)             32
+    //    384  pair 0 (set 32 resident, 33)   x5, pair 1                    x4, w33                  3 (x5, pair 1)          32
+    //  384+8c pair c, not first of a chunk   pair c+1                      pair c                   2 (pair c+1)             8
+    //    416  pair 4 (first of chunk 5)      x6, pair 5                    x5, pair 4               3 (x6, pair 5)           8 (x5: 32)
+    //    448  pair 8 (first of chunk 6)      x7, pair 9                    x6, pair 8               3 (x7, pair 9)           8 (x6: 32)
+    //    480  pair 12 (first of chunk 7)     pair 13                       x7, pair 12              2 (pair 13)              8 (x7: 32)
+    //    504  pair 15                        -                             pair 15                  0 (nothing younger)      8
+    //    512  vmcnt(0) for the rows of x_{step+2}, barrier.  Nothing hand-issued is outstanding here.
+    //
+    // The LAST step (written out behind the loop, see one_step) has no input part behind it: it requests no x0' / x1', its wait
+    // at 240 is KEEP 0 and it has no group at 272.
+    //
+    // Leads are the source's own: one k-chunk (32 MFMAs) for h and x fragments, one pair (8 MFMAs) for the W_ih sets, the
+    // held-back half of chunk 0 (16 MFMAs) for the first h fragment.  Differences from SCHED 0 that are not order alone:
+    // BOTH h rows a lane stores are read at the top of the step (SCHED 0 read the second behind the first store, 8 MFMAs
+    // in front of its wait; the 16 registers of the W_ih pairs are free in this part of the step), x0' / x1' are read
+    // under recurrent chunk 7 (their buffer was published by the barrier that opened the step) and w33, the first LDS
+    // set, a k-chunk ahead.  No register forces a shorter lead anywhere.  Judge the GENERATED loop, not this table:
+    // tools/lds_wait_scan.py, tests/test_lds_wait_schedule.py.
+    const uint32_t hs_lds = lds_addr(Hs);
+    const uint32_t a_off = (uint32_t)((i16 * L16_LDH + 4 * ks) * 4);      // the lane's A fragment of chunk m: + 64 m
+    const uint32_t hrow_off = (uint32_t)((srow * L16_LDH + scol) * 4);    // the two h rows the lane stores: + 0, + 2 rows
+    const uint32_t xf_off = (uint32_t)(xlane * 4);
+    auto request_x = [&](auto M, int buf, f32x4v& dst) {                  // the lane's x fragment of k-chunk M
+      constexpr int m = decltype(M)::value;
+      lds_read4_uncounted<256 * (m >> 2)>(dst, xs_lds + (uint32_t)(buf * (X128_XS_FLOATS * 4)) + xf_off + ((uint32_t)((m & 3) ^ xq) << 6));
+    };
+    auto request_w = [&](auto CH, f32x4v (&dst)[2]) {                     // the LDS sets of pair CH
+      constexpr int p0 = 32 + 2 * decltype(CH)::value;
+      if constexpr (p0 >= RES) lds_read4_uncounted<(p0 >= RES ? p0 - RES : 0) * 1024>(dst[0], wl_lds);
+      lds_read4_uncounted<(p0 + 1 - RES) * 1024>(dst[1], wl_lds);
+    };
+    // acc = b + x W_ih^T without the held-back half of chunk 0; xc0 / xc1 (k-chunks 0 and 1) have landed
+    auto input_part1 = [&](int buf, const f32x4v& xc0, const f32x4v& xc1) {
+#pragma unroll
+      for (int b = 0; b < 8; ++b) acc[b] = (f32x4v){bsc[b], bsc[b], bsc[b], bsc[b]};
+      x0 = (f32x2){xc0.x, xc0.y};
+      input_chunk0(xc0.z, xc0.w, 2);
+      f32x4v xf[8];                             // k-chunks 2..7
+      f32x4v fa[2][2];
+      static_for<3>([&](auto MM) {              // k-chunks 1..3: sets 8..31, all resident
+        constexpr int m = decltype(MM)::value + 1;
+        __builtin_amdgcn_sched_barrier(0);
+        request_x(std::integral_constant<int, m + 1>{}, buf, xf[m + 1]);
+        if constexpr (m == 3) request_w(std::integral_constant<int, 0>{}, fa[0]);
+        if constexpr (m == 2) wait_lds<1>(xf[2]);
+        if constexpr (m == 3) wait_lds<2>(xf[3]);
+        __builtin_amdgcn_sched_barrier(0);
+        const f32x4v xv = m == 1 ? xc1 : xf[m];
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+          for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int p = 8 * m + 4 * half + j;
+              acc[p & 7] = mfma16(xv[tt], wiv[p][tt], acc[p & 7]);
+            }
+      });
+      static_for<16>([&](auto CH) {             // k-chunks 4..7: sets 32..63 in pairs (p0, p0 + 1)
+        constexpr int ch = decltype(CH)::value, p0 = 32 + 2 * ch, m = p0 >> 3;
+        constexpr bool first = (p0 & 7) == 0, more_x = first && m + 1 < 8, more_w = ch + 1 < 16;
+        constexpr int keep = (more_x ? 1 : 0) + (more_w ? 2 : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (more_x) request_x(std::integral_constant<int, more_x ? m + 1 : 0>{}, buf, xf[more_x ? m + 1 : 0]);
+        if constexpr (more_w) request_w(std::integral_constant<int, more_w ? ch + 1 : 1>{}, fa[(ch + 1) & 1]);
+        if constexpr (ch == 0) wait_lds<keep>(xf[m], fa[0][1]);
+        else if constexpr (first) wait_lds<keep>(xf[m], fa[ch & 1][0], fa[ch & 1][1]);
+        else wait_lds<keep>(fa[ch & 1][0], fa[ch & 1][1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+          if constexpr (p0 < RES) acc[p0 & 7] = mfma16(xf[m][tt], wiv[p0 < RES ? p0 : 0][tt], acc[p0 & 7]);
+          else acc[p0 & 7] = mfma16(xf[m][tt], fa[ch & 1][0][tt], acc[p0 & 7]);
+          acc[(p0 + 1) & 7] = mfma16(xf[m][tt], fa[ch & 1][1][tt], acc[(p0 + 1) & 7]);
+        }
+      });
+    };
+    f32x4v xc0, xc1;
+    request_x(std::integral_constant<int, 0>{}, 0, xc0);
+    request_x(std::integral_constant<int, 1>{}, 0, xc1);
+    wait_lds<0>(xc0, xc1);
+    input_part1(0, xc0, xc1);
+    __syncthreads();      // step 0 requests x_2 into the buffer of x_0
+
+    // The last step has no input part behind it and is written out on its own behind the loop (LAST): with the input part
+    // under `if (step + 1 < g.len)` inside the loop, the x fragments requested under recurrent chunk 7 were live into a
+    // conditional block, and the register allocator answered with W_hh fragments in scratch, 87 v_accvgpr_read and 110
+    // v_mov in the loop.
+    auto one_step = [&](int step, auto LAST) {
+      constexpr bool last = decltype(LAST)::value;
+      const uint32_t hcur = hs_lds + (uint32_t)((step & 1) * (16 * L16_LDH * 4));
+      float* hnext = Hs + ((step + 1) & 1) * 16 * L16_LDH;
+      f32x4v hsv[2], af[8];
+      lds_read4_uncounted<0>(hsv[0], hcur + hrow_off);
+      lds_read4_uncounted<2 * L16_LDH * 4>(hsv[1], hcur + hrow_off);
+      lds_read4_uncounted<0>(af[0], hcur + a_off);
+#pragma unroll
+      for (int b = 0; b < 8; ++b) asm volatile("" : "+v"(acc[b]));
+      input_chunk0(x0.x, x0.y, 0);      // (this step's x_t, fragment read before the barrier)
+      const unsigned adv = step > 0 ? hstep : 0u;
+
+      // h_{t-1} W_hh^T, k-chunk by k-chunk, all eight blocks per chunk; one memory instruction per MFMA group in the first
+      // groups: the stores of h_{t-1}, then the requests for the input rows of step + 2
+      static_for<8>([&](auto MM) {
+        constexpr int m = decltype(MM)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (m + 1 < 8) lds_read4_uncounted<64 * (m + 1 < 8 ? m + 1 : 0)>(af[m + 1 < 8 ? m + 1 : 0], hcur + a_off);
+        if constexpr (m == 7 && !last) {
+          request_x(std::integral_constant<int, 0>{}, (step + 1) & 1, xc0);
+          request_x(std::integral_constant<int, 1>{}, (step + 1) & 1, xc1);
+        }
+        if constexpr (m == 0) wait_lds<1>(hsv[0], hsv[1], af[0]);
+        else wait_lds<(m == 7 ? (last ? 0 : 2) : 1)>(af[m]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+#pragma unroll
+          for (int b = 0; b < 8; ++b) acc[b] = mfma16(af[m][tt], wf[b][4 * m + tt], acc[b]);
+          const int slot = 4 * m + tt;
+          if (slot < 2) {
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4v v = hsv[slot];
+            if (RELU) v = (f32x4v){relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)};
+            *reinterpret_cast<f32x4v*>(hcb + hp[slot]) = v;
+            hp[slot] += adv;
+            __builtin_amdgcn_sched_barrier(0);
+          } else if (slot < 4) {
+            __builtin_amdgcn_sched_barrier(0);
+            dma_x(step + 2, step & 1, slot - 2);    // x_{step+2} -> the buffer of x_step (last read before the previous barrier)
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      });
+      if constexpr (!last) {
+        __builtin_amdgcn_sched_barrier(0);
+        wait_lds<0>(xc0, xc1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      cell_update(hnext);
+      if constexpr (!last) input_part1((step + 1) & 1, xc0, xc1);
+      __builtin_amdgcn_sched_barrier(0);                 // (the last pair's MFMAs in front of the barrier, not behind it)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows of x_{step+2} have landed (read behind the NEXT barrier)
+      __syncthreads();
+    };
+    for (int step = 0; step + 1 < g.len; ++step) one_step(step, std::false_type{});
+    one_step(g.len - 1, std::true_type{});
   }
   {
     const float* hfin = Hs + (g.len & 1) * 16 * L16_LDH;
@@ -529,14 +723,15 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
 
 int lstm16x_launch(int nin, bool relu, int nst16, int ndir, void* stream, const float* x, int ldx, const float* const* wih,
                    const float* const* bih, const float* const* bhh, const float* const* whh, float* hc, int ldh,
-                   int64_t dump_row, const SeqGeom& g) {
+                   int64_t dump_row, const SeqGeom& g, int sched) {
   if ((nin != 64 && nin != 128) || nst16 < 1 || ndir < 1 || ndir > 2 || g.len < 1) return (int)hipErrorInvalidValue;
   auto kern = nin == 64 ? (relu ? lstm16x_kernel<64, true> : lstm16x_kernel<64, false>)
-                        : (relu ? lstm16x128_kernel<true> : lstm16x128_kernel<false>);
+                        : sched == 0 ? (relu ? lstm16x128_kernel<true, 0> : lstm16x128_kernel<false, 0>)
+                                     : (relu ? lstm16x128_kernel<true, 1> : lstm16x128_kernel<false, 1>);
   const size_t lds = nin == 64 ? X16<64>::LDS_BYTES : X128_LDS_BYTES;
-  static PerDeviceOnce ready[4];
+  static PerDeviceOnce ready[6];
   const int dev = current_hip_device();
-  const int ki = (nin == 128 ? 2 : 0) + (relu ? 1 : 0);
+  const int ki = (nin == 128 ? (sched == 0 ? 4 : 2) : 0) + (relu ? 1 : 0);
   if (!ready[ki].done(dev)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;

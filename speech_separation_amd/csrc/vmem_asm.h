@@ -96,6 +96,35 @@ DEV void retire_vm1(int r) {
   asm volatile("s_waitcnt vmcnt(%[n])" ::"v"(r), [n] "n"(KEEP) : "memory");
 }
 
+// ---- LDS reads the compiler does not count (lstm16x.hip) ---------------------------------------------------------------------
+// The same bargain on the other counter.  A plain C++ LDS load under register pressure is sunk to the MFMA that consumes it and
+// waited for there with lgkmcnt(0): the wave sits out the LDS round trip AND whatever younger read it had in flight.  A volatile
+// asm read stays where it is written, and the wait that covers it is written by hand as well: the LDS answers a wave's requests
+// in order, so `s_waitcnt lgkmcnt(KEEP)` with KEEP = the number of LDS instructions issued behind the wanted one lets exactly
+// those stay in flight.  The registers waited for are in-out operands of the wait (no use of them moves in front of it, none is
+// copied or given away before it); KEEP comes from the issue-order table in the kernel.  Two rules beyond vmcnt's:
+//   * arithmetic (MFMAs included) is scheduled ACROSS asm statements, so a wait + request group stands between two
+//     __builtin_amdgcn_sched_barrier(0), one on EACH side: with a fence behind the group only, the MFMAs in front of it slid
+//     down behind it and the wait came 1-2 MFMAs after its request;
+//   * compiler-counted LDS instructions may share the loop only where no hand-counted wait has them among the instructions it
+//     leaves in flight (the compiler pairs ds_write_b32 into ds_write2_b32 as it likes: their number is not the source's).
+template <int OFF>
+DEV void lds_read4_uncounted(f32x4v& dst, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+template <int KEEP>
+DEV void wait_lds(f32x4v& r0) {
+  asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(r0) : [n] "n"(KEEP) : "memory");
+}
+template <int KEEP>
+DEV void wait_lds(f32x4v& r0, f32x4v& r1) {
+  asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(r0), "+v"(r1) : [n] "n"(KEEP) : "memory");
+}
+template <int KEEP>
+DEV void wait_lds(f32x4v& r0, f32x4v& r1, f32x4v& r2) {
+  asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(r0), "+v"(r1), "+v"(r2) : [n] "n"(KEEP) : "memory");
+}
+
 // ---- tile tickets of the persistent kernels built on the operations above (dgrad_t.hip, dgrad_r.hip, gemm_t.hip) -----------------
 // A workgroup takes 32-token tiles until none is left; the rows of tile i + 1 are requested while tile i multiplies, so the ticket
 // of tile i + 2 must be on its way by then.  Thread 0 asks for it with an UNCOUNTED returning atomic right behind the barrier of
