@@ -297,6 +297,15 @@ int dptnav_dropout_mask(dptnav_handle h, int block, int path, int B, int S, floa
  *                 that, where the compiler had sunk 18 of 29 such reads to within two MFMAs of their wait.  The same
  *                 MFMAs per accumulator in the same order: bit-identical to 0.  Kept for same-process A/B
  *                 (tools/ab_option.py lstm_sched 0 1; B = 16 x 4 s: 27.91 -> 27.43 ms, profiles/lstm16x_lds_sched_ab.txt).
+ *   "lstm_prologue" (0/1, default 1): the prologue of the fused recurrences (lstm16x.hip, "fuse_pre" / "fuse_pre128").  1 = at the
+ *                 first such launch of a pass one small kernel copies every path's W_ih, W_hh and summed bias, as they are at
+ *                 that moment and already multiplied by their gate's exp2 scale, into the workspace in the order the kernel
+ *                 keeps them ([path][direction][wave][set][lane][4]); each workgroup then fetches its weights in one burst of
+ *                 hand-issued 1-KiB requests (W_ih to LDS by LDS-DMA and into its VGPRs, W_hh straight into its AGPRs, the
+ *                 last 64 requests in flight under step 0's input part) behind two waits.  0 = every lane reads its rows of
+ *                 the nn.LSTM tensors and scales them; the compiler serialised those loads into 80 (num_features = 64: 44)
+ *                 dependent round trips per workgroup.  The same values in the same registers: bit-identical to 0.  Kept
+ *                 for same-process A/B (tools/ab_option.py lstm_prologue 0 1; profiles/lstm16x_prologue_ab.txt).
  *   "fcln" (0/1/2, default 1): a Linear layer with its LayerNorm and residual by fcln.hip -- 16-token tiles fetched by LDS-DMA,
  *                 two or three workgroups per CU -- instead of the GEMM engine's 32- / 64-token tiles, one workgroup per CU (0):
  *                 (a) DPRNN blocks with num_features = 64 and two directions, inference: Linear(256 -> 64) + LayerNorm +

@@ -44,7 +44,7 @@ constexpr int QUEUE_SLOTS = 1024;
 
 struct Plan {  // workspace offsets in floats
   int64_t L, S, M;
-  size_t queue, vid, E, X0, X1, qkv, att, y1, pre, hc, stamps, wfold, wpack, wih, whh4, winp, wmask, total;
+  size_t queue, vid, E, X0, X1, qkv, att, y1, pre, hc, stamps, wfold, wpack, wih, whh4, x16pack, winp, wmask, total;
   size_t qkv_n, att_n, y1_n, hc_n;
 };
 
@@ -58,6 +58,7 @@ struct Run {
   hipEvent_t lstm_record = nullptr;  // if set: recorded right after the recurrence launch
   int half = 0;                      // which half of a split batch this run is (salts the dropout seed)
   bool packed_whh4 = false;          // ws + pl.whh4 holds the fragment-order W_hh copies of ALL paths for lstm4.hip (made at its first launch of the pass)
+  bool packed_x16 = false;           // ws + pl.x16pack holds the fragment-order, pre-scaled W_ih / W_hh / bias copies of ALL paths for lstm16x.hip (made at its first launch of the pass)
   bool packed_inw = false;           // ws + pl.winp holds the fragment-order in-projection weights of ALL paths (dptnav_train_forward); otherwise slot 0 = this path
   bool packed_wih = false;           // ws + pl.wih holds the fragment-order W_ih copies of ALL paths; otherwise run_path packs its own
   bool fuse128 = false;              // num_features = 128: input projection inside the recurrence for this pass (dptnav_ctx::fuse128_for)
@@ -95,6 +96,7 @@ struct dptnav_ctx {
                                     // 1 (default) from B = 12: a fused launch is 1.17 ms whatever its size -- below that the chip is not full
                                     // and the shorter K4 + recurrence chain wins (B = 8: 17.0 vs 18.0 ms; B = 16: equal; B = 24: 44.8 vs 44.0)
   int opt_lstm_sched = 1;           // lstm16x128_kernel's step loop: 1 = LDS reads and waits issued by hand, 0 = the loop before that (A/B; bit-identical)
+  int opt_lstm_prologue = 1;        // lstm16x.hip's prologue: 1 = one burst of 1-KiB requests from a packed copy made once per pass, 0 = row-per-lane loads of the nn.LSTM tensors (A/B; bit-identical)
   bool fuse128_for(int B) const { return opt_fuse_pre128 == 2 || (opt_fuse_pre128 == 1 && B >= 12); }
   int opt_fcln = 1;                 // Linear + LayerNorm + residual on 16-token tiles, several workgroups per CU (fcln.hip) instead of the GEMM engine (0):
                                     // DPRNN fc (64 features, two directions, inference; 2 = two tiles ahead, two workgroups per CU) and the
@@ -410,6 +412,8 @@ int make_plan(dptnav_ctx* c, int B, int64_t T, int Tv, Plan* p) {
   p->wih = take((size_t)2 * g.num_blocks * 2 * 4 * H * N);
   // ... and of W_hh in the order of the low-latency recurrence (lstm4.hip, `packed`)
   p->whh4 = take((size_t)2 * g.num_blocks * 2 * 4 * H * H);
+  // ... and of W_ih, W_hh and the summed bias, pre-scaled, in the order of the fused recurrence's prologue (lstm16x.hip, `pack`)
+  p->x16pack = take((N == 64 || N == 128) && H == LSTM_H ? (size_t)2 * g.num_blocks * 2 * lstm16x_pack_floats((int)N) : 0);
   // ... and of the attention in-projection weights of every path, for gemm_t.hip (training forward)
   p->winp = take(g.arch == 0 && N == 128 ? (size_t)2 * g.num_blocks * 3 * N * N : 0);
   // masked tail: [W_out; W_gate] and the two biases packed from the current weights on every call (mask_tail.h)
@@ -921,9 +925,33 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
   if (run.lstm_wait && hipStreamWaitEvent(st, run.lstm_wait, 0) != hipSuccess)
     return c->fail(DPTNAV_ERR_HIP, "lstm stagger wait");
   if (usex) {
+    const float* xpack = nullptr;
+    if (c->opt_lstm_prologue) {
+      float* base = ws + pl.x16pack;
+      if (!run.packed_x16) {   // first fused recurrence of this pass: copy every path's weights as they are now, LSTM16X_PACK_MAX matrix sets per launch
+        const int nmat = 2 * (int)c->pw.size();
+        for (int first = 0; first < nmat; first += LSTM16X_PACK_MAX) {
+          const float *s_ih[LSTM16X_PACK_MAX], *s_hh[LSTM16X_PACK_MAX], *s_bi[LSTM16X_PACK_MAX], *s_bh[LSTM16X_PACK_MAX];
+          const int n = std::min(LSTM16X_PACK_MAX, nmat - first);
+          for (int i = 0; i < n; ++i) {
+            const PathWeights& q = c->pw[(size_t)(first + i) / 2];
+            const int dir = (first + i) & 1;
+            const bool have = dir == 0 || q.ndir == 2;
+            s_ih[i] = have ? q.w_ih[dir] : nullptr;
+            s_hh[i] = have ? q.w_hh[dir] : nullptr;
+            s_bi[i] = have ? q.b_ih[dir] : nullptr;
+            s_bh[i] = have ? q.b_hh[dir] : nullptr;
+          }
+          const int rcp = lstm16x_pack_launch(N, st, s_ih, s_hh, s_bi, s_bh, n, base + (size_t)first * lstm16x_pack_floats(N));
+          if (rcp != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16x weight pack: %s", hipGetErrorString((hipError_t)rcp));
+        }
+        run.packed_x16 = true;
+      }
+      xpack = base + (size_t)(2 * (2 * block + path)) * lstm16x_pack_floats(N);
+    }
     ProfScope ps(c, CAT_LSTM, st);
     const int rc = lstm16x_launch(N, dptn, nst16, w.ndir, st, lstm_in, N, w.w_ih, w.b_ih, w.b_hh, w.w_hh, hc, w.ndir * LSTM_H,
-                                  M, geom, c->opt_lstm_sched);
+                                  M, geom, c->opt_lstm_sched, xpack);
     if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16x: %s", hipGetErrorString((hipError_t)rc));
   } else if (use16 && split) {
     ProfScope ps(c, CAT_LSTM, st);
@@ -2091,6 +2119,7 @@ int begin_run(dptnav_ctx* c, Run* run, float* ws, const Plan& pl, hipStream_t st
   run->packed = false;
   run->packed_wih = false;
   run->packed_whh4 = false;
+  run->packed_x16 = false;
   hipError_t e = hipMemsetAsync(ws + pl.queue, 0, QUEUE_SLOTS * sizeof(unsigned), st);
   if (e != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "ticket counter reset: %s", hipGetErrorString(e));
   return DPTNAV_OK;
@@ -2898,6 +2927,7 @@ int dptnav_set_option(dptnav_handle h, const char* key, int value) {
   else if (k == "fcln" && value >= 0 && value <= 2) h->opt_fcln = value;
   else if (k == "fuse_pre128" && value >= 0 && value <= 2) h->opt_fuse_pre128 = value;
   else if (k == "lstm_sched" && value >= 0 && value <= 1) h->opt_lstm_sched = value;
+  else if (k == "lstm_prologue" && value >= 0 && value <= 1) h->opt_lstm_prologue = value;
   else if (k == "pack_whh") h->opt_pack_whh = value != 0;
   else if (k == "lstm16") h->opt_lstm16 = value != 0;
   else if (k == "lstm4") {

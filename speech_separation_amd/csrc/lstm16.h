@@ -62,6 +62,15 @@ int lstm4_pack_launch(void* stream, const float* const* src, int n, float* dst);
 // tensors in their PyTorch layouts; hc addressed with 64-bit offsets (any launch size).  Inference only.
 // sched (num_features = 128 only): 1 = the step loop with its LDS reads and waits issued by hand, 0 = the loop before that
 // (the same arithmetic in the same order: bit-identical results; kept for same-process A/B).
+// pack: the directions' weights in fragment order, pre-scaled ([direction][lstm16x_pack_floats(nin)], written by
+// lstm16x_pack_launch) -- the prologue fetches them in one burst of 1-KiB requests (W_ih to LDS by LDS-DMA, W_hh straight into
+// AGPRs); nullptr = the prologue before that, every lane reading its rows of the nn.LSTM tensors (bit-identical; same-process A/B).
 int lstm16x_launch(int nin, bool relu, int nst16, int ndir, void* stream, const float* x, int ldx, const float* const* wih,
                    const float* const* bih, const float* const* bhh, const float* const* whh, float* hc, int ldh,
-                   int64_t dump_row, const SeqGeom& g, int sched = 1);
+                   int64_t dump_row, const SeqGeom& g, int sched = 1, const float* pack = nullptr);
+// The packed copy of n <= LSTM16X_PACK_MAX matrix sets (one per path and direction; wih[i] == nullptr: slot left untouched)
+// -> dst[n][lstm16x_pack_floats(nin)], from the tensors as they are when the launch runs.
+constexpr int LSTM16X_PACK_MAX = 24;
+constexpr size_t lstm16x_pack_floats(int nin) { return (size_t)4 * (8 * (nin / 16) + 66) * 256; }
+int lstm16x_pack_launch(int nin, void* stream, const float* const* wih, const float* const* whh, const float* const* bih,
+                        const float* const* bhh, int n, float* dst);

@@ -34,13 +34,29 @@ struct X16 {
   static_assert(LDS_BYTES <= 160 * 1024, "W_ih must fit the LDS beside the h and x tiles");
 };
 
-template <int NIN, bool RELU>
-__global__ __launch_bounds__(256) void lstm16x_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ wih_f,
-                                                       const float* __restrict__ wih_b, const float* __restrict__ bih_f,
-                                                       const float* __restrict__ bih_b, const float* __restrict__ bhh_f,
-                                                       const float* __restrict__ bhh_b, const float* __restrict__ whh_f,
-                                                       const float* __restrict__ whh_b, float* __restrict__ hc, int ldh,
-                                                       int64_t dump_row, SeqGeom g) {
+// Fragment-order copy of one direction's weights, written by lstm16x_pack_kernel from the weights as they are at that moment and
+// read by the PRO = 1 prologues: per wave `SETS` sets of 1 KiB ([lane 64][4 floats], one wave instruction each), every value
+// already multiplied by l16_gate_scale of its gate (the multiply the PRO = 0 prologue does itself: the same bits).
+//   sets [0, HH0):      W_ih set p = 8 m + b:  W_ih[row(b)][16 m + 4 ks .. + 3]      row(b) = (b >> 1) 128 + 32 wave + 16 (b & 1) + i16
+//   sets [HH0, BIAS0):  W_hh set q = 8 b + m:  W_hh[row(b)][16 m + 4 ks .. + 3]
+//   sets BIAS0 + j:     (b_ih + b_hh)[row(4 j + k)], k = 0..3
+template <int NIN>
+struct XPack {
+  static constexpr int HH0 = 8 * (NIN / 16), BIAS0 = HH0 + 64, SETS = BIAS0 + 2;
+  static constexpr size_t DIR_FLOATS = (size_t)4 * SETS * 256;
+  static_assert(DIR_FLOATS == lstm16x_pack_floats(NIN), "lstm16.h");
+};
+
+// PRO: the prologue.  0 = every lane reads its rows of the nn.LSTM tensors with ordinary loads and scales them (the compiler
+// serialises them: 44 blocking load groups, 80 in the 128-feature kernel); 1 = one burst of hand-issued 1-KiB requests from the
+// packed copy, W_ih to LDS by LDS-DMA, W_hh straight into its AGPRs, one wait.  Same values in the same registers either way.
+template <int NIN, bool RELU, int PRO>
+DEV void lstm16x_body(const float* __restrict__ x, int ldx, const float* __restrict__ wih_f,
+                      const float* __restrict__ wih_b, const float* __restrict__ bih_f,
+                      const float* __restrict__ bih_b, const float* __restrict__ bhh_f,
+                      const float* __restrict__ bhh_b, const float* __restrict__ whh_f,
+                      const float* __restrict__ whh_b, const float* __restrict__ pk, float* __restrict__ hc, int ldh,
+                      int64_t dump_row, SeqGeom g) {
   using Sh = X16<NIN>;
   constexpr int MK = Sh::MK, LDX = Sh::LDX, NXL = Sh::NXL;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -60,32 +76,53 @@ __global__ __launch_bounds__(256) void lstm16x_kernel(const float* __restrict__ 
   float wf[8][32];
   float bsc[8];                                   // (b_ih + b_hh) of the lane's column in block b, pre-scaled
   float* wl_wave = Wl + w * (MK * 8 * 256) + lane * 4;
+  f32x4 wq[64], bq[2];                            // PRO = 1: W_hh set q = 8 b + m, the bias of blocks 0..3 / 4..7, in flight
+  if constexpr (PRO == 0) {
 #pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
-    const float gs = l16_gate_scale(b >> 1);
-    const float* wrow = whh + (int64_t)row * L16_H + 4 * ks;
+    for (int b = 0; b < 8; ++b) {
+      const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
+      const float gs = l16_gate_scale(b >> 1);
+      const float* wrow = whh + (int64_t)row * L16_H + 4 * ks;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const float4 v = *reinterpret_cast<const float4*>(wrow + 16 * m);
-      wf[b][4 * m + 0] = v.x * gs;
-      wf[b][4 * m + 1] = v.y * gs;
-      wf[b][4 * m + 2] = v.z * gs;
-      wf[b][4 * m + 3] = v.w * gs;
+      for (int m = 0; m < 8; ++m) {
+        const float4 v = *reinterpret_cast<const float4*>(wrow + 16 * m);
+        wf[b][4 * m + 0] = v.x * gs;
+        wf[b][4 * m + 1] = v.y * gs;
+        wf[b][4 * m + 2] = v.z * gs;
+        wf[b][4 * m + 3] = v.w * gs;
+      }
+      bsc[b] = (bih[row] + bhh[row]) * gs;
+      // ---- W_ih -> LDS, the same fragment map (this lane writes exactly what it will read) ----------------------------------
+      const float* irow = wih + (int64_t)row * NIN + 4 * ks;
+#pragma unroll
+      for (int m = 0; m < MK; ++m) {
+        const float4 v = *reinterpret_cast<const float4*>(irow + 16 * m);
+        *reinterpret_cast<float4*>(wl_wave + (m * 8 + b) * 256) = make_float4(v.x * gs, v.y * gs, v.z * gs, v.w * gs);
+      }
     }
-    bsc[b] = (bih[row] + bhh[row]) * gs;
-    // ---- W_ih -> LDS, the same fragment map (this lane writes exactly what it will read) ----------------------------------
-    const float* irow = wih + (int64_t)row * NIN + 4 * ks;
 #pragma unroll
-    for (int m = 0; m < MK; ++m) {
-      const float4 v = *reinterpret_cast<const float4*>(irow + 16 * m);
-      *reinterpret_cast<float4*>(wl_wave + (m * 8 + b) * 256) = make_float4(v.x * gs, v.y * gs, v.z * gs, v.w * gs);
-    }
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
+  } else {
+    // One burst, oldest first: W_ih (this wave's 32 KiB of LDS, set by set), the bias, W_hh.  Everything the compiler counts in
+    // this kernel (the input rows' loads, the h row stores) is issued behind the burst, so its own waits cover the burst as well;
+    // the one wait written by hand is vmcnt(0), in front of the first barrier.
+    using P = XPack<NIN>;
+    const char* pw = reinterpret_cast<const char*>(pk) + (size_t)(d * 4 + w) * (P::SETS * 1024);
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    const uint32_t wl_lds = lds_addr(Wl + w * (MK * 8 * 256));
+    static_for<8 * MK>([&](auto PP) {
+      constexpr int p = decltype(PP)::value;
+      dma_part<false>(pw + p * 1024, lane16, wl_lds + p * 1024);
+    });
+    ldg4_uncounted<0>(bq[0], pw + P::BIAS0 * 1024, lane16);
+    ldg4_uncounted<1024>(bq[1], pw + P::BIAS0 * 1024, lane16);
+    static_for<64>([&](auto Q) {
+      constexpr int q = decltype(Q)::value;
+      ldg4_uncounted_a<(q & 3) * 1024>(wq[q], pw + (P::HH0 + (q & ~3)) * 1024, lane16);
+    });
   }
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
 
   const int t0 = d ? g.len - 1 : 0, tdir = d ? -1 : 1;
   const int tstride = seq_token_stride(g);
@@ -131,6 +168,20 @@ __global__ __launch_bounds__(256) void lstm16x_kernel(const float* __restrict__ 
   load_x(2);
   for (int i = tid; i < 16 * L16_LDH; i += 256) Hs[i] = 0.f;      // h_{-1} = 0 (buffer 0)
   f32x4v cst[2] = {(f32x4v){0.f, 0.f, 0.f, 0.f}, (f32x4v){0.f, 0.f, 0.f, 0.f}};
+  if constexpr (PRO == 1) {
+    static_for<4>([&](auto Q) { wait_vm_a16<0>(wq + 16 * decltype(Q)::value); });      // the burst is in (W_ih: in LDS)
+    wait_vm_v2<0>(bq[0], bq[1]);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      bsc[b] = bq[b >> 2][b & 3];
+#pragma unroll
+      for (int i = 0; i < 32; ++i) wf[b][i] = wq[8 * b + (i >> 2)][i & 3];
+    }
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
+  }
   __syncthreads();
 
   // ---- acc = b + x W_ih^T of one step, from the staged rows (all of a wave's B fragments come from its own LDS slice) -----
@@ -248,6 +299,22 @@ __global__ __launch_bounds__(256) void lstm16x_kernel(const float* __restrict__ 
   }
 }
 
+#define LSTM16X_ARGS                                                                                                         \
+  const float *__restrict__ x, int ldx, const float *__restrict__ wih_f, const float *__restrict__ wih_b,                    \
+      const float *__restrict__ bih_f, const float *__restrict__ bih_b, const float *__restrict__ bhh_f,                     \
+      const float *__restrict__ bhh_b, const float *__restrict__ whh_f, const float *__restrict__ whh_b,                     \
+      const float *__restrict__ pk, float *__restrict__ hc, int ldh, int64_t dump_row, SeqGeom g
+#define LSTM16X_PASS x, ldx, wih_f, wih_b, bih_f, bih_b, bhh_f, bhh_b, whh_f, whh_b, pk, hc, ldh, dump_row, g
+// the kernel, and the kernel with the prologue before the packed copy (engine option lstm_prologue = 0: same-process A/B)
+template <int NIN, bool RELU>
+__global__ __launch_bounds__(256) void lstm16x_kernel(LSTM16X_ARGS) {
+  lstm16x_body<NIN, RELU, 1>(LSTM16X_PASS);
+}
+template <int NIN, bool RELU>
+__global__ __launch_bounds__(256) void lstm16x_pro0_kernel(LSTM16X_ARGS) {
+  lstm16x_body<NIN, RELU, 0>(LSTM16X_PASS);
+}
+
 // =====================================================================================================================
 // num_features = 128: W_ih (512 x 128) is as large as W_hh and the two do not fit one CU's registers together -- W_hh fills
 // the AGPR half (256 registers per lane), the LDS has room for 31 of the wave's 64 W_ih fragment sets (k-chunk m, block b)
@@ -278,13 +345,8 @@ DEV LstmCell2 lstm_cell2_fc(f32x2 ai, f32x2 af, f32x2 ag, f32x2 ao, f32x2 c_prev
   return r;
 }
 
-template <bool RELU, int SCHED>
-__global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ wih_f,
-                                                          const float* __restrict__ wih_b, const float* __restrict__ bih_f,
-                                                          const float* __restrict__ bih_b, const float* __restrict__ bhh_f,
-                                                          const float* __restrict__ bhh_b, const float* __restrict__ whh_f,
-                                                          const float* __restrict__ whh_b, float* __restrict__ hc, int ldh,
-                                                          int64_t dump_row, SeqGeom g) {
+template <bool RELU, int SCHED, int PRO>
+DEV void lstm16x128_body(LSTM16X_ARGS) {
   constexpr int NIN = 128, RES = X128_RES;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Wl = smem;                               // [4][64 - RES][256]
@@ -302,47 +364,49 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
   float wf[8][32];                                // W_hh fragments -> AGPRs
   float bsc[8];
   float* wl_wave = Wl + w * ((64 - RES) * 256) + lane * 4;
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
-    const float gs = l16_gate_scale(b >> 1);
-    const float* wrow = whh + (int64_t)row * L16_H + 4 * ks;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const float4 v = *reinterpret_cast<const float4*>(wrow + 16 * m);
-      wf[b][4 * m + 0] = v.x * gs;
-      wf[b][4 * m + 1] = v.y * gs;
-      wf[b][4 * m + 2] = v.z * gs;
-      wf[b][4 * m + 3] = v.w * gs;
-    }
-    bsc[b] = (bih[row] + bhh[row]) * gs;
-  }
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
   float wiv[RES][4];                              // W_ih fragment sets 0 .. RES-1 -> VGPRs, the others -> LDS
+  if constexpr (PRO == 0) {
 #pragma unroll
-  for (int p = 0; p < 64; ++p) {
-    const int m = p >> 3, b = p & 7;
-    const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
-    const float gs = l16_gate_scale(b >> 1);
-    const float4 v = *reinterpret_cast<const float4*>(wih + (int64_t)row * NIN + 16 * m + 4 * ks);
-    if (p < RES) {
-      constexpr int dummy = 0;
-      (void)dummy;
-      wiv[p % RES][0] = v.x * gs;
-      wiv[p % RES][1] = v.y * gs;
-      wiv[p % RES][2] = v.z * gs;
-      wiv[p % RES][3] = v.w * gs;
-    } else {
-      *reinterpret_cast<float4*>(wl_wave + (p - RES) * 256) = make_float4(v.x * gs, v.y * gs, v.z * gs, v.w * gs);
+    for (int b = 0; b < 8; ++b) {
+      const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
+      const float gs = l16_gate_scale(b >> 1);
+      const float* wrow = whh + (int64_t)row * L16_H + 4 * ks;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const float4 v = *reinterpret_cast<const float4*>(wrow + 16 * m);
+        wf[b][4 * m + 0] = v.x * gs;
+        wf[b][4 * m + 1] = v.y * gs;
+        wf[b][4 * m + 2] = v.z * gs;
+        wf[b][4 * m + 3] = v.w * gs;
+      }
+      bsc[b] = (bih[row] + bhh[row]) * gs;
     }
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
+#pragma unroll
+    for (int p = 0; p < 64; ++p) {
+      const int m = p >> 3, b = p & 7;
+      const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
+      const float gs = l16_gate_scale(b >> 1);
+      const float4 v = *reinterpret_cast<const float4*>(wih + (int64_t)row * NIN + 16 * m + 4 * ks);
+      if (p < RES) {
+        constexpr int dummy = 0;
+        (void)dummy;
+        wiv[p % RES][0] = v.x * gs;
+        wiv[p % RES][1] = v.y * gs;
+        wiv[p % RES][2] = v.z * gs;
+        wiv[p % RES][3] = v.w * gs;
+      } else {
+        *reinterpret_cast<float4*>(wl_wave + (p - RES) * 256) = make_float4(v.x * gs, v.y * gs, v.z * gs, v.w * gs);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < RES; ++p)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(wiv[p][i]));
   }
-#pragma unroll
-  for (int p = 0; p < RES; ++p)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(wiv[p][i]));
 
   const int t0 = d ? g.len - 1 : 0, tdir = d ? -1 : 1;
   const int tstride = seq_token_stride(g);
@@ -382,9 +446,73 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
   };
   dma_x(0, 0, 0); dma_x(0, 0, 1);
   dma_x(1, 1, 0); dma_x(1, 1, 1);
+  // PRO = 1: the weights, in one burst behind the rows of x_0 / x_1 and in the order step 0 wants them -- the bias, W_ih (sets
+  // 0 .. RES-1 into their VGPRs, the others into this wave's LDS slice by LDS-DMA: no staging registers), then W_hh straight into
+  // its AGPRs.  Issue order of the prologue and what each wait leaves in flight (every request is 1 KiB per wave instruction;
+  // this kernel has no compiler-counted vector-memory LOAD anywhere and no store in front of the step loop):
+  //     4 x rows (LDS-DMA), 2 bias, 64 W_ih, W_hh sets 0..59        130 requests
+  //     wait vmcnt(60): names the bias and the resident W_ih sets     rows, bias and all of W_ih are in; 60 W_hh sets in flight
+  //     W_hh sets 60..63                                               64 in flight (a wave's counter holds 63: the last one waits for the first)
+  //     barrier, step 0's input part (240 MFMAs, no vector-memory instruction)
+  //     wait vmcnt(0): names all 64 W_hh quads                         in front of step 0's recurrent product
+  f32x4 wq[64], wiq[RES], bq[2];
+  auto request_whh = [&](auto Q) {
+    constexpr int q = decltype(Q)::value;
+    const char* pw = reinterpret_cast<const char*>(pk) + (size_t)(d * 4 + w) * (XPack<128>::SETS * 1024);
+    ldg4_uncounted_a<(q & 3) * 1024>(wq[q], pw + (XPack<128>::HH0 + (q & ~3)) * 1024, (uint32_t)lane * 16u);
+  };
+  // W_hh has landed: in front of the first recurrent product (nothing else of this wave is outstanding then)
+  auto whh_landed = [&]() {
+    if constexpr (PRO == 1) {
+      static_for<4>([&](auto Q) { wait_vm_a16<0>(wq + 16 * decltype(Q)::value); });
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+#pragma unroll
+        for (int i = 0; i < 32; ++i) wf[b][i] = wq[8 * b + (i >> 2)][i & 3];
+      // (SCHED 0's loop, left to the compiler, copied quad elements to VGPRs -- 216 v_accvgpr_read and 20 scratch accesses per
+      //  step -- until each fragment was pinned on its own as the PRO = 0 prologue pins it; SCHED 1's loop needs no pin)
+      if constexpr (SCHED == 0) {
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int i = 0; i < 32; ++i) asm volatile("" : "+a"(wf[b][i]));
+      }
+    }
+  };
+  if constexpr (PRO == 1) {
+    using P = XPack<128>;
+    const char* pw = reinterpret_cast<const char*>(pk) + (size_t)(d * 4 + w) * (P::SETS * 1024);
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    const uint32_t wl_dma = lds_addr(Wl + w * ((64 - RES) * 256));
+    ldg4_uncounted<0>(bq[0], pw + P::BIAS0 * 1024, lane16);
+    ldg4_uncounted<1024>(bq[1], pw + P::BIAS0 * 1024, lane16);
+    static_for<64>([&](auto PP) {
+      constexpr int p = decltype(PP)::value;
+      if constexpr (p < RES) ldg4_uncounted<(p & 3) * 1024>(wiq[p < RES ? p : 0], pw + (p & ~3) * 1024, lane16);
+      else dma_part<false>(pw + p * 1024, lane16, wl_dma + (p - RES) * 1024);
+    });
+    static_for<60>(request_whh);
+  }
   for (int i = tid; i < 16 * L16_LDH; i += 256) Hs[i] = 0.f;
   f32x4v cst[2] = {(f32x4v){0.f, 0.f, 0.f, 0.f}, (f32x4v){0.f, 0.f, 0.f, 0.f}};
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (PRO == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    wait_vm_v16<60>(wiq);
+    wait_vm_v16<60>(wiq + 16);
+    wait_vm_v3<60>(wiq[32], bq[0], bq[1]);
+    static_assert(RES == 33, "the three waits above name every resident set");
+    request_whh(std::integral_constant<int, 60>{});
+    request_whh(std::integral_constant<int, 61>{});
+    request_whh(std::integral_constant<int, 62>{});
+    request_whh(std::integral_constant<int, 63>{});
+#pragma unroll
+    for (int b = 0; b < 8; ++b) bsc[b] = bq[b >> 2][b & 3];
+#pragma unroll
+    for (int p = 0; p < RES; ++p)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wiv[p][i] = wiq[p][i];
+  }
   __syncthreads();
 
   f32x4v acc[8];
@@ -490,6 +618,7 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
   // SCHED 0: the step loop as it was before the LDS schedule was written by hand (kept for same-process A/B, option "lstm_sched")
   if constexpr (SCHED == 0) {
     input_part(0);
+    whh_landed();
     __syncthreads();      // step 0 requests x_2 into the buffer of x_0
 
     for (int step = 0; step < g.len; ++step) {
@@ -643,6 +772,7 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
     request_x(std::integral_constant<int, 1>{}, 0, xc1);
     wait_lds<0>(xc0, xc1);
     input_part1(0, xc0, xc1);
+    whh_landed();
     __syncthreads();      // step 0 requests x_2 into the buffer of x_0
 
     // The last step has no input part behind it and is written out on its own behind the loop (LAST): with the input part
@@ -719,19 +849,83 @@ __global__ __launch_bounds__(256) void lstm16x128_kernel(const float* __restrict
   }
 }
 
+template <bool RELU, int SCHED>
+__global__ __launch_bounds__(256) void lstm16x128_kernel(LSTM16X_ARGS) {
+  lstm16x128_body<RELU, SCHED, 1>(LSTM16X_PASS);
+}
+template <bool RELU, int SCHED>
+__global__ __launch_bounds__(256) void lstm16x128_pro0_kernel(LSTM16X_ARGS) {
+  lstm16x128_body<RELU, SCHED, 0>(LSTM16X_PASS);
+}
+
+// The packed copy (XPack): one block row per matrix set (a path's direction), 16 blocks each, 16 bytes per thread and turn.
+struct Lstm16xPackArgs {
+  const float *wih[LSTM16X_PACK_MAX], *whh[LSTM16X_PACK_MAX], *bih[LSTM16X_PACK_MAX], *bhh[LSTM16X_PACK_MAX];   // wih == nullptr: slot left untouched
+};
+template <int NIN>
+__global__ __launch_bounds__(256) void lstm16x_pack_kernel(Lstm16xPackArgs a, float* __restrict__ dst) {
+  using P = XPack<NIN>;
+  const float *wih = a.wih[blockIdx.y], *whh = a.whh[blockIdx.y], *bih = a.bih[blockIdx.y], *bhh = a.bhh[blockIdx.y];
+  if (wih == nullptr) return;
+  float4* out = reinterpret_cast<float4*>(dst + (size_t)blockIdx.y * P::DIR_FLOATS);
+  for (int f = blockIdx.x * 256 + threadIdx.x; f < 4 * P::SETS * 64; f += gridDim.x * 256) {
+    const int lane = f & 63, set = (f >> 6) % P::SETS, w = (f >> 6) / P::SETS;
+    const int i16 = lane & 15, ks = lane >> 4;
+    float4 v;
+    if (set < P::BIAS0) {
+      const bool hh = set >= P::HH0;
+      const int b = hh ? (set - P::HH0) >> 3 : set & 7, m = hh ? (set - P::HH0) & 7 : set >> 3;
+      const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
+      const float gs = l16_gate_scale(b >> 1);
+      const float* src = hh ? whh + (size_t)row * L16_H + 16 * m + 4 * ks : wih + (size_t)row * NIN + 16 * m + 4 * ks;
+      const float4 s = *reinterpret_cast<const float4*>(src);
+      v = make_float4(s.x * gs, s.y * gs, s.z * gs, s.w * gs);
+    } else {
+      float r[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int b = 4 * (set - P::BIAS0) + k;
+        const int row = (b >> 1) * L16_H + 32 * w + 16 * (b & 1) + i16;
+        r[k] = (bih[row] + bhh[row]) * l16_gate_scale(b >> 1);
+      }
+      v = make_float4(r[0], r[1], r[2], r[3]);
+    }
+    out[f] = v;
+  }
+}
+
 }  // namespace
+
+int lstm16x_pack_launch(int nin, void* stream, const float* const* wih, const float* const* whh, const float* const* bih,
+                        const float* const* bhh, int n, float* dst) {
+  if ((nin != 64 && nin != 128) || n < 1 || n > LSTM16X_PACK_MAX || dst == nullptr) return (int)hipErrorInvalidValue;
+  Lstm16xPackArgs a;
+  for (int i = 0; i < LSTM16X_PACK_MAX; ++i) {
+    a.wih[i] = i < n ? wih[i] : nullptr;
+    a.whh[i] = i < n ? whh[i] : nullptr;
+    a.bih[i] = i < n ? bih[i] : nullptr;
+    a.bhh[i] = i < n ? bhh[i] : nullptr;
+  }
+  if (nin == 64) hipLaunchKernelGGL(lstm16x_pack_kernel<64>, dim3(16, n), dim3(256), 0, static_cast<hipStream_t>(stream), a, dst);
+  else hipLaunchKernelGGL(lstm16x_pack_kernel<128>, dim3(16, n), dim3(256), 0, static_cast<hipStream_t>(stream), a, dst);
+  return (int)hipGetLastError();
+}
 
 int lstm16x_launch(int nin, bool relu, int nst16, int ndir, void* stream, const float* x, int ldx, const float* const* wih,
                    const float* const* bih, const float* const* bhh, const float* const* whh, float* hc, int ldh,
-                   int64_t dump_row, const SeqGeom& g, int sched) {
+                   int64_t dump_row, const SeqGeom& g, int sched, const float* pack) {
   if ((nin != 64 && nin != 128) || nst16 < 1 || ndir < 1 || ndir > 2 || g.len < 1) return (int)hipErrorInvalidValue;
-  auto kern = nin == 64 ? (relu ? lstm16x_kernel<64, true> : lstm16x_kernel<64, false>)
-                        : sched == 0 ? (relu ? lstm16x128_kernel<true, 0> : lstm16x128_kernel<false, 0>)
-                                     : (relu ? lstm16x128_kernel<true, 1> : lstm16x128_kernel<false, 1>);
+  const bool pro = pack != nullptr;
+  auto kern = nin == 64 ? (pro ? (relu ? lstm16x_kernel<64, true> : lstm16x_kernel<64, false>)
+                               : (relu ? lstm16x_pro0_kernel<64, true> : lstm16x_pro0_kernel<64, false>))
+              : pro    ? (sched == 0 ? (relu ? lstm16x128_kernel<true, 0> : lstm16x128_kernel<false, 0>)
+                                     : (relu ? lstm16x128_kernel<true, 1> : lstm16x128_kernel<false, 1>))
+                       : (sched == 0 ? (relu ? lstm16x128_pro0_kernel<true, 0> : lstm16x128_pro0_kernel<false, 0>)
+                                     : (relu ? lstm16x128_pro0_kernel<true, 1> : lstm16x128_pro0_kernel<false, 1>));
   const size_t lds = nin == 64 ? X16<64>::LDS_BYTES : X128_LDS_BYTES;
-  static PerDeviceOnce ready[6];
+  static PerDeviceOnce ready[12];
   const int dev = current_hip_device();
-  const int ki = (nin == 128 ? (sched == 0 ? 4 : 2) : 0) + (relu ? 1 : 0);
+  const int ki = 2 * ((nin == 128 ? (sched == 0 ? 4 : 2) : 0) + (relu ? 1 : 0)) + (pro ? 1 : 0);
   if (!ready[ki].done(dev)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
@@ -739,6 +933,6 @@ int lstm16x_launch(int nin, bool relu, int nst16, int ndir, void* stream, const 
   }
   const int r = ndir == 2 ? 1 : 0;
   hipLaunchKernelGGL(kern, dim3(nst16, ndir), dim3(256), lds, static_cast<hipStream_t>(stream), x, ldx, wih[0], wih[r], bih[0],
-                     bih[r], bhh[0], bhh[r], whh[0], whh[r], hc, ldh, dump_row, g);
+                     bih[r], bhh[0], bhh[r], whh[0], whh[r], pack, hc, ldh, dump_row, g);
   return (int)hipGetLastError();
 }

@@ -86,6 +86,14 @@ DEV void wait_vm_a16(f32x4* r) {
                : "memory");
 }
 template <int KEEP>
+DEV void wait_vm_v2(f32x4& r0, f32x4& r1) {
+  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r0), "+v"(r1) : [n] "n"(KEEP) : "memory");
+}
+template <int KEEP>
+DEV void wait_vm_v3(f32x4& r0, f32x4& r1, f32x4& r2) {
+  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r0), "+v"(r1), "+v"(r2) : [n] "n"(KEEP) : "memory");
+}
+template <int KEEP>
 DEV void wait_vm1(int& r) {
   asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(r) : [n] "n"(KEEP) : "memory");
 }
