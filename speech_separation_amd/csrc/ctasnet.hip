@@ -36,18 +36,17 @@ int make_plan(ctasnet_ctx* c, int B, int64_t T, Plan& p) {
     return c->fail(CTASNET_ERR_INVALID, "B*F*512 = %lld exceeds 32-bit indexing (B=%d, T=%lld)", (long long)(p.M * CT_H), B,
                    (long long)T);
   p.Lout = CT_L * (T / CT_L);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
+  ByteCursor cur;
   const size_t M = (size_t)p.M;
-  p.off_enc = take(M * CT_N * 4);
-  p.off_x = take(M * CT_B * 4);
-  p.off_skip = take(M * CT_B * 4);
-  p.off_c = take(M * CT_H * 4);        // c and w are contiguous: the head's masked rows [M][1024] reuse both
-  p.off_w = take(M * CT_H * 4);
-  p.off_taps = take(M * 4 * CT_L * 4);
-  p.off_part = take(M * 4 * sizeof(float2));
-  p.off_stats = take((size_t)B * 2 * sizeof(float2));
-  p.total = o;
+  p.off_enc = cur.take(M * CT_N * 4);
+  p.off_x = cur.take(M * CT_B * 4);
+  p.off_skip = cur.take(M * CT_B * 4);
+  p.off_c = cur.take(M * CT_H * 4);        // c and w are contiguous: the head's masked rows [M][1024] reuse both
+  p.off_w = cur.take(M * CT_H * 4);
+  p.off_taps = cur.take(M * 4 * CT_L * 4);
+  p.off_part = cur.take(M * 4 * sizeof(float2));
+  p.off_stats = cur.take((size_t)B * 2 * sizeof(float2));
+  p.total = cur.o;
   return CTASNET_OK;
 }
 
@@ -114,7 +113,7 @@ int ctasnet_forward(ctasnet_handle h, const float* mix, int B, int64_t T, float*
 
   // encoder (convtasnet.py:12-15), then the Separator on its output (convtasnet.py:55-83)
   hipLaunchKernelGGL(ctasnet_encoder_kernel<false>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], nullptr, enc, part);
-  CT_LAUNCH_CHECK(c, "ctasnet encoder");
+  HANDLE_LAUNCH_CHECK(c, "ctasnet encoder");
   if (int rc = launch_separator<false>(c, st, W.data() + 1, enc, 2, 256.0f, B, F, M, sb)) return rc;
 
   // decoder taps, overlap-add (convtasnet.py:92-97)

@@ -31,6 +31,7 @@
 #include "../../include/ctasnet.h"
 #include "common.h"
 #include "gemm_ws.h"
+#include "handle.h"
 
 namespace {
 
@@ -364,8 +365,6 @@ __global__ __launch_bounds__(256) void ctasnet_overlap_add_kernel(const float* _
 // ------------------------------------------------------------------------------------------------
 // host side: launch helpers for a handle type with fail(code, fmt, ...), device_id and num_cus
 // ------------------------------------------------------------------------------------------------
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 template <class Ctx, class Kern>
 int set_lds(Ctx* c, Kern kern, size_t bytes, const char* what) {
   if (bytes > 48 * 1024) {
@@ -374,12 +373,6 @@ int set_lds(Ctx* c, Kern kern, size_t bytes, const char* what) {
   }
   return CTASNET_OK;
 }
-
-#define CT_LAUNCH_CHECK(c, what)                                                                   \
-  do {                                                                                             \
-    hipError_t e_ = hipGetLastError();                                                             \
-    if (e_ != hipSuccess) return (c)->fail(CTASNET_ERR_HIP, "%s: %s", what, hipGetErrorString(e_)); \
-  } while (0)
 
 // The engine with its static tile schedule (no ticket queue): workgroup g takes tiles g, g + grid, ...  The grid is what
 // is co-resident (occupancy query once per instantiation and device, at most two workgroups per CU).
@@ -405,14 +398,14 @@ int launch_gemm(Ctx* c, hipStream_t st, const char* what, const float* W, const 
   if (gx < 1) gx = 1;
   if (ntiles < gx) gx = (int)ntiles;
   hipLaunchKernelGGL(kern, dim3(gx, colgroups), dim3(256), lds, st, W, Walt, ldw, (int)ntiles, nullptr, al, ep, NoRider{});
-  CT_LAUNCH_CHECK(c, what);
+  HANDLE_LAUNCH_CHECK(c, what);
   return CTASNET_OK;
 }
 
 template <class Ctx>
 int launch_stats(Ctx* c, hipStream_t st, const float2* part, int B, int F, int P, float n_part, float eps, float2* stats) {
   hipLaunchKernelGGL(ctasnet_stats_kernel, dim3(B), dim3(256), 0, st, part, F, P, n_part, eps, stats);
-  CT_LAUNCH_CHECK(c, "ctasnet stats");
+  HANDLE_LAUNCH_CHECK(c, "ctasnet stats");
   return CTASNET_OK;
 }
 
@@ -425,7 +418,7 @@ int launch_taps(Ctx* c, hipStream_t st, const float* ym, const float* D, int64_t
   }
   hipLaunchKernelGGL(ctasnet_taps_kernel, dim3((unsigned)((M + CT_TAP_ROWS - 1) / CT_TAP_ROWS)), dim3(256), CT_TAPS_LDS, st, ym,
                      D, M, taps);
-  CT_LAUNCH_CHECK(c, "ctasnet taps");
+  HANDLE_LAUNCH_CHECK(c, "ctasnet taps");
   return CTASNET_OK;
 }
 
@@ -435,7 +428,7 @@ int launch_overlap_add(Ctx* c, hipStream_t st, const float* taps, const float* b
   const int64_t n_out = 2 * (int64_t)B * Lout;
   hipLaunchKernelGGL(ctasnet_overlap_add_kernel<BIAS>, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, taps, bias, B, F,
                      Lout, s1, s2);
-  CT_LAUNCH_CHECK(c, "ctasnet overlap-add");
+  HANDLE_LAUNCH_CHECK(c, "ctasnet overlap-add");
   return CTASNET_OK;
 }
 
@@ -483,7 +476,7 @@ int launch_separator(Ctx* c, hipStream_t st, const float* const* sw, const float
     if (int rc = launch_stats(c, st, s.part, B, F, 4, 128.0f, 1e-10f, st1)) return rc;
     hipLaunchKernelGGL(ctasnet_dconv_kernel<TAPE>, dim3(row_wgs), dim3(256), 0, st, ci, bw[2], st1, bw[3], bw[4], bw[5], bw[6],
                        bw[7], dil, F, M, wi, s.part);
-    CT_LAUNCH_CHECK(c, "ctasnet dconv");
+    HANDLE_LAUNCH_CHECK(c, "ctasnet dconv");
     if (int rc = launch_stats(c, st, s.part, B, F, 2, 256.0f, 1e-10f, st2)) return rc;
     float* xn = xi;                           // the residual is added in place ...
     if constexpr (TAPE) {                     // ... into a copy, so x_i stays on the tape

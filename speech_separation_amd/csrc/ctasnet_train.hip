@@ -43,9 +43,9 @@ using Plan = TrainPlanBase;
 
 int make_plan(CtHandle* c, int B, int64_t T, Plan& p) {
   if (int rc = plan_train_head(c, B, T, "B*F*1024", p)) return rc;
-  size_t o = 0;
-  plan_separator_train(p, o, B, (size_t)p.M);
-  p.total = o;
+  ByteCursor cur;
+  plan_separator_train(p, cur, B, (size_t)p.M);
+  p.total = cur.o;
   return CTTRAIN_OK;
 }
 
@@ -121,7 +121,7 @@ int cttrain_train_forward(cttrain_handle h, const float* mix, int B, int64_t T, 
 
   // as ctasnet_forward, on the tape: encoder (convtasnet.py:12-15), Separator (:55-83), decoder taps and overlap-add (:92-97)
   hipLaunchKernelGGL(ctasnet_encoder_kernel<false>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], nullptr, enc, sb.part);
-  CT_LAUNCH_CHECK(c, "cttrain encoder");
+  HANDLE_LAUNCH_CHECK(c, "cttrain encoder");
   if (int rc = launch_separator<true>(c, st, W.data() + 1, enc, 2, 256.0f, B, F, M, sb)) return rc;
   if (int rc = launch_taps(c, st, sb.ym, W[1 + CT_SEP_W], M, taps)) return rc;
   return launch_overlap_add<false>(c, st, taps, nullptr, B, F, p.Lout, s1_pred, s2_pred);
@@ -149,7 +149,7 @@ int cttrain_train_backward(cttrain_handle h, const float* mix, int B, int64_t T,
   {
     const int64_t n = M * 4 * CT_L;
     hipLaunchKernelGGL(cttrain_dtaps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_s1, d_s2, F, M, p.Lout, dtaps);
-    CT_LAUNCH_CHECK(c, "cttrain dtaps");
+    HANDLE_LAUNCH_CHECK(c, "cttrain dtaps");
     if (int rc = launch_wgrad<CT_N, 2 * CT_L>(c, st, 2 * M, ALoadDense{ym, 2 * M, CT_N, 32}, ALoadDense{dtaps, 2 * M, 2 * CT_L, 32},
                                               slab, &ns))
       return rc;

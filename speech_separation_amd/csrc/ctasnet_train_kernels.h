@@ -445,7 +445,7 @@ int launch_reduce(Ctx* c, hipStream_t st, const float* slab, int nslabs, int64_t
   const int64_t n = (int64_t)rows * cols;
   hipLaunchKernelGGL(cttrain_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, slab, nslabs, stride, rows, cols,
                      out, ldo);
-  CT_LAUNCH_CHECK(c, "cttrain reduce");
+  HANDLE_LAUNCH_CHECK(c, "cttrain reduce");
   return CTASNET_OK;
 }
 
@@ -459,7 +459,7 @@ int launch_wgrad(Ctx* c, hipStream_t st, int64_t rows, const YL& yl, const XL& x
   const int ntiles = (int)((rows + 31) / 32);
   const int g = std::min(ntiles, CTT_G_W);
   hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, ntiles, yl, xl, slab);
-  CT_LAUNCH_CHECK(c, "cttrain wgrad");
+  HANDLE_LAUNCH_CHECK(c, "cttrain wgrad");
   *nslabs = g;
   return CTASNET_OK;
 }
@@ -468,7 +468,7 @@ int launch_wgrad(Ctx* c, hipStream_t st, int64_t rows, const YL& yl, const XL& x
 template <int C, class Ctx>
 int launch_colsum(Ctx* c, hipStream_t st, const float* Y, int64_t M, int ld, int col0, float* cslab, float* out) {
   hipLaunchKernelGGL(colsum_kernel<C>, dim3(CTT_G_C), dim3(256), 0, st, Y, M, ld, col0, cslab);
-  CT_LAUNCH_CHECK(c, "cttrain colsum");
+  HANDLE_LAUNCH_CHECK(c, "cttrain colsum");
   return launch_reduce(c, st, cslab, CTT_G_C, C, 1, C, out, C);
 }
 
@@ -483,33 +483,32 @@ struct SepTrainPlan {
 };
 
 // slab_floats: the unit's largest weight-gradient slab beyond the Separator's own
-inline void plan_separator_train(SepTrainPlan& p, size_t& o, int B, size_t M, size_t slab_floats = 0) {
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
-  p.off_enc = take(M * CT_N * 4);
-  p.off_stats0 = take((size_t)B * sizeof(float2));
-  p.off_x = take((size_t)(CT_BLOCKS + 1) * M * CT_B * 4);
-  p.off_skip = take(M * CT_B * 4);
-  p.off_v1 = take((size_t)CT_BLOCKS * M * CT_H * 4);
-  p.off_u = take((size_t)CT_BLOCKS * M * CT_H * 4);
-  p.off_st1 = take((size_t)CT_BLOCKS * B * sizeof(float2));
-  p.off_st2 = take((size_t)CT_BLOCKS * B * sizeof(float2));
-  p.off_ym = take(M * 2 * CT_N * 4);
-  p.off_mk = take(M * 2 * CT_N * 4);
-  p.off_taps = take(M * 4 * CT_L * 4);
-  p.off_part = take(M * 4 * sizeof(float2));
-  p.off_dv = take(M * 2 * CT_N * 4);
-  p.off_denc = take(M * CT_N * 4);
-  p.off_dx = take(M * CT_B * 4);
-  p.off_dskip = take(M * CT_B * 4);
-  p.off_bufa = take(M * CT_H * 4);
-  p.off_bufb = take(M * CT_H * 4);
-  p.off_S = take((size_t)B * sizeof(float2));
-  p.off_wrs = take((size_t)2 * CT_B * CT_H * 4);
+inline void plan_separator_train(SepTrainPlan& p, ByteCursor& cur, int B, size_t M, size_t slab_floats = 0) {
+  p.off_enc = cur.take(M * CT_N * 4);
+  p.off_stats0 = cur.take((size_t)B * sizeof(float2));
+  p.off_x = cur.take((size_t)(CT_BLOCKS + 1) * M * CT_B * 4);
+  p.off_skip = cur.take(M * CT_B * 4);
+  p.off_v1 = cur.take((size_t)CT_BLOCKS * M * CT_H * 4);
+  p.off_u = cur.take((size_t)CT_BLOCKS * M * CT_H * 4);
+  p.off_st1 = cur.take((size_t)CT_BLOCKS * B * sizeof(float2));
+  p.off_st2 = cur.take((size_t)CT_BLOCKS * B * sizeof(float2));
+  p.off_ym = cur.take(M * 2 * CT_N * 4);
+  p.off_mk = cur.take(M * 2 * CT_N * 4);
+  p.off_taps = cur.take(M * 4 * CT_L * 4);
+  p.off_part = cur.take(M * 4 * sizeof(float2));
+  p.off_dv = cur.take(M * 2 * CT_N * 4);
+  p.off_denc = cur.take(M * CT_N * 4);
+  p.off_dx = cur.take(M * CT_B * 4);
+  p.off_dskip = cur.take(M * CT_B * 4);
+  p.off_bufa = cur.take(M * CT_H * 4);
+  p.off_bufb = cur.take(M * CT_H * 4);
+  p.off_S = cur.take((size_t)B * sizeof(float2));
+  p.off_wrs = cur.take((size_t)2 * CT_B * CT_H * 4);
   const size_t slab = std::max({(size_t)CTT_G_W * 256 * 128, (size_t)CTT_G_W * CT_N * 2 * CT_L,
                                 (size_t)CTT_G_ROW * CTT_ROW_SLAB, slab_floats});
-  p.off_slab = take(slab * 4);
-  p.off_cslab = take((size_t)CTT_G_C * 2 * CT_N * 4);
-  p.off_aslab = take((size_t)CTT_G_ROW * 4);
+  p.off_slab = cur.take(slab * 4);
+  p.off_cslab = cur.take((size_t)CTT_G_C * 2 * CT_N * 4);
+  p.off_aslab = cur.take((size_t)CTT_G_ROW * 4);
 }
 
 inline SepBuffers sep_tape_buffers(const SepTrainPlan& p, void* ws) {
@@ -554,7 +553,7 @@ int launch_separator_backward(Ctx* c, hipStream_t st, const float* const* sw, fl
     const unsigned g = (unsigned)std::min<int64_t>(M, 2048);
     hipLaunchKernelGGL(cttrain_head_bwd_kernel<FORM>, dim3(g), dim3(256), CTT_HEAD_LDS, st, head_in, D, fp(p.off_mk), enc, M, dv,
                        denc);
-    CT_LAUNCH_CHECK(c, "cttrain head backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain head backward");
     if (int rc = launch_colsum<2 * CT_N>(c, st, dv, M, 2 * CT_N, 0, cslab, sg[HEAD + 2])) return rc;
     for (int q = 0; q < 4; ++q) {
       if (int rc = launch_wgrad<256, CT_B>(c, st, M, ALoadColsT<false>{dv, M, 2 * CT_N, 256 * q, 32},
@@ -568,7 +567,7 @@ int launch_separator_backward(Ctx* c, hipStream_t st, const float* const* sw, fl
                                            CT_B))
         return rc;
     hipLaunchKernelGGL(cttrain_prelu_bwd_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, dskip, skip, sw[HEAD], M * CT_B, aslab);
-    CT_LAUNCH_CHECK(c, "cttrain head prelu backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain head prelu backward");
     if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, sg[HEAD], 1)) return rc;
   }
 
@@ -605,30 +604,30 @@ int launch_separator_backward(Ctx* c, hipStream_t st, const float* const* sw, fl
     // norm_2 (GroupNorm(1), eps 1e-10) and PReLU_2: bufa = d n2 -> d u in place
     hipLaunchKernelGGL(cttrain_normstat_kernel<true>, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, u, bw[7], st2, bw[8], F, M, part,
                        slab);
-    CT_LAUNCH_CHECK(c, "cttrain norm_2 stats");
+    HANDLE_LAUNCH_CHECK(c, "cttrain norm_2 stats");
     if (int rc = launch_reduce(c, st, slab, CTT_G_ROW, 2 * CT_H, 1, CT_H, bg[8], CT_H)) return rc;
     if (int rc = launch_reduce(c, st, slab + CT_H, CTT_G_ROW, 2 * CT_H, 1, CT_H, bg[9], CT_H)) return rc;
     hipLaunchKernelGGL(cttrain_mixsum_kernel, dim3(B), dim3(256), 0, st, part, F, S);
-    CT_LAUNCH_CHECK(c, "cttrain mixsum");
+    HANDLE_LAUNCH_CHECK(c, "cttrain mixsum");
     hipLaunchKernelGGL(cttrain_normapply_kernel<true>, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, u, bw[7], st2, bw[8], S, F, M,
                        nullptr, aslab);
-    CT_LAUNCH_CHECK(c, "cttrain norm_2 backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain norm_2 backward");
     if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, bg[7], 1)) return rc;
 
     // depthwise conv (taps, bias) and norm_1's pass 1: bufb = d n1
     hipLaunchKernelGGL(cttrain_dconv_bwd_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, v1, bw[2], st1, bw[3], bw[4], bw[5], dil,
                        F, M, bufb, part, slab);
-    CT_LAUNCH_CHECK(c, "cttrain dconv backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain dconv backward");
     if (int rc = launch_reduce(c, st, slab, CTT_G_ROW, CTT_ROW_SLAB, 1, CT_R * CT_H, bg[5], CT_R * CT_H)) return rc;
     if (int rc = launch_reduce(c, st, slab + 3 * CT_H, CTT_G_ROW, CTT_ROW_SLAB, 1, CT_H, bg[6], CT_H)) return rc;
     if (int rc = launch_reduce(c, st, slab + 4 * CT_H, CTT_G_ROW, CTT_ROW_SLAB, 1, CT_H, bg[3], CT_H)) return rc;
     if (int rc = launch_reduce(c, st, slab + 5 * CT_H, CTT_G_ROW, CTT_ROW_SLAB, 1, CT_H, bg[4], CT_H)) return rc;
     hipLaunchKernelGGL(cttrain_mixsum_kernel, dim3(B), dim3(256), 0, st, part, F, S);
-    CT_LAUNCH_CHECK(c, "cttrain mixsum");
+    HANDLE_LAUNCH_CHECK(c, "cttrain mixsum");
     // norm_1 (GroupNorm(1), eps 1e-10) and PReLU_1: bufb = d n1 -> d v1 in place
     hipLaunchKernelGGL(cttrain_normapply_kernel<true>, dim3(CTT_G_ROW), dim3(256), 0, st, bufb, v1, bw[2], st1, bw[3], S, F, M,
                        nullptr, aslab);
-    CT_LAUNCH_CHECK(c, "cttrain norm_1 backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain norm_1 backward");
     if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, bg[2], 1)) return rc;
 
     // 128 -> 512 1x1: weight / bias gradients from d v1 and x_i, then d x_i = d x_{i+1} + d v1 W1 (residual) in place
@@ -659,14 +658,14 @@ int launch_separator_backward(Ctx* c, hipStream_t st, const float* const* sw, fl
       return rc;
     hipLaunchKernelGGL(cttrain_normstat_kernel<false>, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, enc, nullptr, stats0, sw[0], F, M,
                        part, slab);
-    CT_LAUNCH_CHECK(c, "cttrain GlobalNorm stats");
+    HANDLE_LAUNCH_CHECK(c, "cttrain GlobalNorm stats");
     if (int rc = launch_reduce(c, st, slab, CTT_G_ROW, 2 * CT_N, 1, CT_N, sg[0], CT_N)) return rc;
     if (int rc = launch_reduce(c, st, slab + CT_N, CTT_G_ROW, 2 * CT_N, 1, CT_N, sg[1], CT_N)) return rc;
     hipLaunchKernelGGL(cttrain_mixsum_kernel, dim3(B), dim3(256), 0, st, part, F, S);
-    CT_LAUNCH_CHECK(c, "cttrain mixsum");
+    HANDLE_LAUNCH_CHECK(c, "cttrain mixsum");
     hipLaunchKernelGGL(cttrain_normapply_kernel<false>, dim3(CTT_G_ROW), dim3(256), 0, st, bufa, enc, nullptr, stats0, sw[0], S, F,
                        M, denc, nullptr);
-    CT_LAUNCH_CHECK(c, "cttrain GlobalNorm backward");
+    HANDLE_LAUNCH_CHECK(c, "cttrain GlobalNorm backward");
   }
   return CTASNET_OK;
 }

@@ -60,20 +60,19 @@ int make_plan(dctasnet_ctx* c, int B, int64_t T, int Tv, Plan& p) {
   if (c->av && (int64_t)B * Tv * CT_N > (int64_t)INT32_MAX)
     return c->fail(DCTASNET_ERR_INVALID, "B*Tv*512 = %lld exceeds 32-bit indexing (B=%d, Tv=%d)", (long long)B * Tv * CT_N, B, Tv);
   p.Lout = CT_L * (T / CT_L);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
+  ByteCursor cur;
   const size_t M = (size_t)p.M;
-  p.off_wpk = take((size_t)DC_LAYERS * 3 * DC_TAP_FLOATS * 4);
-  p.off_enc = take(M * CT_N * 4);       // encoder output (AV: fused with the video rows); the mask epilogue reads it
-  p.off_x = take(M * CT_B * 4);
-  p.off_skip = take(M * CT_B * 4);
-  p.off_c = take(M * 2 * CT_N * 4);     // separator c | w, then ym [M][1024]; encoder ping-pong buffer before that
-  p.off_dec = take(M * 2 * CT_N * 4);   // decoder ping-pong buffer; the video rows [M][512] before that
-  p.off_taps = take(M * 4 * CT_L * 4);
-  p.off_part = take(M * 4 * sizeof(float2));
-  p.off_stats = take((size_t)B * 2 * sizeof(float2));
-  p.off_vcat = take(c->av ? (size_t)B * Tv * CT_N * 4 : 0);
-  p.total = o;
+  p.off_wpk = cur.take((size_t)DC_LAYERS * 3 * DC_TAP_FLOATS * 4);
+  p.off_enc = cur.take(M * CT_N * 4);       // encoder output (AV: fused with the video rows); the mask epilogue reads it
+  p.off_x = cur.take(M * CT_B * 4);
+  p.off_skip = cur.take(M * CT_B * 4);
+  p.off_c = cur.take(M * 2 * CT_N * 4);     // separator c | w, then ym [M][1024]; encoder ping-pong buffer before that
+  p.off_dec = cur.take(M * 2 * CT_N * 4);   // decoder ping-pong buffer; the video rows [M][512] before that
+  p.off_taps = cur.take(M * 4 * CT_L * 4);
+  p.off_part = cur.take(M * 4 * sizeof(float2));
+  p.off_stats = cur.take((size_t)B * 2 * sizeof(float2));
+  p.off_vcat = cur.take(c->av ? (size_t)B * Tv * CT_N * 4 : 0);
+  p.total = cur.o;
   return DCTASNET_OK;
 }
 }  // namespace
@@ -149,7 +148,7 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
     ps.w[4 + l] = W[DC_DEC0 + 3 * l];         // decoder.sequential.{0,2,4,6}.weight
   }
   hipLaunchKernelGGL(dctasnet_pack_kernel, dim3((unsigned)(DC_TAP_FLOATS / 4 / 256), DC_LAYERS), dim3(256), 0, st, ps, wpk);
-  CT_LAUNCH_CHECK(c, "dctasnet weight pack");
+  HANDLE_LAUNCH_CHECK(c, "dctasnet weight pack");
 
   // video rows (deepavconvtasnet.py:140-151), kept in the decoder's buffer until the encoder is done
   float* vid = nullptr;
@@ -157,18 +156,18 @@ int dctasnet_forward(dctasnet_handle h, const float* mix, const float* e1, const
     float* vcat = reinterpret_cast<float*>(base + p.off_vcat);
     hipLaunchKernelGGL(dctasnet_video_linear_kernel, dim3((unsigned)((Tv + DC_VT - 1) / DC_VT), B), dim3(256), 0, st, e1, e2,
                        W[DC_AV0], W[DC_AV0 + 1], Tv, vcat);
-    CT_LAUNCH_CHECK(c, "dctasnet video linear");
+    HANDLE_LAUNCH_CHECK(c, "dctasnet video linear");
     vid = dec;
     hipLaunchKernelGGL(dctasnet_video_frames_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, vcat, W[DC_AV0 + 2],
                        W[DC_AV0 + 3], F, Tv, M, vid);
-    CT_LAUNCH_CHECK(c, "dctasnet video frames");
+    HANDLE_LAUNCH_CHECK(c, "dctasnet video frames");
   }
 
   // deep encoder (deepconvtasnet.py:7-26): Conv1d(1, 512, 32, 16) + bias, then 4 x [dense conv d, PReLU], d = 1, 2, 4, 8.
   // Ping-pong enc <-> c; the last conv lands in enc, adds the video rows and writes the GlobalNorm partials.
   const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
   hipLaunchKernelGGL(ctasnet_encoder_kernel<true>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], W[1], enc, nullptr);
-  CT_LAUNCH_CHECK(c, "dctasnet encoder");
+  HANDLE_LAUNCH_CHECK(c, "dctasnet encoder");
   for (int l = 0; l < 4; ++l) {
     const float* x = (l & 1) ? cbuf : enc;
     float* y = (l & 1) ? enc : cbuf;

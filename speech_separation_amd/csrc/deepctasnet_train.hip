@@ -334,21 +334,20 @@ int make_plan(CtHandle* h, int B, int64_t T, int Tv, Plan& p) {
   if (av && Tv < 1) return c->fail(CTASNET_ERR_INVALID, "Tv must be >= 1 (got %d)", Tv);
   if (av && (int64_t)B * Tv * CT_N > (int64_t)INT32_MAX)
     return c->fail(CTASNET_ERR_INVALID, "B*Tv*512 = %lld exceeds 32-bit indexing (B=%d, Tv=%d)", (long long)B * Tv * CT_N, B, Tv);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
+  ByteCursor cur;
   const size_t M = (size_t)p.M;
-  plan_separator_train(p, o, B, M, (size_t)DCT_G_W * DCT_WN * DCT_WK);
-  p.off_wpk = take((size_t)DC_LAYERS * 3 * DC_TAP_FLOATS * 4);   // forward pack, then the backward's
-  p.off_c0 = take(M * CT_N * 4);                                  // tape: first conv output
-  p.off_ez = take(4 * M * CT_N * 4);                              // tape: encoder pre-activations
-  p.off_dz = take(4 * 2 * M * CT_N * 4);                          // tape: decoder pre-activations
-  p.off_ga = take(2 * M * CT_N * 4);                              // backward ping-pong
-  p.off_gb = take(2 * M * CT_N * 4);
+  plan_separator_train(p, cur, B, M, (size_t)DCT_G_W * DCT_WN * DCT_WK);
+  p.off_wpk = cur.take((size_t)DC_LAYERS * 3 * DC_TAP_FLOATS * 4);   // forward pack, then the backward's
+  p.off_c0 = cur.take(M * CT_N * 4);                                  // tape: first conv output
+  p.off_ez = cur.take(4 * M * CT_N * 4);                              // tape: encoder pre-activations
+  p.off_dz = cur.take(4 * 2 * M * CT_N * 4);                          // tape: decoder pre-activations
+  p.off_ga = cur.take(2 * M * CT_N * 4);                              // backward ping-pong
+  p.off_gb = cur.take(2 * M * CT_N * 4);
   const size_t rows_v = av ? (size_t)B * Tv : 0;
-  p.off_dvcat = take(rows_v * CT_N * 4);                         // d vcat
-  p.off_vslab = take(rows_v * 2 * CT_N * 4);                     // per-(b, t) partials of d video_ln.weight | bias
-  p.off_vcat = take(rows_v * CT_N * 4);                          // tape: compressed embeddings; the workspace ends with it
-  p.total = o;
+  p.off_dvcat = cur.take(rows_v * CT_N * 4);                         // d vcat
+  p.off_vslab = cur.take(rows_v * 2 * CT_N * 4);                     // per-(b, t) partials of d video_ln.weight | bias
+  p.off_vcat = cur.take(rows_v * CT_N * 4);                          // tape: compressed embeddings; the workspace ends with it
+  p.total = cur.o;
   return DCTTRAIN_OK;
 }
 
@@ -370,11 +369,11 @@ int launch_dense_wgrad(DctCtx* c, hipStream_t st, int64_t rows, const YL& yl, co
   const int ntiles = (int)((rows + 31) / 32);
   const int g = std::min(ntiles, DCT_G_W);
   hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds, st, ntiles, (unsigned*)nullptr, yl, xl, slab, (float*)nullptr);
-  CT_LAUNCH_CHECK(c, "dcttrain dense wgrad");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain dense wgrad");
   constexpr int RB = DCT_WN / 128, CB = DCT_WK / 32;
   hipLaunchKernelGGL((dcttrain_reduce_frag_kernel<RB, CB>), dim3(RB * CB * 32), dim3(256), 0, st, slab, g,
                      (int64_t)DCT_WN * DCT_WK, out, 3 * CT_N, 3);
-  CT_LAUNCH_CHECK(c, "dcttrain dense wgrad reduce");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain dense wgrad reduce");
   return DCTTRAIN_OK;
 }
 
@@ -419,7 +418,7 @@ int dense_wgrads(DctCtx* c, hipStream_t st, const DenseBwd& d, float* slab) {
 int dense_backward(DctCtx* c, hipStream_t st, const DenseBwd& d, float* slab, float* cslab, float* aslab) {
   // PReLU: dz = dy (z > 0 ? 1 : a) in place, d a = sum dy z over z <= 0
   hipLaunchKernelGGL(cttrain_prelu_bwd_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, d.dy, d.z, d.slope, d.rows * CT_N, aslab);
-  CT_LAUNCH_CHECK(c, "dcttrain dense prelu backward");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain dense prelu backward");
   if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, d.ga, 1)) return rc;
   if (int rc = launch_colsum<CT_N>(c, st, d.dy, d.rows, CT_N, 0, cslab, d.gb)) return rc;
   if (int rc = d.xslope ? dense_wgrads<true>(c, st, d, slab) : dense_wgrads<false>(c, st, d, slab)) return rc;
@@ -483,7 +482,7 @@ int dct_train_forward(DctCtx* c, const float* mix, const float* e1, const float*
   pack_sources(W, ps);
   ps.tmask = 0xF0u;
   hipLaunchKernelGGL(dctasnet_pack_kernel, dim3((unsigned)(DC_TAP_FLOATS / 4 / 256), DC_LAYERS), dim3(256), 0, st, ps, wpk);
-  CT_LAUNCH_CHECK(c, "dcttrain weight pack");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain weight pack");
 
   // video rows (deepavconvtasnet.py:140-151), the launches of dctasnet_forward: vcat stays on the tape; vid waits in the
   // scratch that holds the last decoder activation later on
@@ -492,18 +491,18 @@ int dct_train_forward(DctCtx* c, const float* mix, const float* e1, const float*
     float* vcat = at.fp(p.off_vcat);
     hipLaunchKernelGGL(dctasnet_video_linear_kernel, dim3((unsigned)((Tv + DC_VT - 1) / DC_VT), B), dim3(256), 0, st, e1, e2,
                        W[DC_AV0], W[DC_AV0 + 1], Tv, vcat);
-    CT_LAUNCH_CHECK(c, "davtrain video linear");
+    HANDLE_LAUNCH_CHECK(c, "davtrain video linear");
     vid = ydec;
     hipLaunchKernelGGL(dctasnet_video_frames_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, vcat, W[DC_AV0 + 2],
                        W[DC_AV0 + 3], F, Tv, M, vid);
-    CT_LAUNCH_CHECK(c, "davtrain video frames");
+    HANDLE_LAUNCH_CHECK(c, "davtrain video frames");
   }
 
   // deep encoder (deepconvtasnet.py:7-26): first conv -> c0; layer l reads c0 / PReLU(z_{l-1}) and writes z_l; the last one
   // also writes enc = PReLU(z_3) (+ the video rows: the fused tensor) and the GlobalNorm partials of enc
   const unsigned row_wgs = (unsigned)((M + CT_ROWS_PER_WG - 1) / CT_ROWS_PER_WG);
   hipLaunchKernelGGL(ctasnet_encoder_kernel<true>, dim3(row_wgs), dim3(256), 0, st, mix, T, F, M, W[0], W[1], c0, nullptr);
-  CT_LAUNCH_CHECK(c, "dcttrain encoder");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain encoder");
   for (int l = 0; l < 4; ++l) {
     float* z = at.fp(p.off_ez) + (size_t)l * M * CT_N;
     const float* x = l == 0 ? c0 : z - (size_t)M * CT_N;
@@ -557,15 +556,15 @@ int dct_train_backward(DctCtx* c, const float* mix, const float* e1, const float
   pack_sources(W, ps);
   ps.tmask = 0x0Fu;
   hipLaunchKernelGGL(dctasnet_pack_kernel, dim3((unsigned)(DC_TAP_FLOATS / 4 / 256), DC_LAYERS), dim3(256), 0, st, ps, wpk);
-  CT_LAUNCH_CHECK(c, "dcttrain backward weight pack");
+  HANDLE_LAUNCH_CHECK(c, "dcttrain backward weight pack");
 
   // ---- output head (decoder.sequential.8, ConvTranspose1d(512, 1, 32, 16) + bias, cropped): d taps, d bias, d W, d y_3
   {
     const int64_t n = M * 4 * CT_L;
     hipLaunchKernelGGL(cttrain_dtaps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_s1, d_s2, F, M, p.Lout, dtaps);
-    CT_LAUNCH_CHECK(c, "dcttrain dtaps");
+    HANDLE_LAUNCH_CHECK(c, "dcttrain dtaps");
     hipLaunchKernelGGL(dcttrain_outsum_kernel, dim3(CTT_G_ROW), dim3(256), 0, st, d_s1, d_s2, (int64_t)B * p.Lout, aslab);
-    CT_LAUNCH_CHECK(c, "dcttrain output bias");
+    HANDLE_LAUNCH_CHECK(c, "dcttrain output bias");
     if (int rc = launch_reduce(c, st, aslab, CTT_G_ROW, 1, 1, 1, G[DC_DEC0 + 13], 1)) return rc;
     const float* z3 = at.fp(p.off_dz) + (size_t)3 * 2 * M * CT_N;
     if (int rc = launch_wgrad<CT_N, 2 * CT_L>(c, st, 2 * M, ALoadDensePReLU{z3, W[DC_DEC0 + 11], 2 * M, CT_N, 32},
@@ -577,7 +576,7 @@ int dct_train_backward(DctCtx* c, const float* mix, const float* e1, const float
     const unsigned g = (unsigned)std::min<int64_t>(M, 2048);
     hipLaunchKernelGGL(cttrain_head_bwd_kernel<HEAD_DYM_OUT>, dim3(g), dim3(256), CTT_HEAD_LDS, st, dtaps, W[DC_DEC0 + 12], nullptr,
                        nullptr, M, ga, nullptr);
-    CT_LAUNCH_CHECK(c, "dcttrain head dgrad");
+    HANDLE_LAUNCH_CHECK(c, "dcttrain head dgrad");
   }
 
   // ---- deep decoder, layers 3..0 (d = 1, 2, 4, 8) on 2M rows: ga -> gb -> ga -> gb -> ga = d ym
@@ -604,14 +603,14 @@ int dct_train_backward(DctCtx* c, const float* mix, const float* e1, const float
     const int rows_v = B * Tv;
     hipLaunchKernelGGL(davtrain_video_ln_bwd_kernel, dim3(Tv, B), dim3(256), 0, st, denc, at.fp(p.off_vcat), W[DC_AV0 + 2], F, Tv,
                        dvcat, vslab);
-    CT_LAUNCH_CHECK(c, "davtrain video LayerNorm backward");
+    HANDLE_LAUNCH_CHECK(c, "davtrain video LayerNorm backward");
     if (int rc = launch_reduce(c, st, vslab, rows_v, 2 * CT_N, 1, CT_N, G[DC_AV0 + 2], CT_N)) return rc;
     if (int rc = launch_reduce(c, st, vslab + CT_N, rows_v, 2 * CT_N, 1, CT_N, G[DC_AV0 + 3], CT_N)) return rc;
     const int nchunk = (Tv + DAV_TT - 1) / DAV_TT;
     const int gr = (int)std::min<int64_t>((int64_t)B * nchunk, DAV_G_R);
     hipLaunchKernelGGL(davtrain_video_linear_bwd_kernel, dim3(CT_N / DAV_KT, gr), dim3(256), 0, st, e1, e2, dvcat, B, Tv, nchunk,
                        slab, cslab);
-    CT_LAUNCH_CHECK(c, "davtrain video linear backward");
+    HANDLE_LAUNCH_CHECK(c, "davtrain video linear backward");
     if (int rc = launch_reduce(c, st, slab, gr, (int64_t)DC_HV * CT_N, DC_HV, CT_N, G[DC_AV0], CT_N)) return rc;
     if (int rc = launch_reduce(c, st, cslab, gr, DC_HV, 1, DC_HV, G[DC_AV0 + 1], DC_HV)) return rc;
   }

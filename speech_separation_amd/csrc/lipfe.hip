@@ -1,6 +1,7 @@
 // lipfe.hip -- the lip-reading front end (src/lipreader/lipreading/model.py:141-273 with extract_feats = True: Conv3d stem
 // + ResNet-18 trunk, mouth video -> 512-wide embeddings per frame) for gfx950: handle and the extern "C" boundary declared
-// in include/lipfe.h; the kernels are in lipfe_kernels.h.
+// in include/lipfe.h; the kernels are in lipfe_kernels.h.  The handle's scaffolding is handle.h's; everything up to the trunk
+// (argument checks, the head of the workspace plan, fold, stem, max-pool) is lipfront.h's, shared with lipsn.hip.
 //
 // One forward is 24 launches, all on the caller's stream:
 //   fold      the 20 eval-mode BatchNorms -> scale = w / sqrt(var + eps), shift = b - mean * scale        (1 launch)
@@ -15,13 +16,13 @@
 // when load_state_dict copies into the same storages.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <string>
-#include <vector>
 
 #include "../../include/lipfe.h"
 #include "lipfe_kernels.h"
+
+HANDLE_ASSERT_CODES(LIPFE);
+static_assert(LIPFE_RELU == LF_ACT_RELU && LIPFE_PRELU == LF_ACT_PRELU && LIPFE_SWISH == LF_ACT_SWISH, "relu_type is LF_ACT_*");
 
 namespace {
 thread_local std::string g_create_error;
@@ -33,62 +34,23 @@ struct ConvDesc {
   int fold_off;                     // floats into the fold buffer
 };
 
-struct Sizes {
-  int Hs, Ws, h[4], w[4];           // after the stem conv; after the pool and in layers 1..4
-};
-
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-Sizes sizes_of(int H, int W) {
-  Sizes z;
-  z.Hs = (H - 1) / 2 + 1;  z.Ws = (W - 1) / 2 + 1;
-  z.h[0] = (z.Hs - 1) / 2 + 1;  z.w[0] = (z.Ws - 1) / 2 + 1;
-  for (int l = 1; l < 4; ++l) { z.h[l] = (z.h[l - 1] - 1) / 2 + 1;  z.w[l] = (z.w[l - 1] - 1) / 2 + 1; }
-  return z;
-}
-
 const int PLANES[4] = {64, 128, 256, 512};
 
-struct Plan {
-  Sizes z;
-  int64_t N;
-  size_t off_fold, off_pack, off_pre, off_act[4], total;
+struct Plan : LfPlan {
+  size_t off_act[4];
 };
+
+const LfModel LIPFE_MODEL = {"lipfe", 64, INT32_MAX, "32-bit indexing", lipfe_fold_kernel, lipfe_stem_kernel, lipfe_maxpool_kernel};
 }  // namespace
 
-struct lipfe_ctx {
-  std::string err;
-  std::vector<std::string> names;
-  std::vector<int64_t> numels;
-  std::vector<const float*> w;
-  bool bound = false;
-  int act = LIPFE_SWISH;
+struct lipfe_ctx : LfCtx {
   ConvDesc stem;
   ConvDesc conv1[8], conv2[8], down[4];   // down[l]: first block of layer l (l >= 1)
-  int64_t pack_floats = 0;
-  int fold_floats = 0;
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
-  int add(const std::string& n, int64_t numel) {
-    names.push_back(n);
-    numels.push_back(numel);
-    return (int)names.size() - 1;
-  }
-  int add_bn(const std::string& p, int C) {
-    const int i = add(p + "weight", C);
-    add(p + "bias", C);  add(p + "running_mean", C);  add(p + "running_var", C);
-    return i;
-  }
-  void place(ConvDesc& d) {
+  lipfe_ctx() { model = &LIPFE_MODEL; }
+  // conv `d`'s BatchNorm `p`* and its place in the pack buffer
+  void place(ConvDesc& d, const std::string& p) {
+    d.bn = add_bn(p, d.cout, d.fold_off);
     d.pack_off = pack_floats;  pack_floats += (int64_t)d.cout * d.cin * d.taps;
-    d.fold_off = fold_floats;  fold_floats += 2 * d.cout;
   }
 };
 
@@ -106,26 +68,24 @@ void build_table(lipfe_ctx* c) {
       ConvDesc& c1 = c->conv1[2 * l + b];
       ConvDesc& c2 = c->conv2[2 * l + b];
       c1 = ConvDesc{c->add(p + "conv1.weight", (int64_t)P * cin * 9), 0, -1, cin, P, 9, ds ? 2 : 1, 0, 0};
-      c1.bn = c->add_bn(p + "bn1.", P);
+      c->place(c1, p + "bn1.");
       int s1 = -1, s2 = -1;
       if (prelu) { s1 = c->add(p + "relu1.weight", P);  s2 = c->add(p + "relu2.weight", P); }
       c1.slope = s1;
       c2 = ConvDesc{c->add(p + "conv2.weight", (int64_t)P * P * 9), 0, s2, P, P, 9, 1, 0, 0};
-      c2.bn = c->add_bn(p + "bn2.", P);
-      c->place(c1);  c->place(c2);
+      c->place(c2, p + "bn2.");
       if (ds) {
         ConvDesc& d = c->down[l];
         d = ConvDesc{c->add(p + "downsample.0.weight", (int64_t)P * cin), 0, -1, cin, P, 1, 2, 0, 0};
-        d.bn = c->add_bn(p + "downsample.1.", P);
-        c->place(d);
+        c->place(d, p + "downsample.1.");
       }
     }
     inp = P;
   }
   c->stem = ConvDesc{c->add("frontend3D.0.weight", 64 * 245), 0, -1, 1, 64, 245, 2, 0, 0};
-  c->stem.bn = c->add_bn("frontend3D.1.", 64);
+  c->place(c->stem, "frontend3D.1.");
   if (prelu) c->stem.slope = c->add("frontend3D.2.weight", 64);
-  c->place(c->stem);
+  c->stem_pack_off = c->stem.pack_off;  c->stem_fold_off = c->stem.fold_off;  c->stem_slope = c->stem.slope;
   c->w.assign(c->names.size(), nullptr);
 }
 
@@ -146,32 +106,17 @@ const char* check_shape(int S, int T, int H, int W) {
 }
 
 int make_plan(lipfe_ctx* c, int S, int T, int H, int W, Plan& p) {
-  if (const char* why = check_shape(S, T, H, W)) return c->fail(LIPFE_ERR_INVALID, "%s (got S=%d T=%d H=%d W=%d)", why, S, T, H, W);
-  p.z = sizes_of(H, W);
-  p.N = (int64_t)S * T;
-  if (p.N * p.z.Hs * p.z.Ws > (int64_t)INT32_MAX)
-    return c->fail(LIPFE_ERR_INVALID, "S*T*Hs*Ws = %lld exceeds 32-bit indexing (S=%d T=%d H=%d W=%d)",
-                   (long long)(p.N * p.z.Hs * p.z.Ws), S, T, H, W);
+  ByteCursor cur;
+  if (int rc = lf_plan_head(c, check_shape(S, T, H, W), S, T, H, W, p, cur)) return rc;
   size_t act = 0;
   for (int l = 0; l < 4; ++l) {
     const size_t a = (size_t)p.z.h[l] * p.z.w[l] * PLANES[l];
     if (a > act) act = a;
   }
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += align256(bytes); return r; };
-  p.off_fold = take((size_t)c->fold_floats * 4);
-  p.off_pack = take((size_t)c->pack_floats * 4);
-  p.off_pre = take((size_t)p.N * p.z.Hs * p.z.Ws * 64 * 4);
-  for (int i = 0; i < 4; ++i) p.off_act[i] = take((size_t)p.N * act * 4);
-  p.total = o;
+  for (int i = 0; i < 4; ++i) p.off_act[i] = cur.take((size_t)p.N * act * 4);
+  p.total = cur.o;
   return LIPFE_OK;
 }
-
-#define LF_LAUNCH_CHECK(c, what)                                                                 \
-  do {                                                                                           \
-    hipError_t e_ = hipGetLastError();                                                           \
-    if (e_ != hipSuccess) return (c)->fail(LIPFE_ERR_HIP, "%s: %s", what, hipGetErrorString(e_)); \
-  } while (0)
 
 int launch_conv(lipfe_ctx* c, hipStream_t st, const ConvDesc& d, const float* fold, const float* pack, const float* in,
                 const float* res, float* out, int64_t N, int Hi, int Wi, int Ho, int Wo, int act) {
@@ -184,12 +129,12 @@ int launch_conv(lipfe_ctx* c, hipStream_t st, const ConvDesc& d, const float* fo
   const dim3 grid((unsigned)((a.M + LF_BM - 1) / LF_BM), (unsigned)(d.cout / LF_BN));
   if (d.taps == 9) hipLaunchKernelGGL((lipfe_conv_kernel<3, 3>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((lipfe_conv_kernel<1, 1>), grid, dim3(256), 0, st, a);
-  LF_LAUNCH_CHECK(c, "lipfe conv");
+  HANDLE_LAUNCH_CHECK(c, "lipfe conv");
   return LIPFE_OK;
 }
 
 double conv_macs_per_frame(int H, int W) {
-  const Sizes z = sizes_of(H, W);
+  const LfSizes z = sizes_of(H, W);
   double macs = (double)z.Hs * z.Ws * 64 * 245;
   int inp = 64;
   for (int l = 0; l < 4; ++l) {
@@ -207,24 +152,12 @@ extern "C" {
 int lipfe_abi_version(void) { return LIPFE_ABI_VERSION; }
 
 int lipfe_create(lipfe_handle* out, int relu_type) {
-  if (!out) {
-    g_create_error = "out must not be NULL";
-    return LIPFE_ERR_INVALID;
-  }
-  *out = nullptr;
-  if (relu_type != LIPFE_RELU && relu_type != LIPFE_PRELU && relu_type != LIPFE_SWISH) {
-    g_create_error = "relu_type must be LIPFE_RELU, LIPFE_PRELU or LIPFE_SWISH (got " + std::to_string(relu_type) + ")";
-    return LIPFE_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_create_error = "no HIP device visible: libdptnav's lip-reading front end has no CPU path";
-    return LIPFE_ERR_INVALID;
-  }
-  lipfe_ctx* c = new lipfe_ctx();
-  c->act = relu_type;
-  build_table(c);
-  *out = c;
+  if (out && relu_type != LIPFE_RELU && relu_type != LIPFE_PRELU && relu_type != LIPFE_SWISH)
+    return refuse_create(out, g_create_error,
+                         "relu_type must be LIPFE_RELU, LIPFE_PRELU or LIPFE_SWISH (got " + std::to_string(relu_type) + ")");
+  if (int rc = create(out, "lip-reading front end", g_create_error)) return rc;
+  (*out)->act = relu_type;
+  build_table(*out);
   return LIPFE_OK;
 }
 
@@ -234,24 +167,12 @@ const char* lipfe_last_error(lipfe_handle h) { return h ? h->err.c_str() : g_cre
 
 int lipfe_num_weights(lipfe_handle h) { return h ? (int)h->names.size() : 0; }
 
-const char* lipfe_weight_name(lipfe_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
-}
+const char* lipfe_weight_name(lipfe_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
 
-int64_t lipfe_weight_numel(lipfe_handle h, int i) { return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1; }
+int64_t lipfe_weight_numel(lipfe_handle h, int i) { return h ? h->weight_numel(i) : -1; }
 
 int lipfe_bind_weights(lipfe_handle h, const float* const* dev_ptrs, int n) {
-  if (!h) return LIPFE_ERR_INVALID;
-  const int nw = (int)h->names.size();
-  if (n != nw || !dev_ptrs) return h->fail(LIPFE_ERR_WEIGHTS, "expected %d weight pointers, got %d", nw, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(LIPFE_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 4)
-      return h->fail(LIPFE_ERR_WEIGHTS, "weight %d (%s) is not 4-byte aligned", i, h->names[i].c_str());
-  }
-  h->w.assign(dev_ptrs, dev_ptrs + n);
-  h->bound = true;
-  return LIPFE_OK;
+  return h ? bind_weights(h, dev_ptrs, n, 4) : LIPFE_ERR_INVALID;
 }
 
 size_t lipfe_workspace_bytes(lipfe_handle h, int S, int T, int H, int W) {
@@ -265,55 +186,30 @@ int lipfe_forward(lipfe_handle h, const float* x, int S, int T, int Hin, int Win
                   float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!h) return LIPFE_ERR_INVALID;
   lipfe_ctx* c = h;
-  if (!c->bound) return c->fail(LIPFE_ERR_WEIGHTS, "weights not bound (lipfe_bind_weights)");
-  if (!x || !out) return c->fail(LIPFE_ERR_INVALID, "x / out must not be NULL");
-  Plan p;
-  if (int rc = make_plan(c, S, T, H, W, p)) return rc;
-  if (y0 < 0 || x0 < 0 || (int64_t)y0 + H > Hin || (int64_t)x0 + W > Win)
-    return c->fail(LIPFE_ERR_INVALID, "window %d x %d at (%d, %d) does not lie inside the %d x %d frame", H, W, y0, x0, Hin, Win);
-  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
-    return c->fail(LIPFE_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Plan p;
+  // the front: act[0] = [N][h0][w0][64]; the pack (a derived copy of this forward, as the fold) is this reader's own
+  auto pack_weights = [&](float* pack) {
+    LfPackSrc ps;
+    int nb = 0;
+    for_each_conv(c, [&](const ConvDesc& d) {
+      ps.w[nb] = c->w[d.w];  ps.cin[nb] = d.cin;  ps.cout[nb] = d.cout;  ps.taps[nb] = d.taps;  ps.off[nb] = d.pack_off;
+      ++nb;
+    });
+    hipLaunchKernelGGL(lipfe_pack_kernel, dim3(512, nb), dim3(256), 0, st, ps, pack);
+    HANDLE_LAUNCH_CHECK(c, "lipfe pack");
+    return LIPFE_OK;
+  };
+  if (int rc = lf_front(c, LfVideo{x, S, T, Hin, Win, y0, x0, H, W, a, b}, out, p,
+                        [&](Plan& q) { return make_plan(c, S, T, H, W, q); }, ws, ws_bytes, st, pack_weights))
+    return rc;
   char* base = static_cast<char*>(ws);
-  float* fold = reinterpret_cast<float*>(base + p.off_fold);
-  float* pack = reinterpret_cast<float*>(base + p.off_pack);
-  float* pre = reinterpret_cast<float*>(base + p.off_pre);
+  const float* fold = reinterpret_cast<float*>(base + p.off_fold);
+  const float* pack = reinterpret_cast<float*>(base + p.off_pack);
   float* act[4];
   for (int i = 0; i < 4; ++i) act[i] = reinterpret_cast<float*>(base + p.off_act[i]);
-  const auto& Wt = c->w;
-  const Sizes& z = p.z;
+  const LfSizes& z = p.z;
   const int64_t N = p.N;
-
-  // derived copies of this forward
-  LfFoldSrc fs;
-  LfPackSrc ps;
-  int nb = 0;
-  for_each_conv(c, [&](const ConvDesc& d) {
-    fs.w[nb] = Wt[d.bn];  fs.b[nb] = Wt[d.bn + 1];  fs.m[nb] = Wt[d.bn + 2];  fs.v[nb] = Wt[d.bn + 3];
-    fs.C[nb] = d.cout;  fs.off[nb] = d.fold_off;
-    ps.w[nb] = Wt[d.w];  ps.cin[nb] = d.cin;  ps.cout[nb] = d.cout;  ps.taps[nb] = d.taps;  ps.off[nb] = d.pack_off;
-    ++nb;
-  });
-  hipLaunchKernelGGL(lipfe_fold_kernel, dim3(nb), dim3(256), 0, st, fs, fold);
-  LF_LAUNCH_CHECK(c, "lipfe fold");
-  hipLaunchKernelGGL(lipfe_pack_kernel, dim3(512, nb), dim3(256), 0, st, ps, pack);
-  LF_LAUNCH_CHECK(c, "lipfe pack");
-
-  // stem + pool -> act[0] = [N][h0][w0][64]
-  LfStemArgs sa;
-  sa.x = x;  sa.wpk = pack + c->stem.pack_off;  sa.scale = fold + c->stem.fold_off;
-  sa.slope = c->stem.slope >= 0 ? Wt[c->stem.slope] : nullptr;
-  sa.pre = pre;
-  sa.T = T;  sa.Hin = Hin;  sa.Win = Win;  sa.y0 = y0;  sa.x0 = x0;  sa.H = H;  sa.W = W;  sa.Hs = z.Hs;  sa.Ws = z.Ws;
-  sa.tiles_x = (z.Ws + LF_STX - 1) / LF_STX;  sa.tiles_y = (z.Hs + LF_STY - 1) / LF_STY;
-  sa.act = c->act;  sa.a = a;  sa.b = b;
-  const int64_t stem_wgs = N * sa.tiles_x * sa.tiles_y;   // <= N * Hs * Ws <= INT32_MAX
-  hipLaunchKernelGGL(lipfe_stem_kernel, dim3((unsigned)stem_wgs), dim3(256), 0, st, sa);
-  LF_LAUNCH_CHECK(c, "lipfe stem");
-  const int64_t pool4 = N * z.h[0] * z.w[0] * 16;
-  hipLaunchKernelGGL(lipfe_maxpool_kernel, dim3((unsigned)((pool4 + 255) / 256)), dim3(256), 0, st, pre, act[0], (long long)pool4,
-                     z.Hs, z.Ws, z.h[0], z.w[0]);
-  LF_LAUNCH_CHECK(c, "lipfe maxpool");
 
   // trunk: the block's input is act[cur]; mid, the downsampled residual and the output take the other three buffers
   int cur = 0;
@@ -337,7 +233,7 @@ int lipfe_forward(lipfe_handle h, const float* x, int S, int T, int Hin, int Win
   const int64_t total = N * 512;
   hipLaunchKernelGGL(lipfe_avgpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, act[cur], out, (long long)total,
                      z.h[3] * z.w[3]);
-  LF_LAUNCH_CHECK(c, "lipfe avgpool");
+  HANDLE_LAUNCH_CHECK(c, "lipfe avgpool");
   return LIPFE_OK;
 }
 
@@ -349,7 +245,7 @@ double lipfe_flops_per_stream(int T, int H, int W) {
 double lipfe_min_bytes_per_stream(int T, int H, int W) {
   if (check_shape(1, T, H, W)) return 0.0;
   // floats per frame that the launches read + write once each when nothing stays cached between them
-  const Sizes z = sizes_of(H, W);
+  const LfSizes z = sizes_of(H, W);
   double f = (double)H * W + 2.0 * z.Hs * z.Ws * 64 + (double)z.h[0] * z.w[0] * 64;   // stem in, pre out + in, pool out
   int inp = 64;
   for (int l = 0; l < 4; ++l) {

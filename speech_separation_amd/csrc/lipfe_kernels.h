@@ -1,49 +1,21 @@
-// lipfe_kernels.h -- device code of the lip-reading front end (lipfe.hip): Conv3d stem, max-pool, the ResNet-18 trunk's
-// 3x3 / 1x1 convolutions as implicit GEMMs on fp32 MFMA, the average pool, and the per-forward derived copies (weights in
-// K-major order, eval-mode BatchNorm folded to scale / shift).
+// lipfe_kernels.h -- device code of the lip-reading front end (lipfe.hip): the ResNet-18 trunk's 3x3 / 1x1 convolutions as
+// implicit GEMMs on fp32 MFMA, the average pool, the per-forward copy of the weights in K-major order, and the 64-channel
+// instantiations of lipfront.h's BatchNorm fold, Conv3d stem and max-pool.
 //
 // Activations are channel-last: [frame n = s*T + t][y][x][C].  Every output element is one fixed-order sum that depends on
 // its own stream only: no atomics, no split-K, so results do not depend on the batch a stream runs in.
 #pragma once
-#include "common.h"
+#include "lipfront.h"
 
 namespace {
 
-constexpr int LF_ACT_NONE = -1, LF_ACT_RELU = 0, LF_ACT_PRELU = 1, LF_ACT_SWISH = 2;
 constexpr int LF_MAX_CONVS = 20;   // 16 block convs, 3 downsample convs, the stem
-constexpr int LF_MAX_BNS = 20;
-constexpr float LF_BN_EPS = 1e-5f;
-
-DEV float lf_act(float v, int act, float slope) {
-  if (act == LF_ACT_RELU) return fmaxf(v, 0.f);
-  if (act == LF_ACT_PRELU) return v >= 0.f ? v : slope * v;
-  if (act == LF_ACT_SWISH) return v * (1.0f / (1.0f + expf(-v)));
-  return v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // derived copies, made in every forward
 // ------------------------------------------------------------------------------------------------
-struct LfFoldSrc {
-  const float* w[LF_MAX_BNS];   // weight, bias, running_mean, running_var
-  const float* b[LF_MAX_BNS];
-  const float* m[LF_MAX_BNS];
-  const float* v[LF_MAX_BNS];
-  int C[LF_MAX_BNS];
-  int off[LF_MAX_BNS];          // floats into the fold buffer: scale[C] then shift[C]
-};
-
 // grid (n_bn), block 256
-__global__ void __launch_bounds__(256) lipfe_fold_kernel(LfFoldSrc s, float* __restrict__ fold) {
-  const int i = blockIdx.x, C = s.C[i];
-  float* scale = fold + s.off[i];
-  float* shift = scale + C;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float sc = s.w[i][c] / sqrtf(s.v[i][c] + LF_BN_EPS);
-    scale[c] = sc;
-    shift[c] = s.b[i][c] - s.m[i][c] * sc;
-  }
-}
+__global__ void __launch_bounds__(256) lipfe_fold_kernel(LfFoldSrc s, float* __restrict__ fold) { lf_fold(s, fold); }
 
 struct LfPackSrc {
   const float* w[LF_MAX_CONVS];   // [Cout][Cin][taps]
@@ -81,101 +53,14 @@ __global__ void __launch_bounds__(256) lipfe_pack_kernel(LfPackSrc s, float* __r
 }
 
 // ------------------------------------------------------------------------------------------------
-// stem: Conv3d(1 -> 64, (5,7,7), stride (1,2,2), pad (2,3,3)) + BN + activation  ->  pre [N][Hs][Ws][64]
+// stem Conv3d(1 -> 64) + BN + activation -> pre [N][Hs][Ws][64] and the max-pool behind it: lipfront.h's bodies for 64 channels,
+// lane c of a wave one output channel at 16 x positions; wpk is [245][64]
 // ------------------------------------------------------------------------------------------------
-constexpr int LF_STX = 16, LF_STY = 4;                  // output tile of one workgroup
-constexpr int LF_PR = 2 * LF_STY + 5, LF_PC = 40;       // input patch rows, padded row length (37 used)
+__global__ void __launch_bounds__(256) lipfe_stem_kernel(LfStemArgs p) { lf_stem<64, 64>(p); }
 
-struct LfStemArgs {
-  const float* x;        // [S][T][Hin][Win]
-  const float* wpk;      // [245][64]
-  const float* scale;    // folded BN: scale[64], shift[64] behind it
-  const float* slope;    // PReLU slopes or NULL
-  float* pre;
-  int T, Hin, Win, y0, x0, H, W, Hs, Ws, tiles_x, tiles_y, act;
-  float a, b;
-};
-
-// grid (tiles_x * tiles_y * N), block 256: wave g computes row g of the tile, lane c one output channel at 16 x positions.
-__global__ void __launch_bounds__(256) lipfe_stem_kernel(LfStemArgs p) {
-  __shared__ __attribute__((aligned(16))) float patch[5][LF_PR][LF_PC];
-  __shared__ float ws[49][64];
-  const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
-  long long wg = blockIdx.x;
-  const int tx = (int)(wg % p.tiles_x);  wg /= p.tiles_x;
-  const int ty = (int)(wg % p.tiles_y);  wg /= p.tiles_y;
-  const long long n = wg;                  // frame s*T + t
-  const int t = (int)(n % p.T);
-  const int oy0 = ty * LF_STY, ox0 = tx * LF_STX;
-  const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3;
-  for (int i = tid; i < 5 * LF_PR * LF_PC; i += 256) {
-    const int col = i % LF_PC, r = (i / LF_PC) % LF_PR, kt = i / (LF_PC * LF_PR);
-    const int tt = t + kt - 2, iy = iy0 + r, ix = ix0 + col;
-    float v = 0.f;     // padding is zero in the normalised domain
-    if (col < 37 && tt >= 0 && tt < p.T && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-      v = fmaf(p.a, p.x[((n + (kt - 2)) * p.Hin + (p.y0 + iy)) * p.Win + (p.x0 + ix)], p.b);
-    patch[kt][r][col] = v;
-  }
-  float tot[LF_STX], acc[LF_STX];     // the 49 taps of a frame are summed on their own, then the five frames
-#pragma unroll
-  for (int i = 0; i < LF_STX; ++i) tot[i] = 0.f;
-  for (int kt = 0; kt < 5; ++kt) {
-    __syncthreads();
-    for (int i = tid; i < 49 * 64; i += 256) ws[i >> 6][i & 63] = p.wpk[kt * 49 * 64 + i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < LF_STX; ++i) acc[i] = 0.f;
-#pragma unroll 1
-    for (int ky = 0; ky < 7; ++ky) {
-      float row[LF_PC];
-      const float4* src = reinterpret_cast<const float4*>(&patch[kt][2 * g + ky][0]);
-#pragma unroll
-      for (int i = 0; i < LF_PC / 4; ++i) {
-        const float4 q = src[i];
-        row[4 * i] = q.x;  row[4 * i + 1] = q.y;  row[4 * i + 2] = q.z;  row[4 * i + 3] = q.w;
-      }
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx) {
-        const float w = ws[ky * 7 + kx][c];
-#pragma unroll
-        for (int i = 0; i < LF_STX; ++i) acc[i] = fmaf(row[2 * i + kx], w, acc[i]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < LF_STX; ++i) tot[i] += acc[i];
-  }
-  const int oy = oy0 + g;
-  if (oy >= p.Hs) return;
-  const float sc = p.scale[c], sh = p.scale[64 + c], sl = p.slope ? p.slope[c] : 0.f;
-  float* out = p.pre + ((n * p.Hs + oy) * p.Ws + ox0) * 64 + c;
-#pragma unroll
-  for (int i = 0; i < LF_STX; ++i)
-    if (ox0 + i < p.Ws) out[(long long)i * 64] = lf_act(fmaf(tot[i], sc, sh), p.act, sl);
-}
-
-// MaxPool (3,3) stride 2 pad 1 over [N][Hs][Ws][64] -> [N][Hp][Wp][64]; the padding is -inf, i.e. left out of the maximum.
-// One thread per 4 channels of an output position.
 __global__ void __launch_bounds__(256) lipfe_maxpool_kernel(const float* __restrict__ pre, float* __restrict__ out, long long total4,
                                                             int Hs, int Ws, int Hp, int Wp) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
-  const int c4 = (int)(i & 15);
-  long long pos = i >> 4;
-  const int px = (int)(pos % Wp);  pos /= Wp;
-  const int py = (int)(pos % Hp);
-  const long long n = pos / Hp;
-  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-  for (int dy = -1; dy <= 1; ++dy) {
-    const int y = 2 * py + dy;
-    if (y < 0 || y >= Hs) continue;
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int x = 2 * px + dx;
-      if (x < 0 || x >= Ws) continue;
-      const float4 v = ldg4(pre + ((n * Hs + y) * Ws + x) * 64 + 4 * c4);
-      m.x = fmaxf(m.x, v.x);  m.y = fmaxf(m.y, v.y);  m.z = fmaxf(m.z, v.z);  m.w = fmaxf(m.w, v.w);
-    }
-  }
-  *reinterpret_cast<float4*>(out + i * 4) = m;
+  lf_maxpool<64>(pre, out, total4, Hs, Ws, Hp, Wp);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // lipsn.hip -- the ShuffleNet-v2 lip reader (src/lipreader/lipreading/model.py:141-273 with backbone_type = "shufflenet" and
 // extract_feats = True: 24-channel Conv3d stem + ShuffleNetV2.features + conv_last + AvgPool2d(3), mouth video -> 1024-wide
 // embeddings per frame) for gfx950: handle and the extern "C" boundary declared in include/lipsn.h; the kernels are in
-// lipsn_kernels.h.
+// lipsn_kernels.h.  The handle's scaffolding is handle.h's; everything up to the trunk (argument checks, the head of the
+// workspace plan, fold, stem, max-pool) is lipfront.h's, shared with lipfe.hip.
 //
 // One forward is 21 launches, all on the caller's stream:
 //   fold      the 56 eval-mode BatchNorms -> scale = w / sqrt(var + eps), shift = b - mean * scale         (1 launch)
@@ -15,13 +16,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../include/lipsn.h"
 #include "lipsn_kernels.h"
+
+HANDLE_ASSERT_CODES(LIPSN);
+static_assert(LIPSN_RELU == LF_ACT_RELU && LIPSN_PRELU == LF_ACT_PRELU && LIPSN_SWISH == LF_ACT_SWISH, "relu_type is LF_ACT_*");
 
 namespace {
 thread_local std::string g_sn_create_error;
@@ -43,30 +45,18 @@ struct SnBlock {
   SnConv dw1, pwb1;     // banch1 (stride 2)
 };
 
-struct SnSizes {
-  int Hs, Ws, h[4], w[4];   // after the stem conv; after the pool and in stages 2..4
-};
-
 struct SnBlockPlan {
   int band, bands, G, ksx, ksm, ksd, offM, offD, lds_floats;
 };
 
-struct SnPlan {
-  SnSizes z;
-  int64_t N;
-  size_t off_fold, off_pack, off_pre, off_act[2], total;
+struct SnPlan : LfPlan {
+  size_t off_act[2];
 };
 
-inline size_t sn_align256(size_t n) { return (n + 255) & ~(size_t)255; }
-inline int pad32(int n) { return (n + 31) & ~31; }
+const LfModel LIPSN_MODEL = {"lipsn", SN_STEM_C, INT32_MAX / 4, "the supported 2^29 positions", lipsn_fold_kernel, lipsn_stem_kernel,
+                             lipsn_maxpool_kernel};
 
-SnSizes sn_sizes_of(int H, int W) {
-  SnSizes z;
-  z.Hs = (H - 1) / 2 + 1;  z.Ws = (W - 1) / 2 + 1;
-  z.h[0] = (z.Hs - 1) / 2 + 1;  z.w[0] = (z.Ws - 1) / 2 + 1;
-  for (int l = 1; l < 4; ++l) { z.h[l] = (z.h[l - 1] - 1) / 2 + 1;  z.w[l] = (z.w[l - 1] - 1) / 2 + 1; }
-  return z;
-}
+inline int pad32(int n) { return (n + 31) & ~31; }
 
 // LDS floats of a tile of `band` output rows of G frames; fills the offsets
 int sn_block_lds(int stride, int Hi, int Wi, int Wo, int cin, int ch, int band, int G, SnBlockPlan& b) {
@@ -96,40 +86,18 @@ SnBlockPlan sn_plan_block(int stride, int Hi, int Wi, int Ho, int Wo, int cin, i
 }
 }  // namespace
 
-struct lipsn_ctx {
-  std::string err;
-  std::vector<std::string> names;
-  std::vector<int64_t> numels;
-  std::vector<const float*> w;
-  bool bound = false;
-  int act = LIPSN_PRELU, width_x2 = 2;
+struct lipsn_ctx : LfCtx {
+  int width_x2 = 2;
   SnBlock blocks[16];
   SnConv last, stem;
-  int stem_slope = -1;
-  std::vector<SnConv*> convs;   // every conv, in table order: the fold and pack jobs
-  int pack_floats = 0, fold_floats = 0;
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
-  int add(const std::string& n, int64_t numel) {
-    names.push_back(n);
-    numels.push_back(numel);
-    return (int)names.size() - 1;
-  }
+  std::vector<SnConv*> convs;   // every conv, in table order: the pack jobs
+  lipsn_ctx() { model = &LIPSN_MODEL; }
   // conv `p0`.weight [cout][K] followed by the BatchNorm `p1`*
   void conv(SnConv& d, const std::string& p0, const std::string& p1, int cout, int K, int np) {
     d.w = add(p0 + "weight", (int64_t)cout * K);
-    d.bn = add(p1 + "weight", cout);
-    add(p1 + "bias", cout);  add(p1 + "running_mean", cout);  add(p1 + "running_var", cout);
+    d.bn = add_bn(p1, cout, d.fold_off);
     d.K = K;  d.cout = cout;  d.np = np;
-    d.pack_off = pack_floats;  pack_floats += K * np;
-    d.fold_off = fold_floats;  fold_floats += 2 * cout;
+    d.pack_off = (int)pack_floats;  pack_floats += K * np;
     convs.push_back(&d);
   }
 };
@@ -158,6 +126,7 @@ void sn_build_table(lipsn_ctx* c) {
   c->conv(c->last, "trunk.1.0.", "trunk.1.1.", SN_LAST_N, inp, SN_LAST_N);
   c->conv(c->stem, "frontend3D.0.", "frontend3D.1.", SN_STEM_C, 245, SN_STEM_CP);
   if (c->act == LIPSN_PRELU) c->stem_slope = c->add("frontend3D.2.weight", SN_STEM_C);
+  c->stem_pack_off = c->stem.pack_off;  c->stem_fold_off = c->stem.fold_off;
   c->w.assign(c->names.size(), nullptr);
 }
 
@@ -170,35 +139,20 @@ const char* sn_check_shape(int S, int T, int H, int W) {
 }
 
 int sn_make_plan(lipsn_ctx* c, int S, int T, int H, int W, SnPlan& p) {
-  if (const char* why = sn_check_shape(S, T, H, W)) return c->fail(LIPSN_ERR_INVALID, "%s (got S=%d T=%d H=%d W=%d)", why, S, T, H, W);
-  p.z = sn_sizes_of(H, W);
-  p.N = (int64_t)S * T;
-  if (p.N * p.z.Hs * p.z.Ws > (int64_t)INT32_MAX / 4)
-    return c->fail(LIPSN_ERR_INVALID, "S*T*Hs*Ws = %lld exceeds the supported 2^29 positions (S=%d T=%d H=%d W=%d)",
-                   (long long)(p.N * p.z.Hs * p.z.Ws), S, T, H, W);
+  ByteCursor cur;
+  if (int rc = lf_plan_head(c, sn_check_shape(S, T, H, W), S, T, H, W, p, cur)) return rc;
   const int* stages = SN_STAGES[c->width_x2 - 1];
   size_t act = (size_t)p.z.h[0] * p.z.w[0] * SN_STEM_C;
   for (int l = 1; l < 4; ++l) act = std::max(act, (size_t)p.z.h[l] * p.z.w[l] * stages[l - 1]);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t r = o; o += sn_align256(bytes); return r; };
-  p.off_fold = take((size_t)c->fold_floats * 4);
-  p.off_pack = take((size_t)c->pack_floats * 4);
-  p.off_pre = take((size_t)p.N * p.z.Hs * p.z.Ws * SN_STEM_C * 4);
-  for (int i = 0; i < 2; ++i) p.off_act[i] = take((size_t)p.N * act * 4);
-  p.total = o;
+  for (int i = 0; i < 2; ++i) p.off_act[i] = cur.take((size_t)p.N * act * 4);
+  p.total = cur.o;
   return LIPSN_OK;
 }
-
-#define SN_LAUNCH_CHECK(c, what)                                                                 \
-  do {                                                                                           \
-    hipError_t e_ = hipGetLastError();                                                           \
-    if (e_ != hipSuccess) return (c)->fail(LIPSN_ERR_HIP, "%s: %s", what, hipGetErrorString(e_)); \
-  } while (0)
 
 size_t sn_last_lds_bytes(int C) { return (size_t)(9 * SN_LAST_G * ((C | 1) + 4 * 33)) * 4; }
 
 double sn_macs_per_frame(int width_x2, int H, int W) {
-  const SnSizes z = sn_sizes_of(H, W);
+  const LfSizes z = sizes_of(H, W);
   const int* stages = SN_STAGES[width_x2 - 1];
   double macs = (double)z.Hs * z.Ws * SN_STEM_C * 245;
   int inp = SN_STEM_C;
@@ -218,25 +172,15 @@ extern "C" {
 int lipsn_abi_version(void) { return LIPSN_ABI_VERSION; }
 
 int lipsn_create(lipsn_handle* out, int relu_type, int width_x2) {
-  if (!out) {
-    g_sn_create_error = "out must not be NULL";
-    return LIPSN_ERR_INVALID;
-  }
-  *out = nullptr;
-  if (relu_type != LIPSN_RELU && relu_type != LIPSN_PRELU && relu_type != LIPSN_SWISH) {
-    g_sn_create_error = "relu_type must be LIPSN_RELU, LIPSN_PRELU or LIPSN_SWISH (got " + std::to_string(relu_type) + ")";
-    return LIPSN_ERR_INVALID;
-  }
-  if (width_x2 != 1 && width_x2 != 2) {
-    g_sn_create_error = "width_x2 must be 1 (width_mult 0.5) or 2 (width_mult 1.0): width_mult 1.5 and 2.0 are not built (got " +
-                        std::to_string(width_x2) + ")";
-    return LIPSN_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_sn_create_error = "no HIP device visible: libdptnav's ShuffleNet lip reader has no CPU path";
-    return LIPSN_ERR_INVALID;
-  }
+  if (out && relu_type != LIPSN_RELU && relu_type != LIPSN_PRELU && relu_type != LIPSN_SWISH)
+    return refuse_create(out, g_sn_create_error,
+                         "relu_type must be LIPSN_RELU, LIPSN_PRELU or LIPSN_SWISH (got " + std::to_string(relu_type) + ")");
+  if (out && width_x2 != 1 && width_x2 != 2)
+    return refuse_create(out, g_sn_create_error,
+                         "width_x2 must be 1 (width_mult 0.5) or 2 (width_mult 1.0): width_mult 1.5 and 2.0 are not built (got " +
+                             std::to_string(width_x2) + ")");
+  if (int rc = create(out, "ShuffleNet lip reader", g_sn_create_error)) return rc;
+  lipsn_ctx* c = *out;
   // both kernels take more dynamic LDS than the default limit
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lipsn_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      SN_BLOCK_LDS_FLOATS * 4);
@@ -244,14 +188,13 @@ int lipsn_create(lipsn_handle* out, int relu_type, int width_x2) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(lipsn_last_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sn_last_lds_bytes(SN_STAGES[1][2]));
   if (e != hipSuccess) {
-    g_sn_create_error = std::string("hipFuncSetAttribute (dynamic LDS): ") + hipGetErrorString(e);
+    delete c;
+    refuse_create(out, g_sn_create_error, std::string("hipFuncSetAttribute (dynamic LDS): ") + hipGetErrorString(e));
     return LIPSN_ERR_HIP;
   }
-  lipsn_ctx* c = new lipsn_ctx();
   c->act = relu_type;
   c->width_x2 = width_x2;
   sn_build_table(c);
-  *out = c;
   return LIPSN_OK;
 }
 
@@ -261,24 +204,12 @@ const char* lipsn_last_error(lipsn_handle h) { return h ? h->err.c_str() : g_sn_
 
 int lipsn_num_weights(lipsn_handle h) { return h ? (int)h->names.size() : 0; }
 
-const char* lipsn_weight_name(lipsn_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
-}
+const char* lipsn_weight_name(lipsn_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
 
-int64_t lipsn_weight_numel(lipsn_handle h, int i) { return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1; }
+int64_t lipsn_weight_numel(lipsn_handle h, int i) { return h ? h->weight_numel(i) : -1; }
 
 int lipsn_bind_weights(lipsn_handle h, const float* const* dev_ptrs, int n) {
-  if (!h) return LIPSN_ERR_INVALID;
-  const int nw = (int)h->names.size();
-  if (n != nw || !dev_ptrs) return h->fail(LIPSN_ERR_WEIGHTS, "expected %d weight pointers, got %d", nw, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(LIPSN_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 4)
-      return h->fail(LIPSN_ERR_WEIGHTS, "weight %d (%s) is not 4-byte aligned", i, h->names[i].c_str());
-  }
-  h->w.assign(dev_ptrs, dev_ptrs + n);
-  h->bound = true;
-  return LIPSN_OK;
+  return h ? bind_weights(h, dev_ptrs, n, 4) : LIPSN_ERR_INVALID;
 }
 
 size_t lipsn_workspace_bytes(lipsn_handle h, int S, int T, int H, int W) {
@@ -292,54 +223,29 @@ int lipsn_forward(lipsn_handle h, const float* x, int S, int T, int Hin, int Win
                   float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!h) return LIPSN_ERR_INVALID;
   lipsn_ctx* c = h;
-  if (!c->bound) return c->fail(LIPSN_ERR_WEIGHTS, "weights not bound (lipsn_bind_weights)");
-  if (!x || !out) return c->fail(LIPSN_ERR_INVALID, "x / out must not be NULL");
-  SnPlan p;
-  if (int rc = sn_make_plan(c, S, T, H, W, p)) return rc;
-  if (y0 < 0 || x0 < 0 || (int64_t)y0 + H > Hin || (int64_t)x0 + W > Win)
-    return c->fail(LIPSN_ERR_INVALID, "window %d x %d at (%d, %d) does not lie inside the %d x %d frame", H, W, y0, x0, Hin, Win);
-  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
-    return c->fail(LIPSN_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  SnPlan p;
+  // the front: act[0] = [N][h0][w0][24]; the pack (a derived copy of this forward, as the fold) is this reader's own
+  auto pack_weights = [&](float* pack) {
+    SnPackSrc ps;
+    const int nb = (int)c->convs.size();
+    for (int i = 0; i < nb; ++i) {
+      const SnConv& d = *c->convs[i];
+      ps.w[i] = c->w[d.w];  ps.K[i] = d.K;  ps.cout[i] = d.cout;  ps.np[i] = d.np;  ps.off[i] = d.pack_off;
+    }
+    hipLaunchKernelGGL(lipsn_pack_kernel, dim3(64, nb), dim3(256), 0, st, ps, pack);
+    HANDLE_LAUNCH_CHECK(c, "lipsn pack");
+    return LIPSN_OK;
+  };
+  if (int rc = lf_front(c, LfVideo{x, S, T, Hin, Win, y0, x0, H, W, a, b}, out, p,
+                        [&](SnPlan& q) { return sn_make_plan(c, S, T, H, W, q); }, ws, ws_bytes, st, pack_weights))
+    return rc;
   char* base = static_cast<char*>(ws);
-  float* fold = reinterpret_cast<float*>(base + p.off_fold);
-  float* pack = reinterpret_cast<float*>(base + p.off_pack);
-  float* pre = reinterpret_cast<float*>(base + p.off_pre);
+  const float* fold = reinterpret_cast<float*>(base + p.off_fold);
+  const float* pack = reinterpret_cast<float*>(base + p.off_pack);
   float* act[2] = {reinterpret_cast<float*>(base + p.off_act[0]), reinterpret_cast<float*>(base + p.off_act[1])};
-  const auto& Wt = c->w;
-  const SnSizes& z = p.z;
+  const LfSizes& z = p.z;
   const int64_t N = p.N;
-
-  // derived copies of this forward
-  SnFoldSrc fs;
-  SnPackSrc ps;
-  const int nb = (int)c->convs.size();
-  for (int i = 0; i < nb; ++i) {
-    const SnConv& d = *c->convs[i];
-    fs.w[i] = Wt[d.bn];  fs.b[i] = Wt[d.bn + 1];  fs.m[i] = Wt[d.bn + 2];  fs.v[i] = Wt[d.bn + 3];
-    fs.C[i] = d.cout;  fs.off[i] = d.fold_off;
-    ps.w[i] = Wt[d.w];  ps.K[i] = d.K;  ps.cout[i] = d.cout;  ps.np[i] = d.np;  ps.off[i] = d.pack_off;
-  }
-  hipLaunchKernelGGL(lipsn_fold_kernel, dim3(nb), dim3(256), 0, st, fs, fold);
-  SN_LAUNCH_CHECK(c, "lipsn fold");
-  hipLaunchKernelGGL(lipsn_pack_kernel, dim3(64, nb), dim3(256), 0, st, ps, pack);
-  SN_LAUNCH_CHECK(c, "lipsn pack");
-
-  // stem + pool -> act[0] = [N][h0][w0][24]
-  LfStemArgs sa;
-  sa.x = x;  sa.wpk = pack + c->stem.pack_off;  sa.scale = fold + c->stem.fold_off;
-  sa.slope = c->stem_slope >= 0 ? Wt[c->stem_slope] : nullptr;
-  sa.pre = pre;
-  sa.T = T;  sa.Hin = Hin;  sa.Win = Win;  sa.y0 = y0;  sa.x0 = x0;  sa.H = H;  sa.W = W;  sa.Hs = z.Hs;  sa.Ws = z.Ws;
-  sa.tiles_x = (z.Ws + LF_STX - 1) / LF_STX;  sa.tiles_y = (z.Hs + LF_STY - 1) / LF_STY;
-  sa.act = c->act;  sa.a = a;  sa.b = b;
-  const int64_t stem_wgs = N * sa.tiles_x * sa.tiles_y;   // <= N * Hs * Ws < 2^29
-  hipLaunchKernelGGL(lipsn_stem_kernel, dim3((unsigned)stem_wgs), dim3(256), 0, st, sa);
-  SN_LAUNCH_CHECK(c, "lipsn stem");
-  const int64_t pool4 = N * z.h[0] * z.w[0] * (SN_STEM_C / 4);
-  hipLaunchKernelGGL(lipsn_maxpool_kernel, dim3((unsigned)((pool4 + 255) / 256)), dim3(256), 0, st, pre, act[0], (long long)pool4,
-                     z.Hs, z.Ws, z.h[0], z.w[0]);
-  SN_LAUNCH_CHECK(c, "lipsn maxpool");
 
   // trunk: block i reads act[i & 1] and writes the other
   int bi = 0;
@@ -367,14 +273,14 @@ int lipsn_forward(lipsn_handle h, const float* x, int S, int T, int Hin, int Win
         return c->fail(LIPSN_ERR_INVALID, "block %d: a one-row tile needs %d floats of LDS", bi, bp.lds_floats);
       const int64_t wgs = (N + bp.G - 1) / bp.G * bp.bands;
       hipLaunchKernelGGL(lipsn_block_kernel, dim3((unsigned)wgs), dim3(256), (size_t)bp.lds_floats * 4, st, ba);
-      SN_LAUNCH_CHECK(c, "lipsn block");
+      HANDLE_LAUNCH_CHECK(c, "lipsn block");
     }
   }
   const int Cl = c->last.K;
   hipLaunchKernelGGL(lipsn_last_kernel, dim3((unsigned)((N + SN_LAST_G - 1) / SN_LAST_G)), dim3(256), sn_last_lds_bytes(Cl), st,
                      (const float*)act[bi & 1], (const float*)(pack + c->last.pack_off), (const float*)(fold + c->last.fold_off), out,
                      (int)N, z.h[3], z.w[3], Cl, Cl | 1);
-  SN_LAUNCH_CHECK(c, "lipsn conv_last");
+  HANDLE_LAUNCH_CHECK(c, "lipsn conv_last");
   return LIPSN_OK;
 }
 
@@ -388,7 +294,7 @@ double lipsn_flops_per_stream(int width_x2, int T, int H, int W) {
 double lipsn_min_bytes_per_stream(int width_x2, int T, int H, int W) {
   if ((width_x2 != 1 && width_x2 != 2) || sn_check_shape(1, T, H, W)) return 0.0;
   // floats per frame that the launches read + write once each when nothing stays cached between them
-  const SnSizes z = sn_sizes_of(H, W);
+  const LfSizes z = sizes_of(H, W);
   const int* stages = SN_STAGES[width_x2 - 1];
   double f = (double)H * W + 2.0 * z.Hs * z.Ws * SN_STEM_C + (double)z.h[0] * z.w[0] * SN_STEM_C;   // stem in, pre out + in, pool out
   int inp = SN_STEM_C;

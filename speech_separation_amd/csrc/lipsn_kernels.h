@@ -1,7 +1,7 @@
-// lipsn_kernels.h -- device code of the ShuffleNet-v2 lip reader (lipsn.hip): the 24-channel Conv3d stem and max-pool, one
-// fused kernel per InvertedResidual block (pointwise -> depthwise 3 x 3 -> pointwise with the block's intermediates in LDS,
-// concat + channel shuffle as a store index), conv_last + ReLU + AvgPool2d(3) in one kernel, and the per-forward derived
-// copies (K-major zero-padded weights, eval-mode BatchNorm folded to scale / shift).
+// lipsn_kernels.h -- device code of the ShuffleNet-v2 lip reader (lipsn.hip): one fused kernel per InvertedResidual block
+// (pointwise -> depthwise 3 x 3 -> pointwise with the block's intermediates in LDS, concat + channel shuffle as a store
+// index), conv_last + ReLU + AvgPool2d(3) in one kernel, the per-forward copy of the weights (K-major, zero-padded), and the
+// 24-channel instantiations of lipfront.h's BatchNorm fold, Conv3d stem and max-pool.
 //
 // Activations are channel-last: [frame n = s*T + t][y][x][C].  Every output element is one fixed-order sum over its own
 // frame's values: no atomics, no split-K.  Frames that share an MFMA tile occupy different ROWS of it, and a row's sum reads
@@ -12,32 +12,13 @@
 namespace {
 
 constexpr int SN_STEM_C = 24, SN_STEM_CP = 32;   // stem channels, padded to the lane group that computes them
-constexpr int SN_MAX_BNS = 64;                   // 13 x 3 + 3 x 5 block BatchNorms, conv_last, the stem
 constexpr int SN_MAX_PACKS = 64;                 // 13 x 3 + 3 x 5 block convs, conv_last, the stem
 
 // ------------------------------------------------------------------------------------------------
 // derived copies, made in every forward
 // ------------------------------------------------------------------------------------------------
-struct SnFoldSrc {
-  const float* w[SN_MAX_BNS];   // weight; bias, running_mean, running_var are the next three table entries
-  const float* b[SN_MAX_BNS];
-  const float* m[SN_MAX_BNS];
-  const float* v[SN_MAX_BNS];
-  int C[SN_MAX_BNS];
-  int off[SN_MAX_BNS];          // floats into the fold buffer: scale[C] then shift[C]
-};
-
 // grid (n_bn), block 256
-__global__ void __launch_bounds__(256) lipsn_fold_kernel(SnFoldSrc s, float* __restrict__ fold) {
-  const int i = blockIdx.x, C = s.C[i];
-  float* scale = fold + s.off[i];
-  float* shift = scale + C;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float sc = s.w[i][c] / sqrtf(s.v[i][c] + LF_BN_EPS);
-    scale[c] = sc;
-    shift[c] = s.b[i][c] - s.m[i][c] * sc;
-  }
-}
+__global__ void __launch_bounds__(256) lipsn_fold_kernel(LfFoldSrc s, float* __restrict__ fold) { lf_fold(s, fold); }
 
 struct SnPackSrc {
   const float* w[SN_MAX_PACKS];   // [Cout][K]: pointwise K = Cin, depthwise K = 9, stem K = 245
@@ -58,93 +39,14 @@ __global__ void __launch_bounds__(256) lipsn_pack_kernel(SnPackSrc s, float* __r
 }
 
 // ------------------------------------------------------------------------------------------------
-// stem: Conv3d(1 -> 24, (5,7,7), stride (1,2,2), pad (2,3,3)) + BN + activation  ->  pre [N][Hs][Ws][24]
-// The patch-in-LDS form of lipfe_stem_kernel for 24 channels: a 16 x 4 output tile per workgroup; thread = (channel of 32,
-// x half, row), 8 x positions each.  Lanes 24..31 of each group of 32 compute on zero weights and store nothing.
-// LfStemArgs: wpk is [245][32] here.
+// stem Conv3d(1 -> 24) + BN + activation -> pre [N][Hs][Ws][24] and the max-pool behind it: lipfront.h's bodies for 24 channels
+// on groups of 32 lanes, thread = (channel of 32, x half, row), 8 x positions each; wpk is [245][32]
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) lipsn_stem_kernel(LfStemArgs p) {
-  __shared__ __attribute__((aligned(16))) float patch[5][LF_PR][LF_PC];
-  __shared__ float ws[49][SN_STEM_CP];
-  const int tid = threadIdx.x, c = tid & 31, xh = (tid >> 5) & 1, g = tid >> 6;
-  long long wg = blockIdx.x;
-  const int tx = (int)(wg % p.tiles_x);  wg /= p.tiles_x;
-  const int ty = (int)(wg % p.tiles_y);  wg /= p.tiles_y;
-  const long long n = wg;                  // frame s*T + t
-  const int t = (int)(n % p.T);
-  const int oy0 = ty * LF_STY, ox0 = tx * LF_STX;
-  const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3;
-  for (int i = tid; i < 5 * LF_PR * LF_PC; i += 256) {
-    const int col = i % LF_PC, r = (i / LF_PC) % LF_PR, kt = i / (LF_PC * LF_PR);
-    const int tt = t + kt - 2, iy = iy0 + r, ix = ix0 + col;
-    float v = 0.f;     // padding is zero in the normalised domain
-    if (col < 37 && tt >= 0 && tt < p.T && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-      v = fmaf(p.a, p.x[((n + (kt - 2)) * p.Hin + (p.y0 + iy)) * p.Win + (p.x0 + ix)], p.b);
-    patch[kt][r][col] = v;
-  }
-  constexpr int NX = LF_STX / 2;      // 8 positions per thread: patch columns 16 xh .. 16 xh + 20
-  float tot[NX], acc[NX];             // the 49 taps of a frame are summed on their own, then the five frames
-#pragma unroll
-  for (int i = 0; i < NX; ++i) tot[i] = 0.f;
-  for (int kt = 0; kt < 5; ++kt) {
-    __syncthreads();
-    for (int i = tid; i < 49 * SN_STEM_CP; i += 256) ws[i >> 5][i & 31] = p.wpk[kt * 49 * SN_STEM_CP + i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NX; ++i) acc[i] = 0.f;
-#pragma unroll 1
-    for (int ky = 0; ky < 7; ++ky) {
-      float row[24];
-      const float4* src = reinterpret_cast<const float4*>(&patch[kt][2 * g + ky][16 * xh]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const float4 q = src[i];
-        row[4 * i] = q.x;  row[4 * i + 1] = q.y;  row[4 * i + 2] = q.z;  row[4 * i + 3] = q.w;
-      }
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx) {
-        const float w = ws[ky * 7 + kx][c];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) acc[i] = fmaf(row[2 * i + kx], w, acc[i]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NX; ++i) tot[i] += acc[i];
-  }
-  const int oy = oy0 + g;
-  if (oy >= p.Hs || c >= SN_STEM_C) return;
-  const float sc = p.scale[c], sh = p.scale[SN_STEM_C + c], sl = p.slope ? p.slope[c] : 0.f;
-  const int oxb = ox0 + NX * xh;
-  float* out = p.pre + ((n * p.Hs + oy) * p.Ws + oxb) * SN_STEM_C + c;
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-    if (oxb + i < p.Ws) out[(long long)i * SN_STEM_C] = lf_act(fmaf(tot[i], sc, sh), p.act, sl);
-}
+__global__ void __launch_bounds__(256) lipsn_stem_kernel(LfStemArgs p) { lf_stem<SN_STEM_C, SN_STEM_CP>(p); }
 
-// MaxPool (3,3) stride 2 pad 1 over [N][Hs][Ws][24] -> [N][Hp][Wp][24]; the padding is -inf, i.e. left out of the maximum.
-// One thread per 4 channels of an output position.
 __global__ void __launch_bounds__(256) lipsn_maxpool_kernel(const float* __restrict__ pre, float* __restrict__ out, long long total4,
                                                             int Hs, int Ws, int Hp, int Wp) {
-  constexpr int C4 = SN_STEM_C / 4;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
-  const int c4 = (int)(i % C4);
-  long long pos = i / C4;
-  const int px = (int)(pos % Wp);  pos /= Wp;
-  const int py = (int)(pos % Hp);
-  const long long n = pos / Hp;
-  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-  for (int dy = -1; dy <= 1; ++dy) {
-    const int y = 2 * py + dy;
-    if (y < 0 || y >= Hs) continue;
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int x = 2 * px + dx;
-      if (x < 0 || x >= Ws) continue;
-      const float4 v = ldg4(pre + ((n * Hs + y) * Ws + x) * SN_STEM_C + 4 * c4);
-      m.x = fmaxf(m.x, v.x);  m.y = fmaxf(m.y, v.y);  m.z = fmaxf(m.z, v.z);  m.w = fmaxf(m.w, v.w);
-    }
-  }
-  *reinterpret_cast<float4*>(out + i * 4) = m;
+  lf_maxpool<SN_STEM_C>(pre, out, total4, Hs, Ws, Hp, Wp);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // vfilt.hip -- the VoiceFilter separator (src/model/voicefilter.py:108-145 in eval mode: lip embeddings -> d-vector, the
 // mixture's magnitude -> dilated CNN -> LSTM -> FC -> sigmoid mask) for gfx950: handle and the extern "C" boundary declared
-// in include/vfilt.h; the kernels are in vfilt_kernels.h and lipfe_kernels.h.
+// in include/vfilt.h; the kernels are in vfilt_kernels.h and lipfe_kernels.h, the handle's scaffolding in handle.h.
 //
 // One forward, all on the caller's stream (F = input_size, q = speaker * B + item: the 2B sequences run together):
 //   fold, pack   the 8 eval-mode BatchNorms with the conv biases -> scale / shift; the six 64 -> 64 conv weights -> K-major
@@ -17,18 +17,15 @@
 // when load_state_dict copies into the same storages.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <string>
-#include <vector>
 
 #include "../../include/vfilt.h"
 #include "vfilt_kernels.h"
 
+HANDLE_ASSERT_CODES(VFILT);
+
 namespace {
 thread_local std::string g_vf_create_error;
-
-inline size_t vf_align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // kernel rows / columns and row dilation of layers 2..7 (the 64 -> 64 convolutions)
 const int VF_KH[6] = {7, 5, 5, 5, 5, 5};
@@ -45,12 +42,7 @@ struct VfPlan {
 };
 }  // namespace
 
-struct vfilt_ctx {
-  std::string err;
-  std::vector<std::string> names;
-  std::vector<int64_t> numels;
-  std::vector<const float*> w;
-  bool bound = false;
+struct vfilt_ctx : Handle {
   int F = 0, E = 0;
   int gru[2][2];                 // [layer][direction]: weight_ih (weight_hh, bias_ih, bias_hh follow)
   int fcd;                       // fc_dvector.weight (bias follows)
@@ -59,20 +51,6 @@ struct vfilt_ctx {
   int lstm;                      // weight_ih (weight_hh, bias_ih, bias_hh follow)
   int fc1, fc2;                  // weight (bias follows)
   int64_t pack_off[6], pack_floats = 0;
-  int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
-  int add(const std::string& n, int64_t numel) {
-    names.push_back(n);
-    numels.push_back(numel);
-    return (int)names.size() - 1;
-  }
 };
 
 namespace {
@@ -125,8 +103,8 @@ int vf_make_plan(vfilt_ctx* c, int B, int W, int Tv, VfPlan& p) {
     return c->fail(VFILT_ERR_INVALID, "%s (got B=%d W=%d Tv=%d, input_size=%d)", why, B, W, Tv, c->F);
   const size_t F = c->F, nseq = 2 * (size_t)B;
   p.nseq = (int)nseq;
-  size_t o = 0;
-  auto take = [&](size_t floats) { const size_t r = o; o += vf_align256(floats * 4); return r; };
+  ByteCursor cur;
+  auto take = [&](size_t floats) { return cur.take(floats * 4); };
   p.off_fold = take(128 * VF_LAYERS);
   p.off_pack = take((size_t)c->pack_floats);
   p.off_act[0] = take((size_t)B * F * W * VF_C);
@@ -144,15 +122,9 @@ int vf_make_plan(vfilt_ctx* c, int B, int W, int Tv, VfPlan& p) {
   p.off_H = take(nseq * W * VF_H);
   p.off_c = take(nseq * VF_H);
   p.off_fc = take(nseq * W * VF_FC);
-  p.total = o;
+  p.total = cur.o;
   return VFILT_OK;
 }
-
-#define VF_LAUNCH_CHECK(c, what)                                                                  \
-  do {                                                                                            \
-    hipError_t e_ = hipGetLastError();                                                            \
-    if (e_ != hipSuccess) return (c)->fail(VFILT_ERR_HIP, "%s: %s", what, hipGetErrorString(e_)); \
-  } while (0)
 
 VfGemmArgs vf_gemm_args(const float* A, long long sam, long long sak, const float* Bw, long long sbn, long long sbk,
                         const float* bias, float* C, long long scm, long long scn, int M, int N, int K) {
@@ -169,7 +141,7 @@ VfGemmArgs vf_gemm_args(const float* A, long long sam, long long sak, const floa
 int vf_launch_gemm(vfilt_ctx* c, hipStream_t st, const VfGemmArgs& a, int batches, const char* what) {
   const dim3 grid((unsigned)((long long)a.mtiles * batches), (unsigned)((a.N + LF_BN - 1) / LF_BN));
   hipLaunchKernelGGL(vfilt_gemm_kernel, grid, dim3(256), 0, st, a);
-  VF_LAUNCH_CHECK(c, what);
+  HANDLE_LAUNCH_CHECK(c, what);
   return VFILT_OK;
 }
 
@@ -191,29 +163,14 @@ extern "C" {
 int vfilt_abi_version(void) { return VFILT_ABI_VERSION; }
 
 int vfilt_create(vfilt_handle* out, int input_size, int embed_size) {
-  if (!out) {
-    g_vf_create_error = "out must not be NULL";
-    return VFILT_ERR_INVALID;
-  }
-  *out = nullptr;
-  if (input_size < 1 || input_size > VF_FMAX) {
-    g_vf_create_error = "input_size must be in [1, 257] (got " + std::to_string(input_size) + ")";
-    return VFILT_ERR_INVALID;
-  }
-  if (embed_size != 512 && embed_size != 1024) {
-    g_vf_create_error = "embed_size must be 512 or 1024 (got " + std::to_string(embed_size) + ")";
-    return VFILT_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    g_vf_create_error = "no HIP device visible: libdptnav's VoiceFilter has no CPU path";
-    return VFILT_ERR_INVALID;
-  }
-  vfilt_ctx* c = new vfilt_ctx();
-  c->F = input_size;
-  c->E = embed_size;
-  vf_build_table(c);
-  *out = c;
+  if (out && (input_size < 1 || input_size > VF_FMAX))
+    return refuse_create(out, g_vf_create_error, "input_size must be in [1, 257] (got " + std::to_string(input_size) + ")");
+  if (out && embed_size != 512 && embed_size != 1024)
+    return refuse_create(out, g_vf_create_error, "embed_size must be 512 or 1024 (got " + std::to_string(embed_size) + ")");
+  if (int rc = create(out, "VoiceFilter", g_vf_create_error)) return rc;
+  (*out)->F = input_size;
+  (*out)->E = embed_size;
+  vf_build_table(*out);
   return VFILT_OK;
 }
 
@@ -223,24 +180,12 @@ const char* vfilt_last_error(vfilt_handle h) { return h ? h->err.c_str() : g_vf_
 
 int vfilt_num_weights(vfilt_handle h) { return h ? (int)h->names.size() : 0; }
 
-const char* vfilt_weight_name(vfilt_handle h, int i) {
-  return (h && i >= 0 && i < (int)h->names.size()) ? h->names[i].c_str() : nullptr;
-}
+const char* vfilt_weight_name(vfilt_handle h, int i) { return h ? h->weight_name(i) : nullptr; }
 
-int64_t vfilt_weight_numel(vfilt_handle h, int i) { return (h && i >= 0 && i < (int)h->numels.size()) ? h->numels[i] : -1; }
+int64_t vfilt_weight_numel(vfilt_handle h, int i) { return h ? h->weight_numel(i) : -1; }
 
 int vfilt_bind_weights(vfilt_handle h, const float* const* dev_ptrs, int n) {
-  if (!h) return VFILT_ERR_INVALID;
-  const int nw = (int)h->names.size();
-  if (n != nw || !dev_ptrs) return h->fail(VFILT_ERR_WEIGHTS, "expected %d weight pointers, got %d", nw, n);
-  for (int i = 0; i < n; ++i) {
-    if (!dev_ptrs[i]) return h->fail(VFILT_ERR_WEIGHTS, "weight %d (%s) is NULL", i, h->names[i].c_str());
-    if (reinterpret_cast<uintptr_t>(dev_ptrs[i]) % 4)
-      return h->fail(VFILT_ERR_WEIGHTS, "weight %d (%s) is not 4-byte aligned", i, h->names[i].c_str());
-  }
-  h->w.assign(dev_ptrs, dev_ptrs + n);
-  h->bound = true;
-  return VFILT_OK;
+  return h ? bind_weights(h, dev_ptrs, n, 4) : VFILT_ERR_INVALID;
 }
 
 size_t vfilt_workspace_bytes(vfilt_handle h, int B, int W, int Tv) {
@@ -259,8 +204,7 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
     return c->fail(VFILT_ERR_INVALID, "mix_magnitude / emb1 / emb2 / out1 / out2 must not be NULL");
   VfPlan p;
   if (int rc = vf_make_plan(c, B, W, Tv, p)) return rc;
-  if (!ws || ws_bytes < p.total || reinterpret_cast<uintptr_t>(ws) % 256)
-    return c->fail(VFILT_ERR_WORKSPACE, "workspace: need %zu bytes, 256-byte aligned (got %zu at %p)", p.total, ws_bytes, ws);
+  if (int rc = check_workspace(c, p.total, ws, ws_bytes)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* base = static_cast<char*>(ws);
   auto at = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -292,19 +236,19 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
     fs.C[l] = l == 7 ? VF_C8 : VF_C;
   }
   hipLaunchKernelGGL(vfilt_fold_kernel, dim3(VF_LAYERS), dim3(64), 0, st, fs, fold);
-  VF_LAUNCH_CHECK(c, "vfilt fold");
+  HANDLE_LAUNCH_CHECK(c, "vfilt fold");
   LfPackSrc ps;
   for (int i = 0; i < 6; ++i) {
     ps.w[i] = Wt[c->conv[i + 1]];  ps.cin[i] = VF_C;  ps.cout[i] = VF_C;  ps.taps[i] = VF_KH[i] * VF_KW[i];
     ps.off[i] = c->pack_off[i];
   }
   hipLaunchKernelGGL(lipfe_pack_kernel, dim3(100, 6), dim3(256), 0, st, ps, pack);
-  VF_LAUNCH_CHECK(c, "vfilt pack");
+  HANDLE_LAUNCH_CHECK(c, "vfilt pack");
 
   // CNN
   hipLaunchKernelGGL(vfilt_conv1_kernel, dim3((unsigned)((pos * 64 + 255) / 256)), dim3(256), 0, st, mix, Wt[c->conv[0]], fold,
                      act[0], pos * 64, W);
-  VF_LAUNCH_CHECK(c, "vfilt conv1");
+  HANDLE_LAUNCH_CHECK(c, "vfilt conv1");
   int cur = 0;
   for (int i = 0; i < 6; ++i) {
     LfConvArgs a;
@@ -316,12 +260,12 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
     const dim3 grid((unsigned)((pos + LF_BM - 1) / LF_BM), 1);
     if (i == 0) hipLaunchKernelGGL((lipfe_conv_kernel<7, 1>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((lipfe_conv_kernel<5, 5>), grid, dim3(256), 0, st, a);
-    VF_LAUNCH_CHECK(c, "vfilt conv");
+    HANDLE_LAUNCH_CHECK(c, "vfilt conv");
     cur ^= 1;
   }
   hipLaunchKernelGGL(vfilt_conv8_kernel, dim3((unsigned)((pos * 8 + 255) / 256)), dim3(256), 0, st, act[cur], Wt[c->conv[7]],
                      fold + 128 * 7, flat, pos * 8, F, W);
-  VF_LAUNCH_CHECK(c, "vfilt conv8");
+  HANDLE_LAUNCH_CHECK(c, "vfilt conv8");
 
   // d-vector: GRU layer 1 in both directions over the 2B sequences
   const long long rows = (long long)B * Tv;          // rows of one speaker's embeddings
@@ -335,14 +279,14 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
   VfTransposeSrc ts;
   ts.w[0] = Wt[c->gru[0][0] + 1];  ts.w[1] = Wt[c->gru[0][1] + 1];  ts.w[2] = Wt[c->gru[1][0] + 1];
   hipLaunchKernelGGL(vfilt_transpose_kernel, dim3((3 * F * F + 255) / 256, 3), dim3(256), 0, st, ts, whht, F);
-  VF_LAUNCH_CHECK(c, "vfilt gru transpose");
+  HANDLE_LAUNCH_CHECK(c, "vfilt gru transpose");
   VfGruArgs ga;
   for (int d = 0; d < 2; ++d) {
     ga.gi[d] = gi0 + (long long)d * nseq * Tv * 3 * F;  ga.whht[d] = whht + (long long)d * 3 * F * F;  ga.bhh[d] = Wt[c->gru[0][d] + 3];
   }
   ga.y = y0;  ga.ldy = 2 * F;  ga.Tv = Tv;  ga.F = F;
   hipLaunchKernelGGL(vfilt_gru_kernel, dim3(nseq, 2), dim3(1024), 0, st, ga);
-  VF_LAUNCH_CHECK(c, "vfilt gru 1");
+  HANDLE_LAUNCH_CHECK(c, "vfilt gru 1");
   // layer 2 forward in full; its backward direction only at the last position, where it starts
   {
     const int g = c->gru[1][0];
@@ -351,14 +295,14 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
     ga.gi[0] = ga.gi[1] = gi1;  ga.whht[0] = ga.whht[1] = whht + (long long)2 * 3 * F * F;  ga.bhh[0] = ga.bhh[1] = Wt[g + 3];
     ga.y = y1;
     hipLaunchKernelGGL(vfilt_gru_kernel, dim3(nseq, 1), dim3(1024), 0, st, ga);
-    VF_LAUNCH_CHECK(c, "vfilt gru 2");
+    HANDLE_LAUNCH_CHECK(c, "vfilt gru 2");
     const int gb = c->gru[1][1];
     const long long last = (long long)(Tv - 1) * 2 * F;
     a = vf_gemm_args(y0 + last, (long long)Tv * 2 * F, 1, Wt[gb], 2 * F, 1, Wt[gb + 2], gi1b, 3 * F, 1, nseq, 3 * F, 2 * F);
     if (int rc = vf_launch_gemm(c, st, a, 1, "vfilt gru input 2 reverse")) return rc;
     hipLaunchKernelGGL(vfilt_gru_first_step_kernel, dim3(nseq), dim3(320), 0, st, gi1b, Wt[gb + 3], y1 + last + F,
                        (long long)Tv * 2 * F, F);
-    VF_LAUNCH_CHECK(c, "vfilt gru 2 reverse");
+    HANDLE_LAUNCH_CHECK(c, "vfilt gru 2 reverse");
     a = vf_gemm_args(y1 + last, (long long)Tv * 2 * F, 1, Wt[c->fcd], 2 * F, 1, Wt[c->fcd + 1], dvec, F, 1, nseq, F, 2 * F);
     if (int rc = vf_launch_gemm(c, st, a, 1, "vfilt fc_dvector")) return rc;
   }
@@ -379,7 +323,7 @@ int vfilt_forward(vfilt_handle h, const float* mix, const float* emb1, const flo
     la.t = t;
     if (nseq == 2) hipLaunchKernelGGL(vfilt_lstm_step_kernel<2>, dim3(VF_H / 4, 1), dim3(256), 0, st, la);
     else hipLaunchKernelGGL(vfilt_lstm_step_kernel<8>, dim3(VF_H / 4, (nseq + 7) / 8), dim3(256), 0, st, la);
-    VF_LAUNCH_CHECK(c, "vfilt lstm step");
+    HANDLE_LAUNCH_CHECK(c, "vfilt lstm step");
   }
 
   // FC tail
