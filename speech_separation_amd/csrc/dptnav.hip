@@ -2,11 +2,13 @@
 // the extern "C" boundary declared in include/dptnav.h.  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dptnav.h"
@@ -48,28 +50,55 @@ struct Plan {  // workspace offsets in floats
   size_t qkv_n, att_n, y1_n, hc_n;
 };
 
-// One in-flight pass over a (sub-)batch: its workspace slice, stream and ticket-counter cursor.
+// The ticket counters of one stream's launches: a zeroed region of QUEUE_SLOTS counters and the next free one.  Every launch
+// that hands out tiles (or sequences) by ticket takes its counters here, in launch order.
+struct Tickets {
+  unsigned* base = nullptr;
+  int next = 0;
+  unsigned* take(int n) {   // nullptr when the zeroed region is used up: the caller fails the launch
+    if (next + n > QUEUE_SLOTS) return nullptr;
+    unsigned* q = base + next;
+    next += n;
+    return q;
+  }
+  void give_back(int n) { next -= n; }   // the launch they were taken for did not go out
+  hipError_t reset(hipStream_t st) {     // stream ordered: behind every launch that still counts on the old values
+    next = 0;
+    return hipMemsetAsync(base, 0, QUEUE_SLOTS * sizeof(unsigned), st);
+  }
+  // between two paths of a long pass: zero the region again while fewer than `reserve` counters are left
+  hipError_t recycle_if_low(hipStream_t st, int reserve) { return next > QUEUE_SLOTS - reserve ? reset(st) : hipSuccess; }
+};
+// A stream and the ticket counters of the launches that go out on it.
+struct Lane {
+  hipStream_t st = nullptr;
+  Tickets tk;
+};
+
+// Fragment-order (or otherwise rearranged) weight copies the kernels read, one slot per path in the workspace.
+enum PackKind {
+  PACK_ATTN = 0,   // attention / FFN weights for the fused attention block (attn_block.h)              Plan::wpack
+  PACK_WIH,        // W_ih, both directions, for the K4 launches (gemm_ws.h, ldw == 0)                   Plan::wih
+  PACK_INW,        // attention in-projection weights for gemm_t.hip (training forward)                 Plan::winp
+  PACK_WHH4,       // W_hh in the order of the low-latency recurrence (lstm4.hip, `packed`)             Plan::whh4
+  PACK_X16,        // W_ih, W_hh and the summed bias, pre-scaled, for lstm16x.hip's prologue (`pack`)    Plan::x16pack
+  PACK_BWD,        // what dgrad_t.hip / dgrad_r.hip multiply by (BWD_PACK_*)                            BwdPlan::wiht
+  PACK_KINDS
+};
+
+// One in-flight pass over a (sub-)batch: its workspace slice, its stream with the ticket-counter cursor, and which weight packs
+// the slice holds.
 struct Run {
-  float* ws;
-  Plan pl;
-  hipStream_t st;
-  int slot;
+  float* ws = nullptr;
+  Plan pl{};
+  Lane lane;
   hipEvent_t lstm_wait = nullptr;    // if set: the recurrence launch waits for this event (other half's recurrence)
   hipEvent_t lstm_record = nullptr;  // if set: recorded right after the recurrence launch
   int half = 0;                      // which half of a split batch this run is (salts the dropout seed)
-  bool packed_whh4 = false;          // ws + pl.whh4 holds the fragment-order W_hh copies of ALL paths for lstm4.hip (made at its first launch of the pass)
-  bool packed_x16 = false;           // ws + pl.x16pack holds the fragment-order, pre-scaled W_ih / W_hh / bias copies of ALL paths for lstm16x.hip (made at its first launch of the pass)
-  bool packed_inw = false;           // ws + pl.winp holds the fragment-order in-projection weights of ALL paths (dptnav_train_forward); otherwise slot 0 = this path
-  bool packed_wih = false;           // ws + pl.wih holds the fragment-order W_ih copies of ALL paths; otherwise run_path packs its own
   bool fuse128 = false;              // num_features = 128: input projection inside the recurrence for this pass (dptnav_ctx::fuse128_for)
   int batch_total = 0;               // mixtures of the whole call this run is a sub-batch of (0: a stage entry point, unknown)
-  bool packed = false;               // ws + pl.wpack holds the packed weights of ALL paths (dptnav_forward); otherwise
-                                     // run_path packs the path it is about to run
-  unsigned* take_queue(int n) {
-    unsigned* q = reinterpret_cast<unsigned*>(ws + pl.queue) + slot;
-    slot += n;
-    return q;
-  }
+  bool all_paths[PACK_KINDS] = {};   // the slice holds this pack for ALL paths (pack_all, or the first on-demand pack of a kind
+                                     // that is always made whole); otherwise run_pack makes the one path that is asked for
 };
 
 }  // namespace
@@ -234,6 +263,14 @@ struct dptnav_ctx {
 namespace {
 
 inline size_t align64(size_t nfloats) { return (nfloats + 63) & ~(size_t)63; }
+
+// f(N) with the model's feature width as a compile-time constant: every host function that is a template over it is called
+// through here, with its argument list written once.
+template <class F>
+int with_width(const dptnav_ctx* c, F&& f) {
+  if (c->cfg.num_features == 128) return f(std::integral_constant<int, 128>{});
+  return f(std::integral_constant<int, 64>{});
+}
 
 // Opt-in per-kernel timing: HIP events recorded on the launch stream around one launch.
 // fault injection for the error-path tests (option "inject_fail"): the n-th launch of the GEMM engine / of fcln.hip from now on fails
@@ -499,12 +536,13 @@ constexpr int BWD_SLAB_WGS = 256;       // workgroups of one wgrad / colsum laun
 // RD = WgradRider<...> (gemm_ws.h): the launch also forms the weight gradient of the layer whose data gradient it is;
 // one workgroup per CU then (as many partial tiles as the stand-alone weight-gradient kernels leave), grid in *grid_used.
 template <int KIN, int NT, int WR, int WC, bool WT = false, bool SPLIT = false, class AL, class EP, class RD = NoRider>
-int launch_gemm(dptnav_ctx* c, Run& run, int cat, const char* what, const float* W, int64_t ntiles, int colgroups,
+int launch_gemm(dptnav_ctx* c, Lane& lane, int cat, const char* what, const float* W, int64_t ntiles, int colgroups,
                 const AL& al, const EP& ep, const float* Walt = nullptr, int ldw = KIN, int* grid_used = nullptr,
                 const RD& rider = RD{}) {
-  hipStream_t st = run.st;
+  hipStream_t st = lane.st;
   if (int rc = inject_failure(c, what)) return rc;
-  if (run.slot + colgroups > QUEUE_SLOTS) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
+  unsigned* const queue = lane.tk.take(colgroups);
+  if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
   auto kern = gemm_ws_kernel<KIN, NT, WR, WC, AL, EP, WT, SPLIT, RD>;
   const size_t lds = GemmShape<KIN, NT, WR, WC>::lds_bytes(EP::DIRECT, SPLIT, rider_kk<RD>::value * (RD::ON ? 1 : 0));
   static std::atomic<int> resident_dev[64];  // per instantiation and device (zero-initialised; idempotent fill)
@@ -524,7 +562,6 @@ int launch_gemm(dptnav_ctx* c, Run& run, int cat, const char* what, const float*
   if (gx < 1) gx = 1;
   ProfScope ps(c, cat, st);
   if (grid_used) *grid_used = cap_grid(ntiles, gx);
-  unsigned* const queue = run.take_queue(colgroups);
   hipLaunchKernelGGL(kern, dim3(cap_grid(ntiles, gx), colgroups), dim3(256), lds, st, W, Walt, ldw, (int)ntiles,
                      c->opt_deterministic ? nullptr : queue, al, ep, rider);
   LAUNCH_CHECK(c, what);
@@ -568,187 +605,183 @@ bool path_fusable(const dptnav_ctx* c, int path, int B, int S) {
          c->cfg.num_heads == 4;
 }
 
-// fragment-order copies of the attention / FFN weights of paths [first, first + n) for the fused attention block, from
-// the weights as they are NOW (an optimizer may have stepped since the last call)
-static int pack_attn_weights(dptnav_ctx* c, hipStream_t st, int first, int n, float* dst) {
-  std::vector<AttnPackSrc> src((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const PathWeights& w = c->pw[first + i];
-    src[(size_t)i] = AttnPackSrc{w.in_w, w.out_w, w.ndir == 2 ? w.ffn_w : nullptr};   // [128][256] only with both directions
-  }
-  const int rc = attn_pack_launch(st, src.data(), n, dst);
-  if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention weight pack: %s", hipGetErrorString((hipError_t)rc));
-  return DPTNAV_OK;
-}
-
-// fragment-order copies of W_ih (forward, reverse) of paths [first, first + n) -> dst[(path - first)][2][512 x N]
-template <int N>
-static int pack_wih(dptnav_ctx* c, hipStream_t st, int first, int n, float* dst) {
-  GemmPackArgs a;
-  for (int i = 0; i < GEMM_PACK_MAX; ++i) a.src[i] = nullptr;
-  if (2 * n > GEMM_PACK_MAX) return c->fail(DPTNAV_ERR_INVALID, "W_ih pack: %d paths in one launch", n);
-  for (int i = 0; i < n; ++i) {
-    const PathWeights& w = c->pw[first + i];
-    a.src[2 * i] = w.w_ih[0];
-    a.src[2 * i + 1] = w.ndir == 2 ? w.w_ih[1] : nullptr;
-  }
-  a.rows = 4 * LSTM_H;
-  a.K = N;
-  hipLaunchKernelGGL(gemm_pack_rows_kernel, dim3(16, 2 * n), dim3(256), 0, st, a, dst);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "W_ih pack: %s", hipGetErrorString(e));
-  return DPTNAV_OK;
-}
-
-// all paths of the model into run.ws + pl.wih (dptnav_forward / dptnav_train_forward: once per pass and sub-batch)
-template <int N>
-static int pack_wih_all(dptnav_ctx* c, Run& run) {
-  if (!c->opt_pack_wih) return DPTNAV_OK;
-  const int npaths = 2 * c->cfg.num_blocks;
-  for (int first = 0; first < npaths; first += GEMM_PACK_MAX / 2) {
-    const int n = std::min(GEMM_PACK_MAX / 2, npaths - first);
-    if (int rc = pack_wih<N>(c, run.st, first, n, run.ws + run.pl.wih + (size_t)first * 2 * (4 * LSTM_H * N))) return rc;
-  }
-  run.packed_wih = true;
-  return DPTNAV_OK;
-}
-
-// fragment-order copies of the attention in-projection weights of paths [first, first + n) -> dst[(path - first)][384 x 128]
-// (gemm_t.hip, training forward)
-static int pack_inw(dptnav_ctx* c, hipStream_t st, int first, int n, float* dst) {
-  GemmPackArgs a;
-  for (int i = 0; i < GEMM_PACK_MAX; ++i) a.src[i] = nullptr;
-  if (n > GEMM_PACK_MAX) return c->fail(DPTNAV_ERR_INVALID, "W_in pack: %d paths in one launch", n);
-  for (int i = 0; i < n; ++i) a.src[i] = c->pw[first + i].in_w;
-  a.rows = 3 * 128;
-  a.K = 128;
-  hipLaunchKernelGGL(gemm_pack_rows_kernel, dim3(16, n), dim3(256), 0, st, a, dst);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "W_in pack: %s", hipGetErrorString(e));
-  return DPTNAV_OK;
-}
-static int pack_inw_all(dptnav_ctx* c, Run& run) {
-  if (!c->opt_gemm_t || c->cfg.num_features != 128 || c->cfg.arch != 0) return DPTNAV_OK;
-  const int npaths = 2 * c->cfg.num_blocks;
-  for (int first = 0; first < npaths; first += GEMM_PACK_MAX) {
-    const int n = std::min(GEMM_PACK_MAX, npaths - first);
-    if (int rc = pack_inw(c, run.st, first, n, run.ws + run.pl.winp + (size_t)first * 3 * 128 * 128)) return rc;
-  }
-  run.packed_inw = true;
-  return DPTNAV_OK;
-}
-
-// fcln.hip for one Linear (+ LayerNorm) launch.  Returns 1 when the launch went out, 0 when fcln_launch does not take the shape
-// (hipErrorInvalidValue, fcln.h: the caller then uses the GEMM engine; the sticky error is cleared), a negative DPTNAV error otherwise.
-static int try_fcln(dptnav_ctx* c, hipStream_t st, const FclnArgs& fa, int cat, const char* what) {
-  if (int rc = inject_failure(c, what)) return rc < 0 ? rc : -rc;
-  ProfScope ps(c, cat, st);
-  const int rc = fcln_launch(st, fa, c->num_cus);
-  if (rc == 0) return 1;
-  if (rc == (int)hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  const int e = c->fail(DPTNAV_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
-  return e < 0 ? e : -e;
-}
-
-// dgrad_t.hip for one wide data-gradient launch (out = addend + A W, kin = 512 or 384; option dgrad_t).  `Wpacked`: the
-// fragment-order copy pack_bwd_weights made on the same stream.  Returns like try_fcln: 1 launched, 0 not taken (the caller uses the
-// GEMM engine), negative DPTNAV error.
-static int try_dgrad_t(dptnav_ctx* c, Run& run, int cat, const char* what, const float* A, int lda, int kin, const float* Wpacked,
-                       const float* addend, float* out, int64_t M) {
-  if (!c->opt_dgrad_t) return 0;
-  if (int rc = inject_failure(c, what)) return rc < 0 ? rc : -rc;
-  if (run.slot + 1 > QUEUE_SLOTS) {
-    const int e = c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    return e < 0 ? e : -e;
-  }
-  DgradTArgs a;
-  a.A = A; a.lda = lda; a.W = Wpacked; a.addend = addend; a.out = out; a.M = M; a.kin = kin;
-  unsigned* const queue = run.take_queue(1);
-  a.queue = c->opt_deterministic ? nullptr : queue;
-  ProfScope ps(c, cat, run.st);
-  const int rc = dgrad_t_launch(run.st, a, c->num_cus);
-  if (rc == 0) return 1;
-  if (rc == (int)hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    run.slot -= 1;
-    return 0;
-  }
-  const int e = c->fail(DPTNAV_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
-  return e < 0 ? e : -e;
-}
-// Fragment-order weight copies the backward's dedicated kernels read (dgrad_t.hip, dgrad_r.hip): one slot of BWD_PACK_FLOATS per
-// path in the backward workspace -- [W_ih fwd | W_ih rev | in_proj_weight | out_proj.weight | ffn.1.weight].  dptnav_train_backward
-// fills the slots of ALL paths with four launches at its start (weights change every step, so once per step); the path-level entry
-// point packs the one path it runs into slot 0.  (Packed where they are used -- two to four 10-us launches in front of every
-// data-gradient launch -- they were 120 launches and 0.6 ms of each stream's chain per step.)
+// ---- weight packs ---------------------------------------------------------------------------------
+// One PACK_BWD slot: [W_ih fwd | W_ih rev | in_proj_weight | out_proj.weight | ffn.1.weight].  dptnav_train_backward fills the
+// slots of ALL paths at its start (weights change every step, so once per step).  (Packed where they are used -- two to four
+// 10-us launches in front of every data-gradient launch -- they were 120 launches and 0.6 ms of each stream's chain per step.)
 constexpr size_t BWD_PACK_WIH = 0, BWD_PACK_INW = (size_t)2 * 512 * 128, BWD_PACK_OUTW = BWD_PACK_INW + (size_t)384 * 128,
                  BWD_PACK_FFNW = BWD_PACK_OUTW + (size_t)128 * 128, BWD_PACK_FLOATS = BWD_PACK_FFNW + (size_t)128 * 256;
-static int pack_bwd_weights(dptnav_ctx* c, hipStream_t st, int first, int n, float* dst) {      // paths [first, first + n) -> slots 0 .. n - 1
-  if (c->cfg.num_features != 128 || c->cfg.arch != 0 || (!c->opt_dgrad_t && !c->opt_dgrad_r)) return DPTNAV_OK;
-  if (2 * n > DGRAD_PACK_MAX || n > DGRAD_R_PACK_MAX) return c->fail(DPTNAV_ERR_INVALID, "backward weight pack: %d paths in one launch", n);
-  const float* src[DGRAD_PACK_MAX];
-  long long off[DGRAD_PACK_MAX];
-  int rc = 0;
-  if (c->opt_dgrad_t) {
-    for (int i = 0; i < n; ++i) {
-      const PathWeights& w = c->pw[first + i];
-      src[2 * i] = w.w_ih[0];
-      src[2 * i + 1] = w.ndir == 2 ? w.w_ih[1] : nullptr;
-      off[2 * i] = (long long)(i * BWD_PACK_FLOATS + BWD_PACK_WIH);
-      off[2 * i + 1] = off[2 * i] + 512 * 128;
-    }
-    rc = dgrad_t_pack_launch(st, src, off, 2 * n, 512, dst);
-    for (int i = 0; i < n && rc == 0; ++i) {
-      src[i] = c->pw[first + i].in_w;
-      off[i] = (long long)(i * BWD_PACK_FLOATS + BWD_PACK_INW);
-    }
-    if (rc == 0) rc = dgrad_t_pack_launch(st, src, off, n, 384, dst);
+
+inline size_t pack_slot_floats(const dptnav_ctx* c, PackKind kind) {   // one path's slot
+  const size_t N = (size_t)c->cfg.num_features;
+  switch (kind) {
+    case PACK_ATTN: return ATTN_PACK_FLOATS;
+    case PACK_WIH: return 2 * (4 * LSTM_H * N);
+    case PACK_INW: return 3 * N * N;
+    case PACK_WHH4: return (size_t)2 * (4 * LSTM_H * LSTM_H);
+    case PACK_X16: return 2 * lstm16x_pack_floats((int)N);
+    default: return BWD_PACK_FLOATS;
   }
-  if (rc == 0 && c->opt_dgrad_r) {
-    for (int i = 0; i < n; ++i) {
-      src[i] = c->pw[first + i].out_w;
-      off[i] = (long long)(i * BWD_PACK_FLOATS + BWD_PACK_OUTW);
-    }
-    rc = dgrad_r_pack_launch(st, src, off, n, 128, dst);
-    for (int i = 0; i < n; ++i) {
-      const PathWeights& w = c->pw[first + i];
-      src[i] = w.ndir == 2 ? w.ffn_w : nullptr;      // [128][256] only with both directions
-      off[i] = (long long)(i * BWD_PACK_FLOATS + BWD_PACK_FFNW);
-    }
-    if (rc == 0) rc = dgrad_r_pack_launch(st, src, off, n, 256, dst);
+}
+inline int pack_paths_per_launch(PackKind kind, int n) {
+  static_assert(2 * (DGRAD_R_PACK_MAX / 2) <= DGRAD_PACK_MAX, "PACK_BWD: two W_ih per path in one dgrad_t pack launch");
+  switch (kind) {
+    case PACK_ATTN: return n;
+    case PACK_WIH: return GEMM_PACK_MAX / 2;
+    case PACK_INW: return GEMM_PACK_MAX;
+    case PACK_WHH4: return LSTM4_PACK_MAX / 2;
+    case PACK_X16: return LSTM16X_PACK_MAX / 2;
+    default: return DGRAD_R_PACK_MAX / 2;
   }
-  if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "backward weight pack: %s", hipGetErrorString((hipError_t)rc));
+}
+
+// Source pointers of paths [first, first + n): one per path (W_IN, W_OUT, W_FFN2) or one per path and direction, [2 * i + dir]
+// (the LSTM tensors).  What a unidirectional path does not have is nullptr, which every pack kernel skips: the reverse
+// direction, and ffn.1.weight as the [N][256] matrix the packs hold (with one direction it is [N][128]).
+enum WeightId { W_IN, W_OUT, W_FFN2, W_IH, W_HH, B_IH, B_HH };
+static std::vector<const float*> gather(const dptnav_ctx* c, WeightId id, int first, int n) {
+  std::vector<const float*> out((size_t)(id >= W_IH ? 2 * n : n));
+  for (int i = 0; i < n; ++i) {
+    const PathWeights& w = c->pw[first + i];
+    const bool two = w.ndir == 2;
+    if (id == W_IN) out[i] = w.in_w;
+    else if (id == W_OUT) out[i] = w.out_w;
+    else if (id == W_FFN2) out[i] = two ? w.ffn_w : nullptr;
+    else {
+      const float* const* m = id == W_IH ? w.w_ih : id == W_HH ? w.w_hh : id == B_IH ? w.b_ih : w.b_hh;
+      out[2 * i] = m[0];
+      out[2 * i + 1] = two ? m[1] : nullptr;
+    }
+  }
+  return out;
+}
+
+// The pack of `kind` for paths [first, first + n) -> dst[path - first], from the weights as they are NOW (an optimizer may
+// have stepped since the last call).
+static int pack_paths(dptnav_ctx* c, hipStream_t st, PackKind kind, int first, int n, float* dst) {
+  const int N = c->cfg.num_features;
+  const int per = pack_paths_per_launch(kind, n);
+  const char* what = "";
+  int rc = 0;   // hipError_t of the pack launches
+  for (int at = 0; at < n && rc == 0; at += per, dst += (size_t)per * pack_slot_floats(c, kind)) {
+    const int f = first + at, m = std::min(per, n - at);
+    switch (kind) {
+      case PACK_ATTN: {
+        what = "attention weight pack";
+        const auto in = gather(c, W_IN, f, m), out = gather(c, W_OUT, f, m), ffn = gather(c, W_FFN2, f, m);
+        std::vector<AttnPackSrc> src((size_t)m);
+        for (int i = 0; i < m; ++i) src[(size_t)i] = AttnPackSrc{in[i], out[i], ffn[i]};
+        rc = attn_pack_launch(st, src.data(), m, dst);
+        break;
+      }
+      case PACK_WIH:
+      case PACK_INW: {
+        what = kind == PACK_WIH ? "W_ih pack" : "W_in pack";
+        const auto src = gather(c, kind == PACK_WIH ? W_IH : W_IN, f, m);
+        GemmPackArgs a{};
+        std::copy(src.begin(), src.end(), a.src);
+        a.rows = kind == PACK_WIH ? 4 * LSTM_H : 3 * N;
+        a.K = N;
+        hipLaunchKernelGGL(gemm_pack_rows_kernel, dim3(16, (unsigned)src.size()), dim3(256), 0, st, a, dst);
+        rc = (int)hipGetLastError();
+        break;
+      }
+      case PACK_WHH4:
+        what = "lstm4 W_hh pack";
+        rc = lstm4_pack_launch(st, gather(c, W_HH, f, m).data(), 2 * m, dst);
+        break;
+      case PACK_X16:
+        what = "lstm16x weight pack";
+        rc = lstm16x_pack_launch(N, st, gather(c, W_IH, f, m).data(), gather(c, W_HH, f, m).data(), gather(c, B_IH, f, m).data(),
+                                 gather(c, B_HH, f, m).data(), 2 * m, dst);
+        break;
+      default: {   // PACK_BWD: the segments dgrad_t.hip reads (two W_ih, in_proj_weight), then those dgrad_r.hip reads
+        what = "backward weight pack";
+        if (N != 128 || c->cfg.arch != 0) return DPTNAV_OK;
+        std::vector<long long> off((size_t)2 * m);
+        auto slots = [&](size_t segment, int per_path) {   // source j -> slot j / per_path, its segment (the reverse W_ih 512 x 128 further)
+          for (int j = 0; j < per_path * m; ++j)
+            off[(size_t)j] = (long long)((size_t)(j / per_path) * BWD_PACK_FLOATS + segment + (size_t)(j % per_path) * 512 * 128);
+          return off.data();
+        };
+        if (c->opt_dgrad_t) {
+          rc = dgrad_t_pack_launch(st, gather(c, W_IH, f, m).data(), slots(BWD_PACK_WIH, 2), 2 * m, 512, dst);
+          if (rc == 0) rc = dgrad_t_pack_launch(st, gather(c, W_IN, f, m).data(), slots(BWD_PACK_INW, 1), m, 384, dst);
+        }
+        if (rc == 0 && c->opt_dgrad_r) {
+          rc = dgrad_r_pack_launch(st, gather(c, W_OUT, f, m).data(), slots(BWD_PACK_OUTW, 1), m, 128, dst);
+          if (rc == 0) rc = dgrad_r_pack_launch(st, gather(c, W_FFN2, f, m).data(), slots(BWD_PACK_FFNW, 1), m, 256, dst);
+        }
+      }
+    }
+  }
+  if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
   return DPTNAV_OK;
 }
 
-// dgrad_r.hip for one K = 128 data gradient with its weight / bias gradient riding (option dgrad_r): `wpacked` from pack_bwd_weights;
-// leaves the partial tiles in `slab` / `colslab` and their number in *grid.  Returns like try_fcln.
-static int try_dgrad_r(dptnav_ctx* c, Run& run, int cat, const char* what, const float* A, const float* wpacked, int nout, bool gate,
-                       const float* X, float* out, int64_t M, float* slab, float* colslab, int max_slabs, int* grid) {
-  if (!c->opt_dgrad_r) return 0;
-  if (int rc = inject_failure(c, what)) return rc < 0 ? rc : -rc;
-  if (run.slot + 1 > QUEUE_SLOTS) {
-    const int e = c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    return e < 0 ? e : -e;
+// *out = path p's pack of `kind` inside `base`.  Unless the pass holds the kind for all paths already it is made here, on the
+// stream, immediately in front of the launch that asked: this path into its own slot (PACK_ATTN, PACK_WIH), this path into
+// slot 0 (PACK_INW, PACK_BWD), or every path (the recurrences' PACK_WHH4 / PACK_X16: once per pass, at the first launch that
+// reads them).
+static int pack_for(dptnav_ctx* c, hipStream_t st, PackKind kind, bool* all_paths, float* base, int p, float** out) {
+  *out = base + (size_t)p * pack_slot_floats(c, kind);
+  if (all_paths[kind]) return DPTNAV_OK;
+  switch (kind) {
+    case PACK_ATTN:
+    case PACK_WIH: return pack_paths(c, st, kind, p, 1, *out);
+    case PACK_INW:
+    case PACK_BWD: *out = base; return pack_paths(c, st, kind, p, 1, base);
+    default: all_paths[kind] = true; return pack_paths(c, st, kind, 0, (int)c->pw.size(), base);
   }
-  DgradRArgs a;
-  a.A = A; a.Wpacked = wpacked; a.X = X; a.out = out; a.M = M; a.nout = nout; a.relu_gate = gate;
-  a.slab = slab; a.colslab = colslab; a.max_slabs = max_slabs;
-  unsigned* const queue = run.take_queue(1);
-  a.queue = c->opt_deterministic ? nullptr : queue;
-  ProfScope ps(c, cat, run.st);
-  const int rc = dgrad_r_launch(run.st, a, c->num_cus, grid);
-  if (rc == 0) return 1;
-  run.slot -= 1;
-  if (rc == (int)hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    return 0;
+}
+inline float* pack_base(const Run& run, PackKind kind) {
+  const size_t at[PACK_KINDS] = {run.pl.wpack, run.pl.wih, run.pl.winp, run.pl.whh4, run.pl.x16pack, 0};
+  return run.ws + at[kind];
+}
+static int run_pack(dptnav_ctx* c, Run& run, PackKind kind, int p, float** out) {
+  return pack_for(c, run.lane.st, kind, run.all_paths, pack_base(run, kind), p, out);
+}
+// every path of the model, once per pass and sub-batch (dptnav_forward, dptnav_train_forward)
+static int pack_all(dptnav_ctx* c, Run& run, PackKind kind) {
+  run.all_paths[kind] = true;
+  return pack_paths(c, run.lane.st, kind, 0, (int)c->pw.size(), pack_base(run, kind));
+}
+
+// ---- dedicated kernels in front of the GEMM engine --------------------------------------------------
+// One attempt at a dedicated kernel (fcln.hip, gemm_t.hip, dgrad_t.hip, dgrad_r.hip) for a product the GEMM engine can also
+// form.  `launch(queue)` returns the hipError_t of its *_launch function; queue is the launch's ticket counter (needs_ticket;
+// nullptr under option deterministic, the counter is consumed all the same).  *took: the launch went out.  Not taken -- the
+// kernel does not do this shape (hipErrorInvalidValue, see the kernels' headers) -- is no error: the sticky error is cleared,
+// the ticket goes back and the caller launches the engine.
+template <class Launch>
+int try_dedicated(dptnav_ctx* c, Lane& lane, int cat, const char* what, bool needs_ticket, Launch&& launch, bool* took) {
+  *took = false;
+  if (int rc = inject_failure(c, what)) return rc;
+  unsigned* queue = nullptr;
+  if (needs_ticket && !(queue = lane.tk.take(1))) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
+  ProfScope ps(c, cat, lane.st);
+  const int rc = launch(c->opt_deterministic ? nullptr : queue);
+  if (rc == 0) {
+    *took = true;
+    return DPTNAV_OK;
   }
-  const int e = c->fail(DPTNAV_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
-  return e < 0 ? e : -e;
+  if (needs_ticket) lane.tk.give_back(1);
+  if (rc != (int)hipErrorInvalidValue) return c->fail(DPTNAV_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
+  (void)hipGetLastError();
+  return DPTNAV_OK;
+}
+// fcln.hip for one Linear (+ LayerNorm) launch
+static int try_fcln(dptnav_ctx* c, Lane& lane, const FclnArgs& fa, int cat, const char* what, bool* took) {
+  return try_dedicated(c, lane, cat, what, false, [&](unsigned*) { return fcln_launch(lane.st, fa, c->num_cus); }, took);
+}
+// dgrad_t.hip for one wide data-gradient launch (out = addend + A W, kin = 512 or 384); a.W from PACK_BWD, made on the same stream
+static int try_dgrad_t(dptnav_ctx* c, Lane& lane, int cat, const char* what, DgradTArgs a, bool* took) {
+  return try_dedicated(c, lane, cat, what, true, [&](unsigned* q) { a.queue = q; return dgrad_t_launch(lane.st, a, c->num_cus); }, took);
+}
+// dgrad_r.hip for one K = 128 data gradient with its weight / bias gradient riding; a.Wpacked from PACK_BWD; leaves the partial
+// tiles in a.slab / a.colslab and their number in *grid
+static int try_dgrad_r(dptnav_ctx* c, Lane& lane, int cat, const char* what, DgradRArgs a, int* grid, bool* took) {
+  return try_dedicated(c, lane, cat, what, true, [&](unsigned* q) { a.queue = q; return dgrad_r_launch(lane.st, a, c->num_cus, grid); }, took);
 }
 
 template <int N>
@@ -756,7 +789,8 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
              const PathBufs* bufs = nullptr, int chain = 0) {
   float* ws = run.ws;
   const Plan& pl = run.pl;
-  hipStream_t st = run.st;
+  Lane& lane = run.lane;
+  hipStream_t st = lane.st;
   const PathBufs pb = bufs ? *bufs : inference_bufs(run);
   constexpr int WR = N == 128 ? 1 : 2, WC = N == 128 ? 4 : 2, GROUP = N / 4, DH = N / 4;
   constexpr int BM = 32 * WR;
@@ -792,20 +826,16 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
       const PathWeights& pw = c->pw[2 * block + path - 1];
       pro = AttnFfnPrologue{hc, pw.ffn_w, pw.ffn_b, pw.ln2_w, pw.ln2_b};
     }
-    const float* wpack = nullptr;
+    float* wpack = nullptr;
     if (!c->opt_split_bf16) {
-      float* pk = ws + pl.wpack + (size_t)(2 * block + path) * ATTN_PACK_FLOATS;
-      if (!run.packed) {   // stage entry points: this path only (dptnav_forward packs all paths in one launch)
-        if (int rc = pack_attn_weights(c, st, 2 * block + path, 1, pk)) return rc;
-      }
-      wpack = pk;
-      if (chain & CHAIN_PRO) pro.wf = pk - ATTN_PACK_FLOATS + ATTN_PACK_IN + ATTN_PACK_OUT;   // previous path's ffn.1 segment
+      if (int rc = run_pack(c, run, PACK_ATTN, 2 * block + path, &wpack)) return rc;
+      if (chain & CHAIN_PRO) pro.wf = wpack - ATTN_PACK_FLOATS + ATTN_PACK_IN + ATTN_PACK_OUT;   // previous path's ffn.1 segment
     }
     unsigned* seq_queue = nullptr;      // persistent form: one sequence-ticket counter of the pass (zeroed with the GEMM engine's, begin_run)
     // (1: only where a workgroup gets more than one sequence -- measured equal at best below that)
     if (c->opt_attn_v2 && !c->opt_split_bf16 && (chain & CHAIN_PRO) && (c->opt_attn_persist > 1 || (c->opt_attn_persist == 1 && geom.nseq > c->num_cus))) {
-      if (run.slot + 1 > QUEUE_SLOTS) return c->fail(DPTNAV_ERR_INVALID, "attention block: ticket counters exhausted");
-      seq_queue = run.take_queue(1);
+      seq_queue = lane.tk.take(1);
+      if (!seq_queue) return c->fail(DPTNAV_ERR_INVALID, "attention block: ticket counters exhausted");
     }
     const int rc = (c->opt_attn_v2 && !c->opt_split_bf16)
                        ? attn_block2_launch(st, x_in, w.in_b, w.out_b, w.ln1_w, w.ln1_b, y1, geom, (chain & CHAIN_PRO) ? &pro : nullptr, wpack, seq_queue,
@@ -818,29 +848,20 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
   }
   // K1: qkv = x W_in^T + b_in                                  (nn.MultiheadAttention in-projection)
   if (dptn && !fused) {
-    int done = 0;
+    bool done = false;
     if constexpr (N == 128) {
-      if (pb.train && c->opt_gemm_t) {      // training forward: gemm_t.hip on the fragment-order copy of W_in (packed here, on the stream)
-        if (int rc = inject_failure(c, "qkv gemm")) return rc;
-        if (run.slot + 1 > QUEUE_SLOTS) return c->fail(DPTNAV_ERR_INVALID, "qkv gemm: ticket counters exhausted");
-        float* wp = ws + pl.winp + (run.packed_inw ? (size_t)(2 * block + path) * 3 * N * N : 0);
-        if (!run.packed_inw)
-          if (int rc = pack_inw(c, st, 2 * block + path, 1, wp)) return rc;
-        GemmTArgs ga;
-        ga.A = x_in; ga.Wpacked = wp; ga.bias = w.in_b; ga.out = qkv; ga.M = M; ga.nout = 3 * N;
-        unsigned* const queue = run.take_queue(1);
-        ga.queue = c->opt_deterministic ? nullptr : queue;
-        ProfScope ps(c, CAT_QKV, st);
-        const int rc = gemm_t_launch(st, ga, c->num_cus);
-        if (rc == 0) done = 1;
-        else if (rc == (int)hipErrorInvalidValue) { (void)hipGetLastError(); run.slot -= 1; }
-        else return c->fail(DPTNAV_ERR_HIP, "qkv gemm: %s", hipGetErrorString((hipError_t)rc));
+      if (pb.train && c->opt_gemm_t) {      // training forward: gemm_t.hip on the fragment-order copy of W_in
+        float* wp = nullptr;
+        if (int rc = run_pack(c, run, PACK_INW, 2 * block + path, &wp)) return rc;
+        GemmTArgs ga{x_in, wp, w.in_b, qkv, M, 3 * N};
+        auto launch = [&](unsigned* q) { ga.queue = q; return gemm_t_launch(st, ga, c->num_cus); };
+        if (int rc = try_dedicated(c, lane, CAT_QKV, "qkv gemm", true, launch, &done)) return rc;
       }
     }
     if (!done) {
       ALoadDense al{x_in, M, N, BM};
       EpiBiasStore ep{qkv, w.in_b, M, 3 * N, BM, 3 * N};
-      if (int rc = launch_gemm<N, 3, WR, WC>(c, run, CAT_QKV, "qkv gemm", w.in_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<N, 3, WR, WC>(c, lane, CAT_QKV, "qkv gemm", w.in_w, ntiles, 1, al, ep)) return rc;
     }
   }
   // K2: softmax(Q K^T / sqrt(dh)) V per (sequence, head)
@@ -855,19 +876,17 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
     {
       if (pb.train && pb.zn1 && N == 128 && c->opt_fcln) {   // 16-token tiles, three workgroups per CU (fcln.hip)
         FclnArgs fa{att, w.out_w, w.out_b, w.ln1_w, w.ln1_b, x_in, y1, pb.zn1, pb.rs1, M, N, N, /*pre_res*/ true, /*act*/ 0};
-        const int r = try_fcln(c, st, fa, CAT_OUTPROJ, "fcln (out-projection)");
-        if (r < 0) return -r;
-        done = r > 0;
+        if (int rc = try_fcln(c, lane, fa, CAT_OUTPROJ, "fcln (out-projection)", &done)) return rc;
       }
       if (!done && pb.train && pb.zn1) {   // + zn / rstd on the tape for the LayerNorm backward
         EpiBiasResLNSave<GROUP> ep{y1, w.out_b, x_in, w.ln1_w, w.ln1_b, M, N, BM, pb.zn1, pb.rs1};
-        if (int rc = launch_gemm<N, 1, WR, WC>(c, run, CAT_OUTPROJ, "out-proj gemm (tape)", w.out_w, ntiles, 1, al, ep)) return rc;
+        if (int rc = launch_gemm<N, 1, WR, WC>(c, lane, CAT_OUTPROJ, "out-proj gemm (tape)", w.out_w, ntiles, 1, al, ep)) return rc;
         done = true;
       }
     }
     if (!done) {
       EpiBiasResLN<GROUP> ep{y1, w.out_b, x_in, w.ln1_w, w.ln1_b, M, N, BM};
-      if (int rc = launch_gemm<N, 1, WR, WC>(c, run, CAT_OUTPROJ, "out-proj gemm", w.out_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<N, 1, WR, WC>(c, lane, CAT_OUTPROJ, "out-proj gemm", w.out_w, ntiles, 1, al, ep)) return rc;
     }
   }
   const int nst16 = (geom.nseq + 15) / 16;
@@ -899,25 +918,24 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
     const float *wih0 = w.w_ih[0], *wih1 = w.w_ih[1];
     int ldw_ih = N;
     if (c->opt_pack_wih && !split) {
-      float* pk = ws + pl.wih + (size_t)(2 * block + path) * 2 * (4 * LSTM_H * N);
-      if (!run.packed_wih)
-        if (int rcp = pack_wih<N>(c, st, 2 * block + path, 1, pk)) return rcp;
+      float* pk = nullptr;
+      if (int rcp = run_pack(c, run, PACK_WIH, 2 * block + path, &pk)) return rcp;
       wih0 = pk;
       wih1 = pk + 4 * LSTM_H * N;
       ldw_ih = 0;
     }
     if (use16 && split) {   // opt-in split-precision mode (bf16 hi/lo operands, fp32 accumulation)
       EpiLstmPre16 ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom, nst16};
-      rc = launch_gemm<N, 4, 1, 4, false, true>(c, run, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
+      rc = launch_gemm<N, 4, 1, 4, false, true>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
     } else if (use16) {
       EpiLstmPre16 ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom, nst16};
-      rc = launch_gemm<N, 4, 1, 4>(c, run, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
+      rc = launch_gemm<N, 4, 1, 4>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
     } else if (split) {
       EpiLstmPre ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom};
-      rc = launch_gemm<N, 4, 1, 4, false, true>(c, run, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
+      rc = launch_gemm<N, 4, 1, 4, false, true>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
     } else {
       EpiLstmPre ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom};
-      rc = launch_gemm<N, 4, 1, 4>(c, run, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
+      rc = launch_gemm<N, 4, 1, 4>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
     }
     if (rc) return rc;
   }
@@ -925,30 +943,9 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
   if (run.lstm_wait && hipStreamWaitEvent(st, run.lstm_wait, 0) != hipSuccess)
     return c->fail(DPTNAV_ERR_HIP, "lstm stagger wait");
   if (usex) {
-    const float* xpack = nullptr;
-    if (c->opt_lstm_prologue) {
-      float* base = ws + pl.x16pack;
-      if (!run.packed_x16) {   // first fused recurrence of this pass: copy every path's weights as they are now, LSTM16X_PACK_MAX matrix sets per launch
-        const int nmat = 2 * (int)c->pw.size();
-        for (int first = 0; first < nmat; first += LSTM16X_PACK_MAX) {
-          const float *s_ih[LSTM16X_PACK_MAX], *s_hh[LSTM16X_PACK_MAX], *s_bi[LSTM16X_PACK_MAX], *s_bh[LSTM16X_PACK_MAX];
-          const int n = std::min(LSTM16X_PACK_MAX, nmat - first);
-          for (int i = 0; i < n; ++i) {
-            const PathWeights& q = c->pw[(size_t)(first + i) / 2];
-            const int dir = (first + i) & 1;
-            const bool have = dir == 0 || q.ndir == 2;
-            s_ih[i] = have ? q.w_ih[dir] : nullptr;
-            s_hh[i] = have ? q.w_hh[dir] : nullptr;
-            s_bi[i] = have ? q.b_ih[dir] : nullptr;
-            s_bh[i] = have ? q.b_hh[dir] : nullptr;
-          }
-          const int rcp = lstm16x_pack_launch(N, st, s_ih, s_hh, s_bi, s_bh, n, base + (size_t)first * lstm16x_pack_floats(N));
-          if (rcp != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16x weight pack: %s", hipGetErrorString((hipError_t)rcp));
-        }
-        run.packed_x16 = true;
-      }
-      xpack = base + (size_t)(2 * (2 * block + path)) * lstm16x_pack_floats(N);
-    }
+    float* xpack = nullptr;
+    if (c->opt_lstm_prologue)
+      if (int rcp = run_pack(c, run, PACK_X16, 2 * block + path, &xpack)) return rcp;
     ProfScope ps(c, CAT_LSTM, st);
     const int rc = lstm16x_launch(N, dptn, nst16, w.ndir, st, lstm_in, N, w.w_ih, w.b_ih, w.b_hh, w.w_hh, hc, w.ndir * LSTM_H,
                                   M, geom, c->opt_lstm_sched, xpack);
@@ -959,20 +956,11 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
     if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16s: %s", hipGetErrorString((hipError_t)rc));
   } else if (use4) {
     const float *whh0 = w.w_hh[0], *whh1 = w.w_hh[1];
-    if (c->opt_pack_whh && 2 * (int)c->pw.size() <= LSTM4_PACK_MAX) {
-      float* base = ws + pl.whh4;
-      if (!run.packed_whh4) {   // first 4-sequence recurrence of this pass: copy every path's W_hh, one launch
-        const float* src[LSTM4_PACK_MAX];
-        for (size_t i = 0; i < c->pw.size(); ++i) {
-          src[2 * i] = c->pw[i].w_hh[0];
-          src[2 * i + 1] = c->pw[i].ndir == 2 ? c->pw[i].w_hh[1] : nullptr;
-        }
-        const int rcp = lstm4_pack_launch(st, src, 2 * (int)c->pw.size(), base);
-        if (rcp != 0) return c->fail(DPTNAV_ERR_HIP, "lstm4 W_hh pack: %s", hipGetErrorString((hipError_t)rcp));
-        run.packed_whh4 = true;
-      }
-      whh0 = base + (size_t)(2 * (2 * block + path)) * (4 * LSTM_H * LSTM_H);
-      whh1 = whh0 + 4 * LSTM_H * LSTM_H;
+    if (c->opt_pack_whh && 2 * (int)c->pw.size() <= LSTM4_PACK_MAX) {   // (the pack is one launch)
+      float* pk = nullptr;
+      if (int rcp = run_pack(c, run, PACK_WHH4, 2 * block + path, &pk)) return rcp;
+      whh0 = pk;
+      whh1 = pk + 4 * LSTM_H * LSTM_H;
     }
     ProfScope ps(c, CAT_LSTM, st);
     const int rc = lstm4_launch(c->cfg.arch == 0, nst4, nst16, w.ndir, st, pre, whh0, whh1, hc,
@@ -1009,29 +997,28 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
     EpiBiasLNRes<GROUP> ep{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM};
     if (w.ndir == 2 && split) {
       ALoadDense al{hc, M, 2 * LSTM_H, BM};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, run, CAT_FFN, "fc gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, lane, CAT_FFN, "fc gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
     } else if (w.ndir == 2 && pb.train && pb.zn2) {   // + zn / rstd on the tape for the LayerNorm backward
       ALoadDense al{hc, M, 2 * LSTM_H, BM};
       EpiBiasLNResSave<GROUP> eps{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
+      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
     } else if (w.ndir == 2) {
-      int r = 0;
+      bool done = false;
       if (N == 64 && c->opt_fcln) {     // 16-token tiles, several workgroups per CU (fcln.hip)
         FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, x_in, x_out, nullptr, nullptr, M, 2 * LSTM_H, N, /*pre_res*/ false, /*act*/ 0, c->opt_fcln == 2 ? 3 : 2};
-        r = try_fcln(c, st, fa, CAT_FFN, "fcln (fc)");
-        if (r < 0) return -r;
+        if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (fc)", &done)) return rc;
       }
-      if (r == 0) {
+      if (!done) {
         ALoadDense al{hc, M, 2 * LSTM_H, BM};
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
       }
     } else if (pb.train && pb.zn2) {
       ALoadDense al{hc, M, LSTM_H, BM};
       EpiBiasLNResSave<GROUP> eps{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
+      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
     } else {
       ALoadDense al{hc, M, LSTM_H, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
     }
     return DPTNAV_OK;
   }
@@ -1042,46 +1029,43 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
     // (training keeps the raw h on the tape and applies ffn[0] = ReLU while loading)
     if (w.ndir == 2 && split) {
       ALoadCols al{hc, M, 2 * LSTM_H, 0, BM};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, run, CAT_FFN, "ffn gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, lane, CAT_FFN, "ffn gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
     } else if (w.ndir == 2 && pb.train) {
       ALoadColsReLU al{hc, M, 2 * LSTM_H, 0, BM};
       bool done = false;
       {
         if (pb.zn2 && N == 128 && c->opt_fcln) {     // ReLU while loading, 16-token tiles, two workgroups per CU (fcln.hip)
           FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, y1, x_out, pb.zn2, pb.rs2, M, 2 * LSTM_H, N, /*pre_res*/ true, /*act: ReLU*/ 1};
-          const int r = try_fcln(c, st, fa, CAT_FFN, "fcln (ffn)");
-          if (r < 0) return -r;
-          done = r > 0;
+          if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (ffn)", &done)) return rc;
         }
         if (!done && pb.zn2) {
           EpiBiasResLNSave<GROUP> eps{x_out, w.ffn_b, y1, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-          if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
+          if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
           done = true;
         }
       }
       if (!done)
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
     } else if (w.ndir == 2) {
-      int r = 0;
+      bool done = false;
       if (c->opt_fcln) {       // (the paths whose FFN does not ride in the next attention block; hc = ReLU(h) already)
         FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, y1, x_out, nullptr, nullptr, M, 2 * LSTM_H, N, /*pre_res*/ true, /*act*/ 0};
-        r = try_fcln(c, st, fa, CAT_FFN, "fcln (ffn)");
-        if (r < 0) return -r;
+        if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (ffn)", &done)) return rc;
       }
-      if (r == 0) {
+      if (!done) {
         ALoadCols al{hc, M, 2 * LSTM_H, 0, BM};
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
       }
     } else if (pb.train && pb.zn2) {
       ALoadColsReLU al{hc, M, LSTM_H, 0, BM};
       EpiBiasResLNSave<GROUP> eps{x_out, w.ffn_b, y1, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
+      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
     } else if (pb.train) {
       ALoadColsReLU al{hc, M, LSTM_H, 0, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
     } else {
       ALoadCols al{hc, M, LSTM_H, 0, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, run, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
     }
   }
   return DPTNAV_OK;
@@ -1092,7 +1076,7 @@ int run_head(dptnav_ctx* c, Run& run, const float* mix, const float* e1, const f
              float* E, float* X, float* vidbuf = nullptr) {
   float* ws = run.ws;
   const Plan& pl = run.pl;
-  hipStream_t st = run.st;
+  hipStream_t st = run.lane.st;
   const dptnav_config& g = c->cfg;
   const float* vid = nullptr;
   if (!g.audio_only) {
@@ -1118,24 +1102,24 @@ int run_tail(dptnav_ctx* c, Run& run, const float* x, const float* E, int B, int
              float* Zbuf = nullptr) {
   float* ws = run.ws;
   const Plan& pl = run.pl;
-  hipStream_t st = run.st;
+  Lane& lane = run.lane;
+  hipStream_t st = lane.st;
   constexpr int WR = N == 128 ? 1 : 2, WC = N == 128 ? 4 : 2, GROUP = N / 4;
   constexpr int BM = 32 * WR;
   const dptnav_config& g = c->cfg;
   float *Z = Zbuf ? Zbuf : ws + pl.qkv, *D = ws + pl.att;
   const int64_t M = pl.M;
   // T1: Z = PReLU(x) W_sep^T + b_sep                            (dptn_wav.py:26-29,47)
-  int sep_done = 0;
+  bool sep_done = false;
   if (c->opt_fcln) {       // 16-token tiles, W_sep in registers, two or more workgroups per CU (fcln.hip, its plain form)
     FclnArgs fa{x, c->w("dprnn.speakers_separation.1.weight"), c->w("dprnn.speakers_separation.1.bias"), nullptr, nullptr, nullptr, Z, nullptr,
                 nullptr, M, N, 2 * N, /*pre_res*/ false, /*act: PReLU*/ 2, 2, /*layernorm*/ false, c->w("dprnn.speakers_separation.0.weight")};
-    sep_done = try_fcln(c, st, fa, CAT_SEP, "fcln (separation conv)");
-    if (sep_done < 0) return -sep_done;
+    if (int rc = try_fcln(c, lane, fa, CAT_SEP, "fcln (separation conv)", &sep_done)) return rc;
   }
   if (!sep_done) {
     ALoadDensePReLU al{x, c->w("dprnn.speakers_separation.0.weight"), M, N, 32};
     EpiBiasStore ep{Z, c->w("dprnn.speakers_separation.1.bias"), M, 2 * N, 32, 2 * N};
-    if (int rc = launch_gemm<N, N / 64, 1, 4>(c, run, CAT_SEP, "separation gemm",
+    if (int rc = launch_gemm<N, N / 64, 1, 4>(c, lane, CAT_SEP, "separation gemm",
                                               c->w("dprnn.speakers_separation.1.weight"), (M + 31) / 32, 1, al, ep))
       return rc;
   }
@@ -1169,7 +1153,7 @@ int run_tail(dptnav_ctx* c, Run& run, const float* x, const float* E, int B, int
     ALoadOla al{Z, N, B, (int)pl.L, (int)pl.S, g.chunk_size, g.step_size, left, ola, BM};
     EpiSkipDecoderTaps<GROUP> ep{D, c->w("dprnn.postprocessing.0.bias"), E, c->w("decoder.weight"),
                                  (int64_t)B * pl.L, g.kernel_size_enc, BM};
-    if (int rc = launch_gemm<N, 1, WR, WC>(c, run, CAT_POST, "postproc gemm", c->w("dprnn.postprocessing.0.weight"),
+    if (int rc = launch_gemm<N, 1, WR, WC>(c, lane, CAT_POST, "postproc gemm", c->w("dprnn.postprocessing.0.weight"),
                                            (rows + BM - 1) / BM, 1, al, ep))
       return rc;
   }
@@ -1253,7 +1237,7 @@ int make_bwd_plan(dptnav_ctx* c, int B, int S, BwdPlan* p, int64_t L = 0, int Tv
   p->dg3 = take((size_t)MD * 2 * 4 * H);
   p->slab2 = take((size_t)BWD_SLAB_WGS * 512 * 128);
   p->queue2 = take(QUEUE_SLOTS);
-  p->wiht = take(g.arch == 0 && N == 128 ? (size_t)2 * g.num_blocks * BWD_PACK_FLOATS : 0);      // pack_bwd_weights
+  p->wiht = take(g.arch == 0 && N == 128 ? (size_t)2 * g.num_blocks * BWD_PACK_FLOATS : 0);      // PACK_BWD
   p->lnp = take((size_t)BWD_LNP_WGS * 8 * N);      // LayerNorm (2N) or decoder-tap (8N) partials per workgroup
   p->dxa = take((size_t)M * N);                     // gradient ping-pong between paths
   p->dxb = take((size_t)M * N);
@@ -1271,36 +1255,36 @@ int make_bwd_plan(dptnav_ctx* c, int B, int S, BwdPlan* p, int64_t L = 0, int Tv
 }
 
 struct BwdRun {
-  float* ws;
-  BwdPlan pl;
-  hipStream_t st;
-  int slot;
-  float* const* gptr;                // where this run WRITES the parameter gradients (slot order)
+  float* ws = nullptr;
+  BwdPlan pl{};
+  Lane lane;                         // counters at pl.queue; dptnav_train_backward recycles them between paths (a path takes at most
+                                     // 40: N = 128: 18 GEMMs + 6 wgrad; N = 64 / DPRNN: <= 40)
+  float* const* gptr = nullptr;      // where this run WRITES the parameter gradients (slot order)
   int half = 0;
   hipEvent_t lstm_wait = nullptr;    // BPTT launches of the two halves of a split batch are chained like the forward's
   hipEvent_t lstm_record = nullptr;
-  // Side stream (option wgrad_side, split batches): nothing needs dW before the step ends, so the LSTM weight-gradient
-  // launches leave the half's chain and run whenever CUs are free -- in particular while this half waits for the other
-  // half's BPTT (8.9 ms per step with 114 CUs idle in the kernel timeline).  dP rotates through three buffers: the BPTT
-  // of path p-3 waits for the weight gradients of path p to have read theirs.
-  hipStream_t side = nullptr;
+  // Side stream (option wgrad_side, split batches; side.st == nullptr: none): nothing needs dW before the step ends, so the
+  // LSTM weight-gradient launches leave the half's chain and run whenever CUs are free -- in particular while this half waits
+  // for the other half's BPTT (8.9 ms per step with 114 CUs idle in the kernel timeline).  dP rotates through three buffers:
+  // the BPTT of path p-3 waits for the weight gradients of path p to have read theirs.  Its counters (pl.queue2) are its own:
+  // the main lane re-zeroes its region while side launches may be in flight.
+  Lane side;
   hipEvent_t ev_bptt = nullptr, ev_wg[3] = {nullptr, nullptr, nullptr};
   bool wg_pending[3] = {false, false, false};
-  int dg_sel = 0, side_slot = 0;
-  bool packed_all = false;           // ws + pl.wiht holds the fragment-order weight copies of ALL paths (dptnav_train_backward); else slot 0 = this path
-  unsigned* take_queue_side(int n) {   // own counters: the main stream re-zeroes its region while side launches may be in flight
-    if (side_slot + n > QUEUE_SLOTS) return nullptr;        // the caller fails the launch (as launch_gemm does for `slot`)
-    unsigned* q = reinterpret_cast<unsigned*>(ws + pl.queue2) + side_slot;
-    side_slot += n;
-    return q;
-  }
-  unsigned* take_queue(int n) {          // nullptr when the zeroed region is used up (the caller fails the launch): the
-    if (slot + n > QUEUE_SLOTS) return nullptr;   // backward recycles its counters per path while slot > QUEUE_SLOTS - 64, and a path takes
-    unsigned* q = reinterpret_cast<unsigned*>(ws + pl.queue) + slot;   // at most 40 (N = 128: 18 GEMMs + 6 wgrad; N = 64 / DPRNN: <= 40)
-    slot += n;
-    return q;
-  }
+  int dg_sel = 0;
+  bool all_paths[PACK_KINDS] = {};   // PACK_BWD: ws + pl.wiht holds the weight copies of ALL paths (dptnav_train_backward); else slot 0 = this path
 };
+
+// Start a backward pass on `st` over the backward workspace `ws`: zero its ticket counters (stream ordered).
+int begin_bwd_run(dptnav_ctx* c, BwdRun* br, float* ws, const BwdPlan& bp, hipStream_t st, float* const* gptr) {
+  *br = BwdRun{};
+  br->ws = ws;
+  br->pl = bp;
+  br->lane = Lane{st, Tickets{reinterpret_cast<unsigned*>(ws + bp.queue), 0}};
+  br->gptr = gptr;
+  if (br->lane.tk.reset(st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "ticket counter reset");
+  return DPTNAV_OK;
+}
 
 // dW[NN][KK] = sum_tokens Y^T X  ->  grad (overwrite);  bias_grad (optional): column sums of Y, fused into the same pass
 template <int NN, int KK, class YL, class XL>
@@ -1317,9 +1301,9 @@ int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, co
       if (int rc = set_lds(c, kern, lds, what)) return rc;
       ready.set(c->device_id);
     }
-    unsigned* const queue = br.take_queue(1);
+    unsigned* const queue = br.lane.tk.take(1);
     if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, colslab);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, colslab);
   } else {
     auto kern = wgrad_kernel<NN, KK, YL, XL, false>;
     static PerDeviceOnce ready;
@@ -1327,9 +1311,9 @@ int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, co
       if (int rc = set_lds(c, kern, lds, what)) return rc;
       ready.set(c->device_id);
     }
-    unsigned* const queue = br.take_queue(1);
+    unsigned* const queue = br.lane.tk.take(1);
     if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, (float*)nullptr);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, (float*)nullptr);
   }
   LAUNCH_CHECK(c, what);
   constexpr int64_t count = (int64_t)NN * KK;
@@ -1337,7 +1321,7 @@ int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, co
   outs.out[0] = grad;
   // the bias gradient's column sums are reduced by extra workgroups of the same launch
   hipLaunchKernelGGL((slab_reduce_frag_kernel<NN / 128, KK / 32>), dim3((unsigned)(count / 128) + (bias_grad ? (NN + 31) / 32 : 0)),
-                     dim3(256), 0, br.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
+                     dim3(256), 0, br.lane.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
   LAUNCH_CHECK(c, what);
   return DPTNAV_OK;
 }
@@ -1356,10 +1340,10 @@ int launch_wgrad_generic(dptnav_ctx* c, BwdRun& br, const char* what, int64_t nt
     if (int rc = set_lds(c, kern, lds, what)) return rc;
     ready.set(c->device_id);
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.st, (int)ntiles, yl, xl, slab);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, yl, xl, slab);
   LAUNCH_CHECK(c, what);
   constexpr int64_t count = (int64_t)NN * KK;
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, br.st, slab, grid, count, grad, 0);
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, br.lane.st, slab, grid, count, grad, 0);
   LAUNCH_CHECK(c, what);
   return DPTNAV_OK;
 }
@@ -1373,7 +1357,7 @@ int reduce_rider(dptnav_ctx* c, BwdRun& br, const char* what, int grid, int col_
   FragOuts outs{};
   outs.out[0] = grad;
   hipLaunchKernelGGL((slab_reduce_frag_kernel<NN / 128, KK / 32>), dim3((unsigned)(count / 128) + (bias_grad ? (NN + 31) / 32 : 0)),
-                     dim3(256), 0, br.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
+                     dim3(256), 0, br.lane.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
   LAUNCH_CHECK(c, what);
   return DPTNAV_OK;
 }
@@ -1382,7 +1366,10 @@ int reduce_rider(dptnav_ctx* c, BwdRun& br, const char* what, int grid, int col_
 // gradA[s] = sum Y_s^T Xa_s, gradB[s] = sum Y_s^T Xb_s
 template <int NN, int KK, int NSL, class YL, class XA, class XB>
 int launch_wgrad2(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, const Wgrad2Args<YL, XA, XB, NSL>& args,
-                  float* const* gradA, float* const* gradB, hipStream_t wst, float* slab, unsigned* queue) {
+                  float* const* gradA, float* const* gradB, Lane& wl, float* slab) {   // wl: the main lane or the side lane
+  hipStream_t wst = wl.st;
+  unsigned* const queue = wl.tk.take(NSL);   // one counter per slice
+  if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
   const size_t lds = sizeof(float) * (4 + 32 * (size_t)(WgradShape<NN, KK>::LDY + 2 * WgradShape<NN, KK>::LDX));
   static_assert(2 * NSL <= 8, "FragOuts");
   int grid = cap_grid(ntiles * NSL, br.pl.slab_wgs);
@@ -1417,10 +1404,10 @@ int launch_colsum(dptnav_ctx* c, BwdRun& br, const char* what, const float* Y, i
                   float* grad2 = nullptr) {
   const int grid = br.pl.slab_wgs;
   float* slab = br.ws + br.pl.slab;
-  hipLaunchKernelGGL(colsum_kernel<C>, dim3(grid), dim3(256), 0, br.st, Y, M, ld, col0, slab);
+  hipLaunchKernelGGL(colsum_kernel<C>, dim3(grid), dim3(256), 0, br.lane.st, Y, M, ld, col0, slab);
   LAUNCH_CHECK(c, what);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, br.st, slab, grid, (int64_t)C, grad, 0);
-  if (grad2) hipLaunchKernelGGL(slab_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, br.st, slab, grid, (int64_t)C, grad2, 0);
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, br.lane.st, slab, grid, (int64_t)C, grad, 0);
+  if (grad2) hipLaunchKernelGGL(slab_reduce_kernel, dim3((C + 31) / 32), dim3(256), 0, br.lane.st, slab, grid, (int64_t)C, grad2, 0);
   LAUNCH_CHECK(c, what);
   return DPTNAV_OK;
 }
@@ -1443,16 +1430,11 @@ int run_path_backward_dprnn(dptnav_ctx* c, BwdRun& br, int block, int path, cons
   const int K = g.chunk_size;
   const int64_t M = (int64_t)B * S * K;
   const SeqGeom geom = make_geom(path, B, S, K);
-  hipStream_t st = br.st;
+  Lane& lane = br.lane;
+  hipStream_t st = lane.st;
   float *hc = tape + tp.hc, *gates = tape + tp.gates, *cst = tape + tp.cst;
   float *DZ = br.ws + br.pl.dz, *DHb = br.ws + br.pl.dh, *DG = br.ws + br.pl.dg, *LNP = br.ws + br.pl.lnp;
   const int64_t ntiles = (M + 31) / 32, ntiles_n = (M + BMn - 1) / BMn;
-  Run run;
-  run.ws = br.ws;
-  run.pl = Plan{};
-  run.pl.queue = br.pl.queue;
-  run.st = st;
-  run.slot = br.slot;
   // 1. LayerNorm backward from the tape
   {
     const int64_t npass = (M + (256 / (N / 4)) - 1) / (256 / (N / 4));
@@ -1475,13 +1457,11 @@ int run_path_backward_dprnn(dptnav_ctx* c, BwdRun& br, int block, int path, cons
         if (int rc = launch_colsum<N>(c, br, "d fc bias", DZ, M, N, 0, G("fc.bias"))) return rc;
       }
     }
-    run.slot = br.slot;
     {
       ALoadDense al{DZ, M, N, 32};
       EpiAddMaskStoreT<false, false> ep{DHb, nullptr, nullptr, M, LSTM_H, 32, LSTM_H};
-      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, run, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
+      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
     }
-    br.slot = run.slot;
   } else {
     {
       ALoadCols yl{DZ, M, N, 0, 32};
@@ -1493,13 +1473,11 @@ int run_path_backward_dprnn(dptnav_ctx* c, BwdRun& br, int block, int path, cons
         if (int rc = launch_colsum<N>(c, br, "d fc bias", DZ, M, N, 0, G("fc.bias"))) return rc;
       }
     }
-    run.slot = br.slot;
     {
       ALoadDense al{DZ, M, N, 32};
       EpiAddMaskStoreT<false, false> ep{DHb, nullptr, nullptr, M, 2 * LSTM_H, 32, 2 * LSTM_H};
-      if (int rc = launch_gemm<N, 2, 1, 4, true>(c, run, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H)) return rc;
+      if (int rc = launch_gemm<N, 2, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H)) return rc;
     }
-    br.slot = run.slot;
   }
   // 3. LSTM backward through time (tile height as in the forward that wrote the tape)
   const bool use16 = lstm_use16(c, geom, nd, M);
@@ -1530,23 +1508,21 @@ int run_path_backward_dprnn(dptnav_ctx* c, BwdRun& br, int block, int path, cons
     }
   }
   // 5. d_in = d_out (residual) + dP_f W_ih_f + dP_b W_ih_b
-  run.slot = br.slot;
   for (int d = 0; d < nd; ++d) {
     if constexpr (N == 128) {
       ALoadCols al{DG, M, nd * 512, d * 512, 32};
       EpiAddMaskStoreT<true, false> ep{d_in, d == 0 ? d_out : d_in, nullptr, M, N, 32, N};
-      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, run, CAT_LSTM_PRE, "d x", w.w_ih[d], ntiles, 1, al, ep, nullptr, N)) return rc;
+      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, "d x", w.w_ih[d], ntiles, 1, al, ep, nullptr, N)) return rc;
     } else {
       for (int half = 0; half < 2; ++half) {
         ALoadCols al{DG, M, nd * 512, d * 512 + half * 256, BMn};
         EpiAddMaskStoreT<true, false> ep{d_in, d == 0 && half == 0 ? d_out : d_in, nullptr, M, N, BMn, N};
-        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, run, CAT_LSTM_PRE, "d x", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1, al,
+        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, lane, CAT_LSTM_PRE, "d x", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1, al,
                                                          ep, nullptr, N))
           return rc;
       }
     }
   }
-  br.slot = run.slot;
   return DPTNAV_OK;
 }
 
@@ -1567,24 +1543,15 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   const int K = g.chunk_size;
   const int64_t M = (int64_t)B * S * K;
   const SeqGeom geom = make_geom(path, B, S, K);
-  hipStream_t st = br.st;
+  Lane& lane = br.lane;
+  hipStream_t st = lane.st;
   float *qkv = tape + tp.qkv, *att = tape + tp.att, *y1 = tape + tp.y1, *hc = tape + tp.hc, *gates = tape + tp.gates,
         *cst = tape + tp.cst;
   float *DZ = br.ws + br.pl.dz, *DHb = br.ws + br.pl.dh, *DG = br.ws + br.pl.dg, *DY1 = br.ws + br.pl.dy1,
         *DATT = br.ws + br.pl.datt, *DQKV = br.ws + br.pl.dqkv, *LNP = br.ws + br.pl.lnp;
   const int64_t ntiles = (M + 31) / 32, ntiles_n = (M + BMn - 1) / BMn;
-  // fragment-order weight copies of this path (pack_bwd_weights): made for all paths by dptnav_train_backward, or here into slot 0
-  float* const wpk = br.ws + br.pl.wiht + (br.packed_all ? (size_t)(2 * block + path) * BWD_PACK_FLOATS : 0);
-  if constexpr (N == 128) {
-    if (!br.packed_all)
-      if (int rc = pack_bwd_weights(c, st, 2 * block + path, 1, wpk)) return rc;
-  }
-  Run run;   // the GEMM engine takes its ticket counters from a Run: alias it onto the backward workspace
-  run.ws = br.ws;
-  run.pl = Plan{};
-  run.pl.queue = br.pl.queue;
-  run.st = st;
-  run.slot = br.slot;
+  float* wpk = nullptr;   // this path's PACK_BWD slot
+  if (int rc = pack_for(c, st, PACK_BWD, br.all_paths, br.ws + br.pl.wiht, 2 * block + path, &wpk)) return rc;
   int grid = 0;
 
   // 1. push d_out through LayerNorm 2: from the tape's zn / rstd (option ln_tape), or by recomputing
@@ -1604,14 +1571,13 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   } else {
     ALoadColsReLU al{hc, M, 2 * LSTM_H, 0, 32};
     EpiLNBackward<GROUP, 0> ep{DZ, w.ffn_b, y1, w.ln2_w, d_out, LNP, M, N, 32};
-    if (int rc = launch_gemm<2 * LSTM_H, 1, 1, 4>(c, run, CAT_FFN, "ffn recompute + ln2 bwd", w.ffn_w, ntiles, 1, al, ep,
+    if (int rc = launch_gemm<2 * LSTM_H, 1, 1, 4>(c, lane, CAT_FFN, "ffn recompute + ln2 bwd", w.ffn_w, ntiles, 1, al, ep,
                                                  nullptr, 2 * LSTM_H, &grid))
       return rc;
     hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)2 * N, G("ln2.weight"),
                        G("ln2.bias"), N);
     LAUNCH_CHECK(c, "ln2 grads");
   }
-  br.slot = run.slot;
   // 2 + 3. ffn parameter gradients and d h = (dz2 W_f) masked by the ReLU.  Option wgrad_ride (default): ONE launch -- the
   //        data-gradient GEMM stages the dz2 tile anyway and forms dW_f / db_f on the side (WgradRider, gemm_ws.h)
   if (nd == 1) {   // one direction: W_f is [N][128]; the plain schedule (no rider)
@@ -1625,34 +1591,33 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
         if (int rc = launch_colsum<N>(c, br, "d ffn bias", DZ, M, N, 0, G("ffn.1.bias"))) return rc;
       }
     }
-    run.slot = br.slot;
     {
       ALoadDense al{DZ, M, N, 32};
       EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, LSTM_H, 32, LSTM_H};
-      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, run, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
+      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
     }
-    br.slot = run.slot;
   } else {
     bool rode = false;
     if constexpr (N == 128) {
       if (c->opt_wgrad_ride) {
         rode = true;
-        run.slot = br.slot;
         ALoadDense al{DZ, M, N, 32};
         EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, 2 * LSTM_H, 32, 2 * LSTM_H};
         float* slab = br.ws + br.pl.slab;
         int rgrid = 0;
-        const int t = try_dgrad_r(c, run, CAT_FFN, "d h + d ffn weight", DZ, wpk + BWD_PACK_FFNW, 2 * LSTM_H, true, hc, DHb, M, slab,
-                                  slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, BWD_SLAB_WGS, &rgrid);
-        if (t < 0) return -t;
+        bool t = false;
+        if (c->opt_dgrad_r) {
+          const DgradRArgs a{DZ, wpk + BWD_PACK_FFNW, hc, DHb, M, 2 * LSTM_H, /*relu_gate*/ true, nullptr, slab,
+                             slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, BWD_SLAB_WGS};
+          if (int rc = try_dgrad_r(c, lane, CAT_FFN, "d h + d ffn weight", a, &rgrid, &t)) return rc;
+        }
         // (grid known only after the occupancy query inside: the column-sum rows go behind BWD_SLAB_WGS partial tiles)
         WgradRider<2 * LSTM_H, ALoadColsReLU, true> rd{ALoadColsReLU{hc, M, 2 * LSTM_H, 0, 32}, slab,
                                                        slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, M};
         if (!t)
-          if (int rc = launch_gemm<N, 2, 1, 4, true, false>(c, run, CAT_FFN, "d h + d ffn weight", w.ffn_w, ntiles, 1, al, ep, nullptr,
+          if (int rc = launch_gemm<N, 2, 1, 4, true, false>(c, lane, CAT_FFN, "d h + d ffn weight", w.ffn_w, ntiles, 1, al, ep, nullptr,
                                                             2 * LSTM_H, &rgrid, rd))
             return rc;
-        br.slot = run.slot;
         if (int rc = reduce_rider<N, 2 * LSTM_H>(c, br, "d ffn weight + bias", rgrid, BWD_SLAB_WGS, G("ffn.1.weight"), G("ffn.1.bias")))
           return rc;
       }
@@ -1669,14 +1634,12 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
           if (int rc = launch_colsum<N>(c, br, "d ffn bias", DZ, M, N, 0, G("ffn.1.bias"))) return rc;
         }
       }
-      run.slot = br.slot;
       {
         ALoadDense al{DZ, M, N, 32};
         EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, 2 * LSTM_H, 32, 2 * LSTM_H};
-        if (int rc = launch_gemm<N, 2, 1, 4, true>(c, run, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H))
+        if (int rc = launch_gemm<N, 2, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H))
           return rc;
       }
-      br.slot = run.slot;
     }
   }
   // 4. LSTM backward through time (tile height as in the forward that wrote the tape)
@@ -1684,12 +1647,12 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   const int ntl = use16 ? (geom.nseq + 15) / 16 : geom.nst;   // workgroups per direction = partial bias rows
   if (br.lstm_wait && hipStreamWaitEvent(st, br.lstm_wait, 0) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "bptt stagger wait");
   const bool wg2 = c->opt_wgrad2 && N == LSTM_H && nd == 2;   // wgrad2 pairs two X operands of equal width, four slices
-  const bool side = br.side != nullptr && wg2;
+  const bool side = br.side.st != nullptr && wg2;
   if (side) {   // this path's dP goes to the buffer the weight gradients of two paths ago have (or will have) read
     if (br.dg_sel) DG = br.ws + (br.dg_sel == 1 ? br.pl.dg2 : br.pl.dg3);
     if (br.wg_pending[br.dg_sel] && hipStreamWaitEvent(st, br.ev_wg[br.dg_sel], 0) != hipSuccess)
       return c->fail(DPTNAV_ERR_HIP, "side stream wait");
-  } else if (br.side != nullptr && br.wg_pending[0]) {
+  } else if (br.side.st != nullptr && br.wg_pending[0]) {
     // A path whose weight gradients stay in this stream (one LSTM direction: bidir = False) writes its dP to buffer 0 --
     // which a side-stream launch of an EARLIER path may still be reading.  Found by tests/test_gpu_memsafety.py (round 4):
     // block 1's intra-chunk LSTM weight gradients of a bidir = False model came out wrong whenever the next (inter-chunk)
@@ -1739,41 +1702,36 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   if constexpr (N == LSTM_H) {
     if (wg2) {
       if (side) {
-        if (hipEventRecord(br.ev_bptt, st) != hipSuccess || hipStreamWaitEvent(br.side, br.ev_bptt, 0) != hipSuccess)
+        if (hipEventRecord(br.ev_bptt, st) != hipSuccess || hipStreamWaitEvent(br.side.st, br.ev_bptt, 0) != hipSuccess)
           return c->fail(DPTNAV_ERR_HIP, "side stream fork");
-        unsigned* side_q = br.take_queue_side(4);
-        if (!side_q) return c->fail(DPTNAV_ERR_INVALID, "d w_ih + d w_hh: side-stream ticket counters exhausted");
-        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, br.side, br.ws + br.pl.slab2, side_q))
-          return rc;
-        if (hipEventRecord(br.ev_wg[br.dg_sel], br.side) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "side stream record");
+        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, br.side, br.ws + br.pl.slab2)) return rc;
+        if (hipEventRecord(br.ev_wg[br.dg_sel], br.side.st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "side stream record");
         br.wg_pending[br.dg_sel] = true;
         br.dg_sel = (br.dg_sel + 1) % 3;
       } else {
-        unsigned* q4 = br.take_queue(4);
-        if (!q4) return c->fail(DPTNAV_ERR_INVALID, "d w_ih + d w_hh: ticket counters exhausted");
-        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, st, br.ws + br.pl.slab, q4))
-          return rc;
+        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, lane, br.ws + br.pl.slab)) return rc;
       }
     }
   }
   // 6. d y1 = dz2 (residual) + dG_f W_ih_f + dG_b W_ih_b
-  run.slot = br.slot;
   for (int d = 0; d < nd; ++d) {
     if constexpr (N == 128) {
-      const int t = try_dgrad_t(c, run, CAT_LSTM_PRE, "d y1", DG + d * 512, nd * 512, 512, wpk + BWD_PACK_WIH + (size_t)d * 512 * 128,
-                                d == 0 ? DZ : DY1, DY1, M);
-      if (t < 0) return -t;
+      bool t = false;
+      if (c->opt_dgrad_t) {
+        const DgradTArgs a{DG + d * 512, nd * 512, wpk + BWD_PACK_WIH + (size_t)d * 512 * 128, d == 0 ? DZ : DY1, DY1, M, 512};
+        if (int rc = try_dgrad_t(c, lane, CAT_LSTM_PRE, "d y1", a, &t)) return rc;
+      }
       if (t) continue;
       ALoadCols al{DG, M, nd * 512, d * 512, 32};
       EpiAddMaskStoreT<true, false> ep{DY1, d == 0 ? DZ : DY1, nullptr, M, N, 32, N};
-      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, run, CAT_LSTM_PRE, "d y1", w.w_ih[d], ntiles, 1, al, ep, nullptr, N))
+      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, "d y1", w.w_ih[d], ntiles, 1, al, ep, nullptr, N))
         return rc;
     } else {
       // 64-row tiles: a 64 x 512 A tile (double buffered) does not fit the LDS, so the gate columns go in two halves
       for (int half = 0; half < 2; ++half) {
         ALoadCols al{DG, M, nd * 512, d * 512 + half * 256, BMn};
         EpiAddMaskStoreT<true, false> ep{DY1, d == 0 && half == 0 ? DZ : DY1, nullptr, M, N, BMn, N};
-        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, run, CAT_LSTM_PRE, "d y1", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1,
+        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, lane, CAT_LSTM_PRE, "d y1", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1,
                                                          al, ep, nullptr, N))
           return rc;
       }
@@ -1787,33 +1745,33 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   } else {
     ALoadDense al{att, M, N, 32};
     EpiLNBackward<GROUP, 0> ep{DZ, w.out_b, x_in, w.ln1_w, DY1, LNP, M, N, 32};
-    if (int rc = launch_gemm<N, 1, 1, 4>(c, run, CAT_OUTPROJ, "out-proj recompute + ln1 bwd", w.out_w, ntiles, 1, al, ep,
+    if (int rc = launch_gemm<N, 1, 1, 4>(c, lane, CAT_OUTPROJ, "out-proj recompute + ln1 bwd", w.out_w, ntiles, 1, al, ep,
                                         nullptr, N, &grid))
       return rc;
     hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)2 * N, G("ln1.weight"),
                        G("ln1.bias"), N);
     LAUNCH_CHECK(c, "ln1 grads");
   }
-  br.slot = run.slot;
   // 8. out-projection gradients and d att (one launch with option wgrad_ride, as in 2 + 3)
   bool rode8 = false;
   if constexpr (N == 128) {
     if (c->opt_wgrad_ride) {
       rode8 = true;
-      run.slot = br.slot;
       ALoadDense al{DZ, M, N, 32};
       EpiAddMaskStoreT<false, false> ep{DATT, nullptr, nullptr, M, N, 32, N};
       float* slab = br.ws + br.pl.slab;
       int rgrid = 0;
-      const int t = try_dgrad_r(c, run, CAT_OUTPROJ, "d att + d out weight", DZ, wpk + BWD_PACK_OUTW, N, false, att, DATT, M, slab,
-                                slab + (size_t)BWD_SLAB_WGS * N * N, BWD_SLAB_WGS, &rgrid);
-      if (t < 0) return -t;
+      bool t = false;
+      if (c->opt_dgrad_r) {
+        const DgradRArgs a{DZ, wpk + BWD_PACK_OUTW, att, DATT, M, N, /*relu_gate*/ false, nullptr, slab, slab + (size_t)BWD_SLAB_WGS * N * N,
+                           BWD_SLAB_WGS};
+        if (int rc = try_dgrad_r(c, lane, CAT_OUTPROJ, "d att + d out weight", a, &rgrid, &t)) return rc;
+      }
       WgradRider<N, ALoadDense, true> rd{ALoadDense{att, M, N, 32}, slab, slab + (size_t)BWD_SLAB_WGS * N * N, M};
       if (!t)
-        if (int rc = launch_gemm<N, 1, 1, 4, true, false>(c, run, CAT_OUTPROJ, "d att + d out weight", w.out_w, ntiles, 1, al, ep,
+        if (int rc = launch_gemm<N, 1, 1, 4, true, false>(c, lane, CAT_OUTPROJ, "d att + d out weight", w.out_w, ntiles, 1, al, ep,
                                                           nullptr, N, &rgrid, rd))
           return rc;
-      br.slot = run.slot;
       if (int rc = reduce_rider<N, N>(c, br, "d out weight + bias", rgrid, BWD_SLAB_WGS, G("mha.out_proj.weight"), G("mha.out_proj.bias")))
         return rc;
     }
@@ -1831,13 +1789,11 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
         if (int rc = launch_colsum<N>(c, br, "d out bias", DZ, M, N, 0, G("mha.out_proj.bias"))) return rc;
       }
     }
-    run.slot = br.slot;
     {
       ALoadDense al{DZ, M, N, BMn};
       EpiAddMaskStoreT<false, false> ep{DATT, nullptr, nullptr, M, N, BMn, N};
-      if (int rc = launch_gemm<N, 1, WRn, WCn, true>(c, run, CAT_OUTPROJ, "d att", w.out_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
+      if (int rc = launch_gemm<N, 1, WRn, WCn, true>(c, lane, CAT_OUTPROJ, "d att", w.out_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
     }
-    br.slot = run.slot;
   }
   // 9. attention backward
   {
@@ -1895,20 +1851,20 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
       if (int rc = launch_colsum<3 * N>(c, br, "d in bias", DQKV, M, 3 * N, 0, G("mha.in_proj_bias"))) return rc;
     }
   }
-  run.slot = br.slot;
   {
-    int t = 0;
+    bool t = false;
     if constexpr (N == 128) {      // d x = dz + d qkv W_in (K = 384) by dgrad_t.hip
-      t = try_dgrad_t(c, run, CAT_QKV, "d x", DQKV, 3 * N, 384, wpk + BWD_PACK_INW, DZ, d_in, M);
-      if (t < 0) return -t;
+      if (c->opt_dgrad_t) {
+        const DgradTArgs a{DQKV, 3 * N, wpk + BWD_PACK_INW, DZ, d_in, M, 384};
+        if (int rc = try_dgrad_t(c, lane, CAT_QKV, "d x", a, &t)) return rc;
+      }
     }
     if (!t) {
       ALoadDense al{DQKV, M, 3 * N, BMn};
       EpiAddMaskStoreT<true, false> ep{d_in, DZ, nullptr, M, N, BMn, N};
-      if (int rc = launch_gemm<3 * N, 1, WRn, WCn, true>(c, run, CAT_QKV, "d x", w.in_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
+      if (int rc = launch_gemm<3 * N, 1, WRn, WCn, true>(c, lane, CAT_QKV, "d x", w.in_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
     }
   }
-  br.slot = run.slot;
   return DPTNAV_OK;
 }
 
@@ -1940,12 +1896,13 @@ int make_model_tape(dptnav_ctx* c, int B, int64_t L, int S, int Tv, ModelTape* t
 }
 
 template <int N>
-int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const float* E, const float* Z,
+int run_tail_backward(dptnav_ctx* c, BwdRun& br, const float* x, const float* E, const float* Z,
                       const float* d_s1, const float* d_s2, float* d_x, int B, int64_t T, int64_t L, int S) {
   constexpr int GROUP = N / 4;
   constexpr int WRn = N == 128 ? 1 : 2, WCn = N == 128 ? 4 : 2, BMn = 32 * WRn;   // tiles of the GEMMs whose output is N wide
   const dptnav_config& g = c->cfg;
-  hipStream_t st = br.st;
+  Lane& lane = br.lane;
+  hipStream_t st = lane.st;
   const int K = g.chunk_size, P = g.step_size;
   const int64_t M = (int64_t)B * S * K, rows = (int64_t)2 * B * L;
   const int ola = (int)((S - 1) * P + K), left = (int)((L - ola) / 2);
@@ -1970,7 +1927,6 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
     hipLaunchKernelGGL(decoder_wgrad_finish_kernel, dim3((N * g.kernel_size_enc + 255) / 256), dim3(256), 0, st, slab,
                        G("decoder.weight"), N, g.kernel_size_enc);
     LAUNCH_CHECK(c, "masked tail backward + decoder weight grad");
-    br.slot = run.slot;
     // [dW_out; dW_gate] = DA^T u and [db_out; db_gate] = column sums of DA in one pass, then into the four slots
     {
       ALoadCols yl{DA, rows, 2 * N, 0, 32};
@@ -1980,23 +1936,21 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
                                         G("dprnn.output_gate.0.weight"), G("dprnn.output_gate.0.bias"));
       if (e != 0) return c->fail(DPTNAV_ERR_HIP, "masked tail gradient scatter: %s", hipGetErrorString((hipError_t)e));
     }
-    run.slot = br.slot;
     // d u = DA [W_out; W_gate]
     {
       ALoadDense al{DA, rows, 2 * N, BMn};
       EpiAddMaskStoreT<false, false> ep{DU, nullptr, nullptr, rows, N, BMn, N};
-      if (int rc = launch_gemm<2 * N, 1, WRn, WCn, true>(c, run, CAT_POST, "d u (masked tail)", Wp, (rows + BMn - 1) / BMn, 1,
+      if (int rc = launch_gemm<2 * N, 1, WRn, WCn, true>(c, lane, CAT_POST, "d u (masked tail)", Wp, (rows + BMn - 1) / BMn, 1,
                                                         al, ep, nullptr, N))
         return rc;
     }
-    br.slot = run.slot;
   } else {
   // T2 recompute: q = OLA(Z) W_post^T + b_post + E ; d q, d decoder.weight
   {
     ALoadOla al{Z, N, B, (int)L, S, K, P, left, ola, BMn};
     EpiDecoderBwd<GROUP> ep{DQ, c->w("dprnn.postprocessing.0.bias"), E, c->w("decoder.weight"), d_s1, d_s2, LNP,
                             (int64_t)B * L, T, (int)L, g.kernel_size_enc, c->stride, pad_left, BMn};
-    if (int rc = launch_gemm<N, 1, WRn, WCn>(c, run, CAT_POST, "postproc recompute + decoder bwd",
+    if (int rc = launch_gemm<N, 1, WRn, WCn>(c, lane, CAT_POST, "postproc recompute + decoder bwd",
                                             c->w("dprnn.postprocessing.0.weight"), (rows + BMn - 1) / BMn, 1, al, ep, nullptr, N, &grid))
       return rc;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((N * 8 + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)N * 8, slab, 0);
@@ -2004,7 +1958,6 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
                        G("decoder.weight"), N, g.kernel_size_enc);
     LAUNCH_CHECK(c, "decoder weight grad");
   }
-  br.slot = run.slot;
   // post-processing conv gradients; d u = d q W_post
   if (int rc = launch_colsum<N>(c, br, "d postproc bias", DQ, rows, N, 0, G("dprnn.postprocessing.0.bias"))) return rc;
   {
@@ -2018,15 +1971,13 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
         return rc;
     }
   }
-  run.slot = br.slot;
   {
     ALoadDense al{DQ, rows, N, BMn};
     EpiAddMaskStoreT<false, false> ep{DU, nullptr, nullptr, rows, N, BMn, N};
-    if (int rc = launch_gemm<N, 1, WRn, WCn, true>(c, run, CAT_POST, "d u", c->w("dprnn.postprocessing.0.weight"),
+    if (int rc = launch_gemm<N, 1, WRn, WCn, true>(c, lane, CAT_POST, "d u", c->w("dprnn.postprocessing.0.weight"),
                                                   (rows + BMn - 1) / BMn, 1, al, ep, nullptr, N))
       return rc;
   }
-  br.slot = run.slot;
   }
   // overlap-add backward -> d Z ; separation conv gradients ; PReLU backward -> d x
   hipLaunchKernelGGL(ola_grad_gather_kernel, dim3((unsigned)M), dim3(64), 0, st, DU, DZs, N, B, (int)L, S, K, P, left);
@@ -2038,18 +1989,16 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, Run& run, const float* x, const
     if (int rc = launch_wgrad<2 * N, N>(c, br, "d sep weight", (M + 31) / 32, yl, xl, G("dprnn.speakers_separation.1.weight")))
       return rc;
   }
-  run.slot = br.slot;
   {
     ALoadDense al{DZs, M, 2 * N, BMn};
     EpiPReLUBwd ep{d_x, x, c->w("dprnn.speakers_separation.0.weight"), LNP, M, N, BMn};
-    if (int rc = launch_gemm<2 * N, 1, WRn, WCn, true>(c, run, CAT_SEP, "d prelu", c->w("dprnn.speakers_separation.1.weight"),
+    if (int rc = launch_gemm<2 * N, 1, WRn, WCn, true>(c, lane, CAT_SEP, "d prelu", c->w("dprnn.speakers_separation.1.weight"),
                                                       (M + BMn - 1) / BMn, 1, al, ep, nullptr, N, &grid))
       return rc;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(1), dim3(256), 0, st, LNP, grid, (int64_t)1,
                        G("dprnn.speakers_separation.0.weight"), 0);
     LAUNCH_CHECK(c, "prelu slope grad");
   }
-  br.slot = run.slot;
   return DPTNAV_OK;
 }
 
@@ -2057,7 +2006,7 @@ template <int N>
 int run_head_backward(dptnav_ctx* c, BwdRun& br, const float* mix, const float* e1, const float* e2, const float* vid,
                       const float* dX0, int B, int64_t T, int64_t L, int S, int Tv) {
   const dptnav_config& g = c->cfg;
-  hipStream_t st = br.st;
+  hipStream_t st = br.lane.st;
   constexpr int FPB = 256 / (N / 4);
   float *DQ = br.ws + br.pl.dq, *DE = br.ws + br.pl.de, *DVI = br.ws + br.pl.dvi, *DV = br.ws + br.pl.dv,
         *slab = br.ws + br.pl.slab, *red = br.ws + br.pl.lnp;
@@ -2112,15 +2061,11 @@ int check_common(dptnav_ctx* c, int B, int64_t T, int Tv, void* ws, size_t ws_by
 
 // Start a pass on `st` over the workspace slice `ws`: zero its ticket counters (stream ordered).
 int begin_run(dptnav_ctx* c, Run* run, float* ws, const Plan& pl, hipStream_t st) {
+  *run = Run{};
   run->ws = ws;
   run->pl = pl;
-  run->st = st;
-  run->slot = 0;
-  run->packed = false;
-  run->packed_wih = false;
-  run->packed_whh4 = false;
-  run->packed_x16 = false;
-  hipError_t e = hipMemsetAsync(ws + pl.queue, 0, QUEUE_SLOTS * sizeof(unsigned), st);
+  run->lane = Lane{st, Tickets{reinterpret_cast<unsigned*>(ws + pl.queue), 0}};
+  hipError_t e = run->lane.tk.reset(st);
   if (e != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "ticket counter reset: %s", hipGetErrorString(e));
   return DPTNAV_OK;
 }
@@ -2250,9 +2195,9 @@ constexpr int MAX_SUB = 32;
 //    (8 + 8 at B = 16, 12 + 12 at B = 24, 11 + 11 + 10 at B = 32).  One exception, option split_policy = 1 (default): when
 //    a half-batch launch needs more than half of the CUs but a third needs less (B = 13..18: 6 + 5 + 5 mixtures = 106 +
 //    94 + 94 workgroups) three sub-batches are 1 % faster for N = 128 (30.6 vs 31.0 ms at B = 16) and equal for N = 64.
-static int forward_split(dptnav_handle h, int B, int64_t T, int Tv, int* sizes, int* inflight = nullptr) {
+static int forward_split(dptnav_handle h, bool overlap, int B, int64_t T, int Tv, int* sizes, int* inflight = nullptr) {
   if (inflight) *inflight = 1;
-  if (!h->opt_overlap || B < 2) { sizes[0] = B; return 1; }
+  if (!overlap || B < 2) { sizes[0] = B; return 1; }
   Plan pl;
   int nsub = 2, depth = 1;
   if (h->opt_lstm16 && make_plan(h, 1, T, Tv, &pl) == DPTNAV_OK) {
@@ -2288,11 +2233,8 @@ size_t dptnav_workspace_bytes(dptnav_handle h, int B, int64_t T, int Tv) {
   size_t need = 0;
   if (make_plan(h, B, T, Tv, &pl) == DPTNAV_OK) need = pl.total;
   if (B >= 2) {
-    const bool keep = h->opt_overlap;
-    h->opt_overlap = true;                       // size for the split even if the option is switched on later
     int sizes[MAX_SUB];
-    const int nsub = forward_split(h, B, T, Tv, sizes);
-    h->opt_overlap = keep;
+    const int nsub = forward_split(h, /*overlap*/ true, B, T, Tv, sizes);   // size for the split even if the option is switched on later
     size_t sum = 0;
     bool ok = true;
     for (int i = 0; i < nsub && ok; ++i) {
@@ -2314,8 +2256,7 @@ int dptnav_stage_head(dptnav_handle h, const float* mix, const float* e1, const 
     return h->fail(DPTNAV_ERR_INVALID, "null tensor argument");
   Run run;
   if (int rc = begin_run(h, &run, (float*)ws, pl, (hipStream_t)stream)) return rc;
-  return h->cfg.num_features == 128 ? run_head<128>(h, run, mix, e1, e2, B, T, Tv, encoded, chunked)
-                                    : run_head<64>(h, run, mix, e1, e2, B, T, Tv, encoded, chunked);
+  return with_width(h, [&](auto N) { return run_head<N()>(h, run, mix, e1, e2, B, T, Tv, encoded, chunked); });
 }
 
 int dptnav_stage_path(dptnav_handle h, int block, int path, const float* x_in, float* x_out, int B, int S, void* ws,
@@ -2334,8 +2275,7 @@ int dptnav_stage_path(dptnav_handle h, int block, int path, const float* x_in, f
   if (int rc = begin_run(h, &run, (float*)ws, pl, (hipStream_t)stream)) return rc;
   run.fuse128 = h->fuse128_for(B);
   run.batch_total = B;
-  return h->cfg.num_features == 128 ? run_path<128>(h, run, block, path, x_in, x_out, B, S)
-                                    : run_path<64>(h, run, block, path, x_in, x_out, B, S);
+  return with_width(h, [&](auto N) { return run_path<N()>(h, run, block, path, x_in, x_out, B, S); });
 }
 
 int dptnav_stage_tail(dptnav_handle h, const float* x, const float* encoded, int B, int64_t T, float* s1, float* s2,
@@ -2346,8 +2286,7 @@ int dptnav_stage_tail(dptnav_handle h, const float* x, const float* encoded, int
   if (!x || !encoded || !s1 || !s2) return h->fail(DPTNAV_ERR_INVALID, "null tensor argument");
   Run run;
   if (int rc = begin_run(h, &run, (float*)ws, pl, (hipStream_t)stream)) return rc;
-  return h->cfg.num_features == 128 ? run_tail<128>(h, run, x, encoded, B, T, s1, s2)
-                                    : run_tail<64>(h, run, x, encoded, B, T, s1, s2);
+  return with_width(h, [&](auto N) { return run_tail<N()>(h, run, x, encoded, B, T, s1, s2); });
 }
 
 int dptnav_forward(dptnav_handle h, const float* mix, const float* e1, const float* e2, int B, int64_t T, int Tv,
@@ -2367,7 +2306,7 @@ int dptnav_forward(dptnav_handle h, const float* mix, const float* e1, const flo
   // launches (dynamic tile tickets) fill the rest of the chip meanwhile.  Fork/join by events on the caller's stream.
   int Bs[MAX_SUB];
   int depth = 1;
-  const int nsub = forward_split(h, B, T, Tv, Bs, &depth);
+  const int nsub = forward_split(h, h->opt_overlap, B, T, Tv, Bs, &depth);
   Plan pl[MAX_SUB];
   size_t need = 0, base[MAX_SUB];
   for (int i = 0; i < nsub; ++i) {
@@ -2418,15 +2357,11 @@ int dptnav_forward(dptnav_handle h, const float* mix, const float* e1, const flo
   auto X0 = [&](int i) { return run[i].ws + run[i].pl.X0; };
   auto X1 = [&](int i) { return run[i].ws + run[i].pl.X1; };
   for (int i = 0; i < nsub; ++i) {
-    int rc = big ? run_head<128>(h, run[i], mixi[i], e1i[i], e2i[i], Bs[i], T, Tv, E(i), X0(i))
-                 : run_head<64>(h, run[i], mixi[i], e1i[i], e2i[i], Bs[i], T, Tv, E(i), X0(i));
-    if (rc) return rc;
-    if (big && g.arch == 0 && h->opt_fuse_attn && !h->opt_split_bf16) {
-      if (int rc2 = pack_attn_weights(h, run[i].st, 0, 2 * g.num_blocks, run[i].ws + run[i].pl.wpack)) return rc2;
-      run[i].packed = true;
-    }
-    if (!h->opt_split_bf16)
-      if (int rc2 = big ? pack_wih_all<128>(h, run[i]) : pack_wih_all<64>(h, run[i])) return rc2;
+    if (int rc = with_width(h, [&](auto N) { return run_head<N()>(h, run[i], mixi[i], e1i[i], e2i[i], Bs[i], T, Tv, E(i), X0(i)); })) return rc;
+    if (big && g.arch == 0 && h->opt_fuse_attn && !h->opt_split_bf16)
+      if (int rc = pack_all(h, run[i], PACK_ATTN)) return rc;
+    if (h->opt_pack_wih && !h->opt_split_bf16)
+      if (int rc = pack_all(h, run[i], PACK_WIH)) return rc;
   }
   // recurrence launch n (path-major, sub-batch minor) waits for launch n - depth: `depth` recurrences may be in flight
   // (forward_split; > 1 pays when two launches fit the chip together: three or more sub-batches).  ev_sub[j] is re-recorded by sub-batch j once per path, so its latest record IS launch n - depth.
@@ -2446,7 +2381,7 @@ int dptnav_forward(dptnav_handle h, const float* mix, const float* e1, const flo
         if (h->opt_fuse_ffn && !h->opt_split_bf16) {
           const int S_i = (int)pl[i].S;
           const bool first = b == 0 && path == 0, last = b == g.num_blocks - 1 && path == 1;
-          auto fusable = [&](int p) { return big ? path_fusable<128>(h, p, Bs[i], S_i) : path_fusable<64>(h, p, Bs[i], S_i); };
+          auto fusable = [&](int p) { return with_width(h, [&](auto N) { return (int)path_fusable<N()>(h, p, Bs[i], S_i); }) != 0; };
           // the prologue contracts over ReLU(h) of BOTH directions (K = 256): a unidirectional inter-chunk LSTM
           // (bidir = false) keeps its own K6 launch
           const bool this_two = h->pw[2 * b + path].ndir == 2;
@@ -2454,14 +2389,11 @@ int dptnav_forward(dptnav_handle h, const float* mix, const float* e1, const flo
           if (!first && prev_two && fusable(path)) chain |= CHAIN_PRO;
           if (!last && this_two && fusable(1 - path)) chain |= CHAIN_SKIP_FFN;
         }
-        int rc = big ? run_path<128>(h, run[i], b, path, xin, xout, Bs[i], (int)pl[i].S, nullptr, chain)
-                     : run_path<64>(h, run[i], b, path, xin, xout, Bs[i], (int)pl[i].S, nullptr, chain);
-        if (rc) return rc;
+        if (int rc = with_width(h, [&](auto N) { return run_path<N()>(h, run[i], b, path, xin, xout, Bs[i], (int)pl[i].S, nullptr, chain); }))
+          return rc;
       }
   for (int i = 0; i < nsub; ++i) {
-    int rc = big ? run_tail<128>(h, run[i], X0(i), E(i), Bs[i], T, s1i[i], s2i[i])
-                 : run_tail<64>(h, run[i], X0(i), E(i), Bs[i], T, s1i[i], s2i[i]);
-    if (rc) return rc;
+    if (int rc = with_width(h, [&](auto N) { return run_tail<N()>(h, run[i], X0(i), E(i), Bs[i], T, s1i[i], s2i[i]); })) return rc;
   }
   return DPTNAV_OK;
   };
@@ -2607,8 +2539,7 @@ int dptnav_train_path_forward(dptnav_handle h, int block, int path, const float*
   float* tb = (float*)tape;
   PathBufs pb{tb + tp.qkv, tb + tp.att, tb + tp.y1, run.ws + pl.pre, tb + tp.hc, tb + tp.gates, tb + tp.cst, true, tb + tp.astats, tb + tp.amask};
   if (tp.zn1) { pb.zn1 = tb + tp.zn1; pb.rs1 = tb + tp.rs1; pb.zn2 = tb + tp.zn2; pb.rs2 = tb + tp.rs2; }
-  return h->cfg.num_features == 128 ? run_path<128>(h, run, block, path, x_in, x_out, B, S, &pb)
-                                    : run_path<64>(h, run, block, path, x_in, x_out, B, S, &pb);
+  return with_width(h, [&](auto N) { return run_path<N()>(h, run, block, path, x_in, x_out, B, S, &pb); });
 }
 int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float* x_in, const float* d_out, float* d_in,
                                int B, int S, void* tape, size_t tape_bytes, void* bws, size_t bws_bytes, void* stream) {
@@ -2626,11 +2557,9 @@ int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float
   make_bwd_plan(h, B, S, &bp);
   if (tape_bytes < tp.total * sizeof(float) || bws_bytes < bp.total * sizeof(float) || ((uintptr_t)bws & 255) != 0)
     return h->fail(DPTNAV_ERR_WORKSPACE, "tape or backward workspace too small / misaligned");
-  BwdRun br{(float*)bws, bp, (hipStream_t)stream, 0, h->gptr.data()};
-  if (hipMemsetAsync(br.ws + bp.queue, 0, QUEUE_SLOTS * sizeof(unsigned), br.st) != hipSuccess)
-    return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
-  return h->cfg.num_features == 128 ? run_path_backward<128>(h, br, block, path, x_in, d_out, d_in, B, S, (float*)tape, tp)
-                                    : run_path_backward<64>(h, br, block, path, x_in, d_out, d_in, B, S, (float*)tape, tp);
+  BwdRun br;
+  if (int rc = begin_bwd_run(h, &br, (float*)bws, bp, (hipStream_t)stream, h->gptr.data())) return rc;
+  return with_width(h, [&](auto N) { return run_path_backward<N()>(h, br, block, path, x_in, d_out, d_in, B, S, (float*)tape, tp); });
 }
 
 // ---- training step, whole model -------------------------------------------------------------------------
@@ -2734,12 +2663,15 @@ int dptnav_train_forward(dptnav_handle h, const float* mix, const float* e1, con
     run[i].half = i;
     tb[i] = (float*)tape + sp.tape_off[i];
     const ModelTape& mt = sp.mt[i];
-    if (int rc = (h->cfg.num_features == 128 ? run_head<128>(h, run[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr, e2 ? e2 + b0[i] * Cv * Tv : nullptr,
-                               sp.Bh[i], T, Tv, tb[i] + mt.E, tb[i] + mt.X0, tb[i] + mt.vid) : run_head<64>(h, run[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr, e2 ? e2 + b0[i] * Cv * Tv : nullptr,
-                               sp.Bh[i], T, Tv, tb[i] + mt.E, tb[i] + mt.X0, tb[i] + mt.vid)))
+    if (int rc = with_width(h, [&](auto N) {
+          return run_head<N()>(h, run[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr, e2 ? e2 + b0[i] * Cv * Tv : nullptr, sp.Bh[i], T, Tv,
+                               tb[i] + mt.E, tb[i] + mt.X0, tb[i] + mt.vid);
+        }))
       return rc;
-    if (int rc = h->cfg.num_features == 128 ? pack_wih_all<128>(h, run[i]) : pack_wih_all<64>(h, run[i])) return rc;
-    if (int rc = pack_inw_all(h, run[i])) return rc;
+    if (h->opt_pack_wih)
+      if (int rc = pack_all(h, run[i], PACK_WIH)) return rc;
+    if (h->opt_gemm_t && h->cfg.num_features == 128 && h->cfg.arch == 0)
+      if (int rc = pack_all(h, run[i], PACK_INW)) return rc;
   }
   // the halves advance in lock step on the host; their recurrences are chained by events as in dptnav_forward
   bool have_prev = false;
@@ -2754,18 +2686,20 @@ int dptnav_train_forward(dptnav_handle h, const float* mix, const float* e1, con
       PathBufs pb{pt + mt.pt.qkv, pt + mt.pt.att, pt + mt.pt.y1, run[i].ws + sp.pl[i].pre, pt + mt.pt.hc, pt + mt.pt.gates,
                   pt + mt.pt.cst, true, pt + mt.pt.astats, pt + mt.pt.amask};
       if (mt.pt.zn1) { pb.zn1 = pt + mt.pt.zn1; pb.rs1 = pt + mt.pt.rs1; pb.zn2 = pt + mt.pt.zn2; pb.rs2 = pt + mt.pt.rs2; }
-      if (int rc = (h->cfg.num_features == 128 ? run_path<128>(h, run[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride,
-                                 tb[i] + mt.X0 + (size_t)(p + 1) * mt.x_stride, sp.Bh[i], (int)sp.pl[i].S, &pb) : run_path<64>(h, run[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride,
-                                 tb[i] + mt.X0 + (size_t)(p + 1) * mt.x_stride, sp.Bh[i], (int)sp.pl[i].S, &pb)))
+      if (int rc = with_width(h, [&](auto N) {
+            return run_path<N()>(h, run[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride, tb[i] + mt.X0 + (size_t)(p + 1) * mt.x_stride,
+                                 sp.Bh[i], (int)sp.pl[i].S, &pb);
+          }))
         return rc;
       have_prev = true;
     }
   // tail: Z (separation-conv output) is needed again by the backward -> kept on the tape
   for (int i = 0; i < sp.nhalf; ++i) {
     const ModelTape& mt = sp.mt[i];
-    if (int rc = (h->cfg.num_features == 128 ? run_tail<128>(h, run[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, sp.Bh[i], T,
-                               s1 + b0[i] * T, s2 + b0[i] * T, tb[i] + mt.Z) : run_tail<64>(h, run[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, sp.Bh[i], T,
-                               s1 + b0[i] * T, s2 + b0[i] * T, tb[i] + mt.Z)))
+    if (int rc = with_width(h, [&](auto N) {
+          return run_tail<N()>(h, run[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, sp.Bh[i], T, s1 + b0[i] * T, s2 + b0[i] * T,
+                               tb[i] + mt.Z);
+        }))
       return rc;
   }
   return DPTNAV_OK;
@@ -2816,70 +2750,59 @@ int dptnav_train_backward(dptnav_handle h, const float* mix, const float* e1, co
     }
   }
   BwdRun br[2];
-  Run run[2];
   float *tb[2], *dcur[2], *dnext[2];
   for (int i = 0; i < sp.nhalf; ++i) {
     const BwdPlan& bp = sp.bp[i];
-    br[i] = BwdRun{(float*)ws + sp.ws_off[i], bp, si[i], 0, i == 0 ? h->gptr.data() : h->gptr_half1.data()};
+    if (int rc = begin_bwd_run(h, &br[i], (float*)ws + sp.ws_off[i], bp, si[i], i == 0 ? h->gptr.data() : h->gptr_half1.data())) return rc;
     br[i].half = i;
-    if (hipMemsetAsync(br[i].ws + bp.queue, 0, QUEUE_SLOTS * sizeof(unsigned), si[i]) != hipSuccess)
-      return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
     if (sp.nhalf == 2 && h->opt_wgrad_side) {
-      if (hipMemsetAsync(br[i].ws + bp.queue2, 0, QUEUE_SLOTS * sizeof(unsigned), si[i]) != hipSuccess)
-        return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
-      br[i].side = h->streams[2 + i];
+      br[i].side = Lane{h->streams[2 + i], Tickets{reinterpret_cast<unsigned*>(br[i].ws + bp.queue2), 0}};
+      // (zeroed on the half's own stream: the side stream's launches wait for an event of it)
+      if (br[i].side.tk.reset(si[i]) != hipSuccess) return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
       br[i].ev_bptt = h->ev_side[i][0];
       br[i].ev_wg[0] = h->ev_side[i][1];
       br[i].ev_wg[1] = h->ev_side[i][2];
       br[i].ev_wg[2] = h->ev_side[i][3];
     }
-    for (int first = 0; first < 2 * nb; first += DGRAD_R_PACK_MAX / 2) {      // weight copies of every path, once per step and half
-      const int n = std::min(DGRAD_R_PACK_MAX / 2, 2 * nb - first);
-      if (int rc = pack_bwd_weights(h, si[i], first, n, br[i].ws + bp.wiht + (size_t)first * BWD_PACK_FLOATS)) return rc;
-    }
-    br[i].packed_all = true;
-    run[i].ws = br[i].ws;
-    run[i].pl = Plan{};
-    run[i].pl.queue = bp.queue;
-    run[i].st = si[i];
-    run[i].slot = 0;
-    run[i].half = i;
+    if (int rc = pack_paths(h, si[i], PACK_BWD, 0, 2 * nb, br[i].ws + bp.wiht)) return rc;      // weight copies of every path, once per step and half
+    br[i].all_paths[PACK_BWD] = true;
     tb[i] = (float*)tape + sp.tape_off[i];
     dcur[i] = br[i].ws + bp.dxa;
     dnext[i] = br[i].ws + bp.dxb;
     const ModelTape& mt = sp.mt[i];
-    if (int rc = (h->cfg.num_features == 128 ? run_tail_backward<128>(h, br[i], run[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, tb[i] + mt.Z,
-                                        d_s1 + b0[i] * T, d_s2 + b0[i] * T, dcur[i], sp.Bh[i], T, sp.pl[i].L, (int)sp.pl[i].S) : run_tail_backward<64>(h, br[i], run[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, tb[i] + mt.Z,
-                                        d_s1 + b0[i] * T, d_s2 + b0[i] * T, dcur[i], sp.Bh[i], T, sp.pl[i].L, (int)sp.pl[i].S)))
+    if (int rc = with_width(h, [&](auto N) {
+          return run_tail_backward<N()>(h, br[i], tb[i] + mt.X0 + (size_t)(2 * nb) * mt.x_stride, tb[i] + mt.E, tb[i] + mt.Z, d_s1 + b0[i] * T,
+                                        d_s2 + b0[i] * T, dcur[i], sp.Bh[i], T, sp.pl[i].L, (int)sp.pl[i].S);
+        }))
       return rc;
   }
   bool have_prev = false;
   for (int p = 2 * nb - 1; p >= 0; --p)
     for (int i = 0; i < sp.nhalf; ++i) {
       const ModelTape& mt = sp.mt[i];
-      if (br[i].slot > QUEUE_SLOTS - 64) {   // plenty of launches per path: recycle the ticket counters
-        if (hipMemsetAsync(br[i].ws + sp.bp[i].queue, 0, QUEUE_SLOTS * sizeof(unsigned), si[i]) != hipSuccess)
-          return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
-        br[i].slot = 0;
-      }
+      // plenty of launches per path: recycle the half's counters in time; the side lane's go four at a time (wgrad2), so they are
+      // zeroed again, on the side stream behind the launches that used them, only once the region is used up (after 256 paths)
+      if (br[i].lane.tk.recycle_if_low(si[i], 64) != hipSuccess ||
+          (br[i].side.st && br[i].side.tk.recycle_if_low(br[i].side.st, 4) != hipSuccess))
+        return h->fail(DPTNAV_ERR_HIP, "ticket counter reset");
       if (sp.nhalf == 2) {
         br[i].lstm_wait = have_prev && h->opt_lstm_chain ? h->ev_lstm[1 - i] : nullptr;
         br[i].lstm_record = h->ev_lstm[i];
       }
       float* pt = tb[i] + mt.paths + (size_t)p * mt.path_stride;
-      if (int rc = (h->cfg.num_features == 128 ? run_path_backward<128>(h, br[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride, dcur[i], dnext[i],
-                                          sp.Bh[i], (int)sp.pl[i].S, pt, mt.pt) : run_path_backward<64>(h, br[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride, dcur[i], dnext[i],
-                                          sp.Bh[i], (int)sp.pl[i].S, pt, mt.pt)))
+      if (int rc = with_width(h, [&](auto N) {
+            return run_path_backward<N()>(h, br[i], p / 2, p % 2, tb[i] + mt.X0 + (size_t)p * mt.x_stride, dcur[i], dnext[i], sp.Bh[i],
+                                          (int)sp.pl[i].S, pt, mt.pt);
+          }))
         return rc;
       std::swap(dcur[i], dnext[i]);
       have_prev = true;
     }
   for (int i = 0; i < sp.nhalf; ++i)
-    if (int rc = (h->cfg.num_features == 128 ? run_head_backward<128>(h, br[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr,
-                                        e2 ? e2 + b0[i] * Cv * Tv : nullptr, tb[i] + sp.mt[i].vid, dcur[i], sp.Bh[i], T,
-                                        sp.pl[i].L, (int)sp.pl[i].S, Tv) : run_head_backward<64>(h, br[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr,
-                                        e2 ? e2 + b0[i] * Cv * Tv : nullptr, tb[i] + sp.mt[i].vid, dcur[i], sp.Bh[i], T,
-                                        sp.pl[i].L, (int)sp.pl[i].S, Tv)))
+    if (int rc = with_width(h, [&](auto N) {
+          return run_head_backward<N()>(h, br[i], mix + b0[i] * T, e1 ? e1 + b0[i] * Cv * Tv : nullptr, e2 ? e2 + b0[i] * Cv * Tv : nullptr,
+                                        tb[i] + sp.mt[i].vid, dcur[i], sp.Bh[i], T, sp.pl[i].L, (int)sp.pl[i].S, Tv);
+        }))
       return rc;
   return DPTNAV_OK;
   };

@@ -1,5 +1,7 @@
 """Training-step parity (GPU): the path-level backward of libdptnav against torch.autograd on the stock-PyTorch CPU
 composition (oracle/torch_stock.py) -- the same graph the reference's loss.backward() differentiates (dptn.py:36-52)."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -673,3 +675,137 @@ def test_unidirectional_whole_model_trains(dev):
     assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
     for k, p_ in model.named_parameters():
         assert p_.grad is not None and torch.isfinite(p_.grad).all() and float(p_.grad.abs().max()) > 0, k
+
+
+# ---------------------------------------------------------------------------------------------
+# the backward's ticket-counter cursor
+# ---------------------------------------------------------------------------------------------
+_RECYCLE_BLOCKS = 161
+_RECYCLE_BAR_DB = 36.2         # 6 dB below what the commit before the cursor refactor reaches (42.20 dB, see the test)
+
+
+@pytest.fixture(scope="module")
+def recycle_case():
+    """Configuration, weights, inputs and the fp64 autograd gradients of the deep model (computed once for both runs)."""
+    from speech_separation_amd.spec import synthetic_inputs
+    cfg = DPTNConfig(**{**DPTN_AV.to_dict(), "num_blocks": _RECYCLE_BLOCKS, "dropout": 0.0, "audio_only": True, "chunk_size": 16,
+                        "step_size": 8})
+    sd = synthetic_state_dict(cfg, seed=2)
+    B, T = 2, 100
+    inp = synthetic_inputs(cfg, B=B, T=T, seed=6)
+    rng = np.random.default_rng(3)
+    d1 = rng.standard_normal((B, T)).astype(np.float32)
+    d2 = rng.standard_normal((B, T)).astype(np.float32)
+    ref = StockDPTN(cfg, sd)
+    ref.sd = {k: v.double().requires_grad_(True) for k, v in ref.sd.items()}
+    ref.paths = [(pre, m.double(), r.double()) for pre, m, r in ref.paths]
+    for _, m, r in ref.paths:
+        for p in list(m.parameters()) + list(r.parameters()):
+            p.requires_grad_(True)
+    with torch.enable_grad():
+        out = StockDPTN.__call__.__wrapped__(ref, mix=torch.from_numpy(inp["mix"]).double())
+        (out["s1_pred"] * torch.from_numpy(d1).double() + out["s2_pred"] * torch.from_numpy(d2).double()).sum().backward()
+    want = {}
+    for pre, m, r in ref.paths:
+        want[pre + "mha.in_proj_weight"], want[pre + "mha.in_proj_bias"] = m.in_proj_weight.grad, m.in_proj_bias.grad
+        want[pre + "mha.out_proj.weight"], want[pre + "mha.out_proj.bias"] = m.out_proj.weight.grad, m.out_proj.bias.grad
+        for k, v in r.named_parameters():
+            want[pre + "rnn." + k] = v.grad
+    for k, v in ref.sd.items():
+        if k not in want and v.grad is not None:
+            want[k] = v.grad
+    return cfg, sd, inp["mix"], d1, d2, {k: v.numpy() for k, v in want.items()}
+
+
+@pytest.mark.parametrize("train_overlap", [1, 0])
+def test_backward_recycles_its_ticket_counters(dev, recycle_case, train_overlap):
+    """A whole-model training step deep enough that dptnav_train_backward zeroes its ticket counters again in the middle of
+    the step, at least twice per half, against fp64 autograd for every parameter.  S = 3 chunks of 16 frames, B = 2, option
+    deterministic = 0 (with 1 the kernels get no counters).
+
+    Counters per pass under default options (num_features = 128, two LSTM directions): the tail's backward takes 5 (three
+    GEMM-engine launches, two weight-gradient launches) and a path 6 from the half's own region (two dgrad_r, three dgrad_t,
+    the in-projection weight gradient) plus 4 for the LSTM weight gradients (wgrad2), which come from the side stream's region
+    while the batch is split (train_overlap = 1: B = 2 runs as two halves of one mixture) and from the half's own otherwise.
+    The region holds 1024 and is zeroed again in front of a path once more than 960 are used:
+      train_overlap = 1: 5 + 6 p > 960 in front of the 161st path, again 161 paths later -- 2 recycles per half at 322 paths,
+      train_overlap = 0: 5 + 10 p > 960 in front of the 97th path, then every 97 paths -- 3 recycles.
+    Hence 161 blocks: the smallest depth with two recycles in both runs (counted with a build that prints the cursor: resets
+    at 965 and 966 used per half, at 965, 970 and 970 unsplit).  The side stream's region is used up after 256 paths and is
+    then zeroed again on the side stream, once per half here.  (The forward has no recycling: its 3 counters per path --
+    gemm_t, and two column groups of the K4 launch -- come to 966 of the 1024.)
+
+    The bar: the commit before the cursor refactor reaches 42.20 dB for its worst parameter (block 155's intra-chunk
+    rnn.bias_hh_l0) with train_overlap = 0; with train_overlap = 1 it refuses this depth ("side-stream ticket counters
+    exhausted": it never zeroed that region again), and with nothing but that reset added it reaches 42.20 dB too.  Ticket
+    order only reorders fp32 partial sums, which moves the figure by far less than 6 dB, so the bar is 36.2 dB; a skipped or
+    doubled tile lands below 30 dB.
+    """
+    from speech_separation_amd.engine import DptnEngine, params_to_device
+    cfg, sd, mix, d1, d2, want = recycle_case
+    eng = DptnEngine(cfg, dev)
+    eng.bind(params_to_device(sd, dev))
+    grads = eng.bind_grads()
+    eng.set_option("train_overlap", train_overlap)
+    mixt = torch.from_numpy(mix).to(dev)
+    s1, s2, tape = eng.train_forward(mixt)
+    eng.train_backward(mixt, None, None, torch.from_numpy(d1).to(dev), torch.from_numpy(d2).to(dev), tape)
+    torch.cuda.synchronize()
+    missing = [k for k in grads if k not in want]
+    assert not missing, missing
+    worst = min((O.agreement_db(grads[k].cpu().numpy(), want[k].reshape(grads[k].shape)), k) for k in grads)
+    print(f"recycle test: train_overlap={train_overlap} worst agreement {worst[0]:.2f} dB at {worst[1]}")
+    assert worst[0] > _RECYCLE_BAR_DB, worst
+
+
+# (n, launch): the launch that the n-th tick of option inject_fail hits in the step below -- found by stepping n over the
+# 80 ticks of the step and reading the error text, which names the launch: 1-32 the forward's paths (gemm_t "qkv gemm", fcln
+# out-projection, engine "lstm-pre gemm", fcln ffn per path and half), 33-34 its tail, 35-40 the backward's tail, 41-80 its
+# paths (dgrad_r "d h + d ffn weight", dgrad_t "d y1" twice, dgrad_r "d att + d out weight", dgrad_t "d x" per path and half)
+_INJECT_CASES = [(7, "lstm-pre gemm"),                 # GEMM engine, forward
+                 (18, "fcln (out-projection)"),        # fcln.hip
+                 (29, "qkv gemm"),                     # gemm_t.hip, last block
+                 (33, "fcln (separation conv)"),       # fcln.hip, forward tail
+                 (36, "d u"),                          # GEMM engine, backward tail
+                 (52, "d y1"),                         # dgrad_t.hip
+                 (64, "d att + d out weight"),         # dgrad_r.hip
+                 (80, "d x")]                          # dgrad_t.hip: the last launch of the step that can fail
+
+
+def test_training_step_survives_an_injected_launch_failure(dev):
+    """A launch failure in the middle of a split training step (fault injection), once per kind of launch that can fail:
+    the call returns the error, the caller's stream is still joined to all four internal streams, and the next step's
+    gradients are bit-identical with an undisturbed step's (option deterministic) -- no ticket, no cursor position and no
+    weight-pack state of the failed step is left behind."""
+    from speech_separation_amd.engine import DptnEngine, params_to_device
+    from speech_separation_amd.spec import synthetic_inputs
+    cfg = DPTNConfig(**{**DPTN_AV.to_dict(), "num_blocks": 2, "dropout": 0.0})
+    sd = synthetic_state_dict(cfg, seed=2)
+    eng = DptnEngine(cfg, dev)
+    eng.bind(params_to_device(sd, dev))
+    grads = eng.bind_grads()
+    eng.set_option("deterministic", 1)
+    B, T, Tv = 2, 2000, 9
+    t = {k: torch.from_numpy(v).to(dev) for k, v in synthetic_inputs(cfg, B=B, T=T, Tv=Tv, seed=6).items()}
+    rng = np.random.default_rng(3)
+    d1 = torch.from_numpy(rng.standard_normal((B, T)).astype(np.float32)).to(dev)
+    d2 = torch.from_numpy(rng.standard_normal((B, T)).astype(np.float32)).to(dev)
+
+    def step():
+        _, _, tape = eng.train_forward(t["mix"], t["s1_embedding"], t["s2_embedding"])
+        eng.train_backward(t["mix"], t["s1_embedding"], t["s2_embedding"], d1, d2, tape)
+
+    step()
+    torch.cuda.synchronize()
+    g0 = {k: v.clone() for k, v in grads.items()}
+    for nth, launch in _INJECT_CASES:
+        for v in grads.values():
+            v.zero_()
+        eng.set_option("inject_fail", nth)
+        with pytest.raises(RuntimeError, match=re.escape(launch + ": injected failure")):
+            step()
+        torch.cuda.current_stream().synchronize()           # must cover the internal streams' work
+        step()
+        torch.cuda.synchronize()
+        bad = [k for k in grads if not torch.equal(grads[k], g0[k])]
+        assert not bad, (nth, launch, bad)
