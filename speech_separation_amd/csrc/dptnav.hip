@@ -136,7 +136,7 @@ struct dptnav_ctx {
   bool opt_deterministic = false;   // 1: static tile assignment instead of device-wide tickets (TileTickets): bit-reproducible gradients
   int opt_lstm4 = 1;          // 4-sequence recurrence tiles (lstm4.hip): 0 never, 1 for launches of up to 1.15 rounds of the chip, 2 whenever PRE16 is in use
   bool opt_split_bf16 = false;      // opt-in: LSTM recurrence on bf16 MFMAs with hi/lo-split operands (lstm16s.hip)
-  bool opt_fuse_attn = true;        // inference: K1 + K2 + K3 as one kernel (attn_block.hip) where it applies
+  bool opt_fuse_attn = true;        // inference: K1 + K2 + K3 as one kernel (attn_block2.hip; attn_block64.hip for 64 features) where it applies
   bool opt_gemm_t = true;           // training forward: the attention in-projection (128 -> 384) by gemm_t.hip instead of the GEMM engine
   bool opt_dgrad_r = true;          // training: the K = 128 data gradients with weight-gradient riders by dgrad_r.hip instead of the GEMM engine
   bool opt_dgrad_t = true;          // training: the K = 512 data gradient (d P W_ih) by dgrad_t.hip instead of the GEMM engine
@@ -595,12 +595,12 @@ inline bool lstm_use16(const dptnav_ctx* c, const SeqGeom& geom, int ndir, int64
 
 // ---- one TransformerDPRNN (dptn.py:36-52) ---------------------------------------------------------
 // chain: bit 0 -- the attention block PRODUCES its input rows itself, as the FFN half (K6) of the previous path (its hc /
-// y1 are still in the workspace; attn_block.hip prologue); bit 1 -- this path's K6 is left to the next path's block.
+// y1 are still in the workspace; the attention block's prologue); bit 1 -- this path's K6 is left to the next path's block.
 constexpr int CHAIN_PRO = 1, CHAIN_SKIP_FFN = 2;
 template <int N>
 bool path_fusable(const dptnav_ctx* c, int path, int B, int S) {
   const SeqGeom geom = make_geom(path, B, S, c->cfg.chunk_size);
-  // N = 128: attn_block.hip (fp32 and split variants); N = 64: attn_block64.hip (fp32 only)
+  // N = 128: attn_block2.hip (fp32), attn_block.hip (fp32 under attn_v2 = 0, and the split variant); N = 64: attn_block64.hip (fp32 only)
   return c->cfg.arch == 0 && (N == 128 || (N == 64 && !c->opt_split_bf16)) && c->opt_fuse_attn && geom.len <= ATTN_BLOCK_MAX_LEN &&
          c->cfg.num_heads == 4;
 }
@@ -784,114 +784,49 @@ static int try_dgrad_r(dptnav_ctx* c, Lane& lane, int cat, const char* what, Dgr
   return try_dedicated(c, lane, cat, what, true, [&](unsigned* q) { a.queue = q; return dgrad_r_launch(lane.st, a, c->num_cus, grid); }, took);
 }
 
-template <int N>
-int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, float* x_out, int B, int S,
-             const PathBufs* bufs = nullptr, int chain = 0) {
-  float* ws = run.ws;
-  const Plan& pl = run.pl;
-  Lane& lane = run.lane;
-  hipStream_t st = lane.st;
-  const PathBufs pb = bufs ? *bufs : inference_bufs(run);
-  constexpr int WR = N == 128 ? 1 : 2, WC = N == 128 ? 4 : 2, GROUP = N / 4, DH = N / 4;
-  constexpr int BM = 32 * WR;
-  const dptnav_config& g = c->cfg;
-  const PathWeights& w = c->pw[2 * block + path];
-  const int K = g.chunk_size;
-  const int64_t M = (int64_t)B * S * K;
-  const SeqGeom geom = make_geom(path, B, S, K);
-  float *qkv = pb.qkv, *att = pb.att, *y1 = pb.y1, *pre = pb.pre, *hc = pb.hc;
-  const int64_t ntiles = (M + BM - 1) / BM;
-  const bool dptn = g.arch == 0;
-  const float* lstm_in = dptn ? y1 : x_in;   // DPRNN feeds the chunk tokens straight into the LSTM (dprnn.py:37-40)
+// ---- the route of one path: which kernels it launches, decided once and ahead of the first launch --------------------
+enum AttnForm {
+  ATTN_NONE,          // DPRNN: no attention
+  ATTN_FUSED64,       // K1 + K2 + K3 in one launch, N = 64 (attn_block64.hip)
+  ATTN_FUSED128_V2,   // ... N = 128, both LayerNorms in fragment space (attn_block2.hip); persistent where PathRoute::persist
+  ATTN_FUSED128_V1,   // ... N = 128, the form before that and the split-precision one (attn_block.hip)
+  ATTN_SEPARATE       // K1, K2, K3 as three launches (training; what the fused kernels do not take)
+};
+enum LstmKernel { LSTM_16X, LSTM_16S, LSTM_4, LSTM_16, LSTM_32S, LSTM_32 };   // lstm16x.hip, lstm16s.hip, lstm4.hip, lstm16.hip, lstm.hip (split / fp32)
+struct PathRoute {
+  AttnForm attn;
+  bool prologue;      // CHAIN_PRO: the fused block starts with the previous path's K6
+  bool persist;       // ATTN_FUSED128_V2 as persistent workgroups (takes one sequence-ticket counter)
+  int persist_grid;   // ... at most this many of them
+  bool use16, split;  // K4 / K5 tile height (lstm_use16); split-precision K4 / K5 / K6
+  int nst16, nst4;    // sequence tiles of 16 / of 4
+  bool k4;            // the K4 launch runs (not under LSTM_16X: input projection inside the recurrence)
+  LstmKernel lstm;
+  bool skip_ffn;      // CHAIN_SKIP_FFN: K6 is left to the next path's block
+};
 
+template <int N>
+int route_path(dptnav_ctx* c, const Run& run, int block, int path, int B, int S, bool train, int chain, PathRoute* r) {
+  const PathWeights& w = c->pw[2 * block + path];
+  const SeqGeom geom = make_geom(path, B, S, c->cfg.chunk_size);
+  const int64_t M = (int64_t)B * S * c->cfg.chunk_size;
+  const bool dptn = c->cfg.arch == 0;
   // K1 + K2 + K3 in one launch (inference, N = 128, sequences of <= 160 positions): QKV and the attention output never
   // leave the chip -- 1 kB of HBM traffic per token instead of 5.5 kB
-  const bool fused = dptn && (!pb.train || c->opt_train_fuse_probe) && path_fusable<N>(c, path, B, S);
-  if (fused && (chain & CHAIN_PRO) && c->pw[2 * block + path - 1].ndir != 2)
+  const bool fused = dptn && (!train || c->opt_train_fuse_probe) && path_fusable<N>(c, path, B, S);
+  r->prologue = (chain & CHAIN_PRO) != 0;
+  if (fused && r->prologue && c->pw[2 * block + path - 1].ndir != 2)
     return c->fail(DPTNAV_ERR_INVALID, "internal: FFN prologue needs both LSTM directions of the previous path");
-  if (fused && N == 64) {
-    ProfScope ps(c, CAT_ATTN, st);
-    AttnFfnPrologue pro{};
-    if (chain & CHAIN_PRO) {
-      const PathWeights& pw = c->pw[2 * block + path - 1];
-      pro = AttnFfnPrologue{hc, pw.ffn_w, pw.ffn_b, pw.ln2_w, pw.ln2_b};
-    }
-    const int rc = attn_block64_launch(st, x_in, w.in_w, w.in_b, w.out_w, w.out_b, w.ln1_w, w.ln1_b, y1, geom,
-                                       (chain & CHAIN_PRO) ? &pro : nullptr);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention block (N = 64): %s", hipGetErrorString((hipError_t)rc));
-  } else if (fused) {
-    ProfScope ps(c, CAT_ATTN, st);
-    AttnFfnPrologue pro{};
-    if (chain & CHAIN_PRO) {
-      const PathWeights& pw = c->pw[2 * block + path - 1];
-      pro = AttnFfnPrologue{hc, pw.ffn_w, pw.ffn_b, pw.ln2_w, pw.ln2_b};
-    }
-    float* wpack = nullptr;
-    if (!c->opt_split_bf16) {
-      if (int rc = run_pack(c, run, PACK_ATTN, 2 * block + path, &wpack)) return rc;
-      if (chain & CHAIN_PRO) pro.wf = wpack - ATTN_PACK_FLOATS + ATTN_PACK_IN + ATTN_PACK_OUT;   // previous path's ffn.1 segment
-    }
-    unsigned* seq_queue = nullptr;      // persistent form: one sequence-ticket counter of the pass (zeroed with the GEMM engine's, begin_run)
-    // (1: only where a workgroup gets more than one sequence -- measured equal at best below that)
-    if (c->opt_attn_v2 && !c->opt_split_bf16 && (chain & CHAIN_PRO) && (c->opt_attn_persist > 1 || (c->opt_attn_persist == 1 && geom.nseq > c->num_cus))) {
-      seq_queue = lane.tk.take(1);
-      if (!seq_queue) return c->fail(DPTNAV_ERR_INVALID, "attention block: ticket counters exhausted");
-    }
-    const int rc = (c->opt_attn_v2 && !c->opt_split_bf16)
-                       ? attn_block2_launch(st, x_in, w.in_b, w.out_b, w.ln1_w, w.ln1_b, y1, geom, (chain & CHAIN_PRO) ? &pro : nullptr, wpack, seq_queue,
-                                            c->opt_attn_persist == 1 ? c->num_cus : c->opt_attn_persist)
-                       : attn_block_launch(st, x_in, w.in_w, w.in_b, w.out_w, w.out_b, w.ln1_w, w.ln1_b, y1, geom, c->opt_split_bf16,
-                                           (chain & CHAIN_PRO) ? &pro : nullptr, wpack);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention block: %s", hipGetErrorString((hipError_t)rc));
-  } else if (chain & CHAIN_PRO) {
-    return c->fail(DPTNAV_ERR_INVALID, "internal: FFN prologue requested for an unfused attention block");
-  }
-  // K1: qkv = x W_in^T + b_in                                  (nn.MultiheadAttention in-projection)
-  if (dptn && !fused) {
-    bool done = false;
-    if constexpr (N == 128) {
-      if (pb.train && c->opt_gemm_t) {      // training forward: gemm_t.hip on the fragment-order copy of W_in
-        float* wp = nullptr;
-        if (int rc = run_pack(c, run, PACK_INW, 2 * block + path, &wp)) return rc;
-        GemmTArgs ga{x_in, wp, w.in_b, qkv, M, 3 * N};
-        auto launch = [&](unsigned* q) { ga.queue = q; return gemm_t_launch(st, ga, c->num_cus); };
-        if (int rc = try_dedicated(c, lane, CAT_QKV, "qkv gemm", true, launch, &done)) return rc;
-      }
-    }
-    if (!done) {
-      ALoadDense al{x_in, M, N, BM};
-      EpiBiasStore ep{qkv, w.in_b, M, 3 * N, BM, 3 * N};
-      if (int rc = launch_gemm<N, 3, WR, WC>(c, lane, CAT_QKV, "qkv gemm", w.in_w, ntiles, 1, al, ep)) return rc;
-    }
-  }
-  // K2: softmax(Q K^T / sqrt(dh)) V per (sequence, head)
-  if (dptn && !fused)
-    if (int rc = launch_attn<DH>(c, qkv, att, N, geom, g.num_heads, st, c->drop_cfg(block, path, pb.train, run.half),
-                                 reinterpret_cast<float2*>(pb.astats), reinterpret_cast<unsigned long long*>(pb.amask)))
-      return rc;
-  // K3: y1 = LN1(att W_o^T + b_o + x)                           (dptn.py:46-47)
-  if (dptn && !fused) {
-    ALoadDense al{att, M, N, BM};
-    bool done = false;
-    {
-      if (pb.train && pb.zn1 && N == 128 && c->opt_fcln) {   // 16-token tiles, three workgroups per CU (fcln.hip)
-        FclnArgs fa{att, w.out_w, w.out_b, w.ln1_w, w.ln1_b, x_in, y1, pb.zn1, pb.rs1, M, N, N, /*pre_res*/ true, /*act*/ 0};
-        if (int rc = try_fcln(c, lane, fa, CAT_OUTPROJ, "fcln (out-projection)", &done)) return rc;
-      }
-      if (!done && pb.train && pb.zn1) {   // + zn / rstd on the tape for the LayerNorm backward
-        EpiBiasResLNSave<GROUP> ep{y1, w.out_b, x_in, w.ln1_w, w.ln1_b, M, N, BM, pb.zn1, pb.rs1};
-        if (int rc = launch_gemm<N, 1, WR, WC>(c, lane, CAT_OUTPROJ, "out-proj gemm (tape)", w.out_w, ntiles, 1, al, ep)) return rc;
-        done = true;
-      }
-    }
-    if (!done) {
-      EpiBiasResLN<GROUP> ep{y1, w.out_b, x_in, w.ln1_w, w.ln1_b, M, N, BM};
-      if (int rc = launch_gemm<N, 1, WR, WC>(c, lane, CAT_OUTPROJ, "out-proj gemm", w.out_w, ntiles, 1, al, ep)) return rc;
-    }
-  }
+  if (!fused && r->prologue) return c->fail(DPTNAV_ERR_INVALID, "internal: FFN prologue requested for an unfused attention block");
+  const bool v2 = c->opt_attn_v2 && !c->opt_split_bf16;
+  r->attn = !dptn ? ATTN_NONE : !fused ? ATTN_SEPARATE : N == 64 ? ATTN_FUSED64 : v2 ? ATTN_FUSED128_V2 : ATTN_FUSED128_V1;
+  // (1: only where a workgroup gets more than one sequence -- measured equal at best below that)
+  r->persist = r->attn == ATTN_FUSED128_V2 && r->prologue && (c->opt_attn_persist > 1 || (c->opt_attn_persist == 1 && geom.nseq > c->num_cus));
+  r->persist_grid = c->opt_attn_persist == 1 ? c->num_cus : c->opt_attn_persist;
+
   const int nst16 = (geom.nseq + 15) / 16;
   const bool use16 = lstm_use16(c, geom, w.ndir, M);
-  const bool split = c->opt_split_bf16 && !pb.train;
+  const bool split = c->opt_split_bf16 && !train;
   // low-latency recurrence on 4-sequence tiles (reads PRE16): small launches, where 16-sequence tiles leave the chip idle.
   // A step of 4 sequences takes ~1.25 us against ~4.3 us for 16 (alone on the chip, bs = 1: 0.19 ms per launch instead of
   // 0.64 ms), so up to a little over one round of the chip it is the shorter launch AND the smaller CU-time.  Measured
@@ -903,172 +838,276 @@ int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, fl
   // tiles (B = 8: 16.47 -> 15.68 ms, B = 10: 19.64 -> 19.12 ms); from B = 12 on the chip is full and the 16-sequence tiles' lower
   // CU-time wins (23.07 vs 22.2 ms).
   const int rounds20 = (run.batch_total > 0 && run.batch_total <= 10) ? 30 : 23;      // launch size limit in twentieths of a round
-  const bool use4 = use16 && !split && !pb.train && !c->opt_lstm_stamps &&
+  const bool use4 = use16 && !split && !train && !c->opt_lstm_stamps &&
                     (c->opt_lstm4 == 2 || (c->opt_lstm4 == 1 && 20 * nst4 * w.ndir <= rounds20 * c->num_cus));
   // num_features = 64: input projection inside the recurrence (lstm16x.hip) -- no K4 launch, no pre-activation tensor
   // (the 128-feature kernel addresses hc and its input rows with 32-bit byte offsets: both tensors below 4 GiB)
   const bool fits32 = (uint64_t)(M + (int64_t)geom.S * geom.K) * (uint64_t)(w.ndir * LSTM_H) * 4u < (1ull << 32);
-  const bool usex = (N == 64 ? c->opt_fuse_pre : (run.fuse128 && fits32)) && c->opt_lstm16 && !pb.train && !split && !use4 && !c->opt_lstm_stamps;
-  // K4: LSTM pre-activations for every (direction, sequence tile, position), in accumulator-fragment order
-  if (!usex) {
-    ALoadSeqTile al{lstm_in, N, geom};
-    const int64_t nt4 = (int64_t)geom.nst * geom.len;
-    int rc;
-    // fp32 form: W_ih from its fragment-order copy (made for all paths at the start of the pass, or here for this path)
-    const float *wih0 = w.w_ih[0], *wih1 = w.w_ih[1];
-    int ldw_ih = N;
-    if (c->opt_pack_wih && !split) {
-      float* pk = nullptr;
-      if (int rcp = run_pack(c, run, PACK_WIH, 2 * block + path, &pk)) return rcp;
-      wih0 = pk;
-      wih1 = pk + 4 * LSTM_H * N;
-      ldw_ih = 0;
+  const bool usex = (N == 64 ? c->opt_fuse_pre : (run.fuse128 && fits32)) && c->opt_lstm16 && !train && !split && !use4 && !c->opt_lstm_stamps;
+  r->use16 = use16;
+  r->split = split;
+  r->nst16 = nst16;
+  r->nst4 = nst4;
+  r->k4 = !usex;
+  r->lstm = usex ? LSTM_16X : (use16 && split) ? LSTM_16S : use4 ? LSTM_4 : use16 ? LSTM_16 : split ? LSTM_32S : LSTM_32;
+  r->skip_ffn = dptn && (chain & CHAIN_SKIP_FFN) != 0;   // (DPRNN has no next block to ride in)
+  return DPTNAV_OK;
+}
+
+// ---- the four stages of one path --------------------------------------------------------------------
+// GEMM-engine tile shape of the N-wide products of a path
+template <int N>
+struct PathTile {
+  static constexpr int WR = N == 128 ? 1 : 2, WC = N == 128 ? 4 : 2, GROUP = N / 4, DH = N / 4, BM = 32 * WR;
+};
+// What every stage reads; run_path builds it once.
+struct PathCall {
+  dptnav_ctx* c;
+  Run& run;
+  const PathWeights& w;
+  PathBufs pb;
+  SeqGeom geom;
+  int block, path;
+  int64_t M, ntiles;   // tokens, and GEMM-engine tiles of PathTile::BM tokens
+  const float* x_in;
+  float* x_out;
+  int slot() const { return 2 * block + path; }   // in dptnav_ctx::pw and in the weight packs
+  bool dptn() const { return c->cfg.arch == 0; }
+  const float* lstm_in() const { return dptn() ? pb.y1 : x_in; }   // DPRNN feeds the chunk tokens straight into the LSTM (dprnn.py:37-40)
+};
+
+// K1, K2, K3 as three launches
+template <int N>
+int attention_separate(const PathCall& pc) {
+  using T = PathTile<N>;
+  dptnav_ctx* c = pc.c;
+  Lane& lane = pc.run.lane;
+  const PathWeights& w = pc.w;
+  const PathBufs& pb = pc.pb;
+  const int64_t M = pc.M;
+  // K1: qkv = x W_in^T + b_in                                  (nn.MultiheadAttention in-projection)
+  bool took = false;
+  if constexpr (N == 128) {
+    if (pb.train && c->opt_gemm_t) {      // training forward: gemm_t.hip on the fragment-order copy of W_in
+      float* wp = nullptr;
+      if (int rc = run_pack(c, pc.run, PACK_INW, pc.slot(), &wp)) return rc;
+      GemmTArgs ga{pc.x_in, wp, w.in_b, pb.qkv, M, 3 * N};
+      auto launch = [&](unsigned* q) { ga.queue = q; return gemm_t_launch(lane.st, ga, c->num_cus); };
+      if (int rc = try_dedicated(c, lane, CAT_QKV, "qkv gemm", true, launch, &took)) return rc;
     }
-    if (use16 && split) {   // opt-in split-precision mode (bf16 hi/lo operands, fp32 accumulation)
-      EpiLstmPre16 ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom, nst16};
-      rc = launch_gemm<N, 4, 1, 4, false, true>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
-    } else if (use16) {
-      EpiLstmPre16 ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom, nst16};
-      rc = launch_gemm<N, 4, 1, 4>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
-    } else if (split) {
-      EpiLstmPre ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom};
-      rc = launch_gemm<N, 4, 1, 4, false, true>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm (split)", w.w_ih[0], nt4, w.ndir, al, ep, w.w_ih[1]);
-    } else {
-      EpiLstmPre ep{pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, geom};
-      rc = launch_gemm<N, 4, 1, 4>(c, lane, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
-    }
-    if (rc) return rc;
   }
-  // K5: recurrence, both directions concurrently; writes ReLU(h) (ffn[0], dptn.py:31)
-  if (run.lstm_wait && hipStreamWaitEvent(st, run.lstm_wait, 0) != hipSuccess)
-    return c->fail(DPTNAV_ERR_HIP, "lstm stagger wait");
-  if (usex) {
-    float* xpack = nullptr;
-    if (c->opt_lstm_prologue)
-      if (int rcp = run_pack(c, run, PACK_X16, 2 * block + path, &xpack)) return rcp;
-    ProfScope ps(c, CAT_LSTM, st);
-    const int rc = lstm16x_launch(N, dptn, nst16, w.ndir, st, lstm_in, N, w.w_ih, w.b_ih, w.b_hh, w.w_hh, hc, w.ndir * LSTM_H,
-                                  M, geom, c->opt_lstm_sched, xpack);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16x: %s", hipGetErrorString((hipError_t)rc));
-  } else if (use16 && split) {
-    ProfScope ps(c, CAT_LSTM, st);
-    const int rc = lstm16s_launch(c->cfg.arch == 0, nst16, w.ndir, st, pre, w.w_hh[0], w.w_hh[1], hc, w.ndir * LSTM_H, (int)M, geom);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16s: %s", hipGetErrorString((hipError_t)rc));
-  } else if (use4) {
-    const float *whh0 = w.w_hh[0], *whh1 = w.w_hh[1];
-    if (c->opt_pack_whh && 2 * (int)c->pw.size() <= LSTM4_PACK_MAX) {   // (the pack is one launch)
-      float* pk = nullptr;
-      if (int rcp = run_pack(c, run, PACK_WHH4, 2 * block + path, &pk)) return rcp;
-      whh0 = pk;
-      whh1 = pk + 4 * LSTM_H * LSTM_H;
-    }
-    ProfScope ps(c, CAT_LSTM, st);
-    const int rc = lstm4_launch(c->cfg.arch == 0, nst4, nst16, w.ndir, st, pre, whh0, whh1, hc,
-                                w.ndir * LSTM_H, (int)M, geom, whh0 != w.w_hh[0]);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm4: %s", hipGetErrorString((hipError_t)rc));
-  } else if (use16) {
-    // lstm_stamps: diagnostic builds; lstm_diag > 0 are timing-only ablations (wrong results), see lstm16.hip
-    const int variant = pb.train ? L16_VARIANT_TRAIN : (c->opt_lstm_stamps ? 1 + c->opt_lstm_diag : 0);
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(ws + pl.stamps);   // room: nst16 <= 2 nst
-    ProfScope ps(c, CAT_LSTM, st);
-    // DPTN inference stores ReLU(h) (ffn = ReLU -> Linear, dptn.py:31); training keeps raw h for the tape, DPRNN
-    // feeds fc directly
-    const int rc = lstm16_launch(variant, c->cfg.arch == 0 && !pb.train, nst16, w.ndir, st, pre, w.w_hh[0], w.w_hh[1], hc,
-                                 w.ndir * LSTM_H, (int)M, geom, stamps, pb.gates, pb.cst);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm16: %s", hipGetErrorString((hipError_t)rc));
-  } else if (split) {
-    ProfScope ps(c, CAT_LSTM, st);
-    const int rc = lstm32s_launch(c->cfg.arch == 0, geom.nst, w.ndir, st, pre, w.w_hh[0], w.w_hh[1], hc, w.ndir * LSTM_H, (int)M, geom);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm32s: %s", hipGetErrorString((hipError_t)rc));
-  } else {
-    // diagnostic stamps land behind the dump rows of hc (see make_plan)
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(ws + pl.stamps);
-    ProfScope ps(c, CAT_LSTM, st);
-    // DPTN inference stores ReLU(h) (ffn = ReLU -> Linear, dptn.py:31); training keeps raw h for the tape, DPRNN
-    // feeds fc directly
-    const int rc = lstm32_launch(c->opt_lstm_stamps && !pb.train, pb.train, c->cfg.arch == 0 && !pb.train, geom.nst, w.ndir,
-                                 st, pre, w.w_hh[0], w.w_hh[1], hc, w.ndir * LSTM_H, (int)M, geom, stamps, pb.gates, pb.cst);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm: %s", hipGetErrorString((hipError_t)rc));
+  if (!took) {
+    ALoadDense al{pc.x_in, M, N, T::BM};
+    EpiBiasStore ep{pb.qkv, w.in_b, M, 3 * N, T::BM, 3 * N};
+    if (int rc = launch_gemm<N, 3, T::WR, T::WC>(c, lane, CAT_QKV, "qkv gemm", w.in_w, pc.ntiles, 1, al, ep)) return rc;
   }
-  if (run.lstm_record && hipEventRecord(run.lstm_record, st) != hipSuccess)
-    return c->fail(DPTNAV_ERR_HIP, "lstm stagger record");
-  // K6 (DPRNN): x_out = LayerNorm(h W_fc^T + b_fc) + x_in       (dprnn.py:41-45, 83-87)
-  if (!dptn) {
-    EpiBiasLNRes<GROUP> ep{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM};
-    if (w.ndir == 2 && split) {
-      ALoadDense al{hc, M, 2 * LSTM_H, BM};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, lane, CAT_FFN, "fc gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
-    } else if (w.ndir == 2 && pb.train && pb.zn2) {   // + zn / rstd on the tape for the LayerNorm backward
-      ALoadDense al{hc, M, 2 * LSTM_H, BM};
-      EpiBiasLNResSave<GROUP> eps{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
-    } else if (w.ndir == 2) {
-      bool done = false;
-      if (N == 64 && c->opt_fcln) {     // 16-token tiles, several workgroups per CU (fcln.hip)
-        FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, x_in, x_out, nullptr, nullptr, M, 2 * LSTM_H, N, /*pre_res*/ false, /*act*/ 0, c->opt_fcln == 2 ? 3 : 2};
-        if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (fc)", &done)) return rc;
-      }
-      if (!done) {
-        ALoadDense al{hc, M, 2 * LSTM_H, BM};
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
-      }
-    } else if (pb.train && pb.zn2) {
-      ALoadDense al{hc, M, LSTM_H, BM};
-      EpiBiasLNResSave<GROUP> eps{x_out, w.ffn_b, x_in, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
-    } else {
-      ALoadDense al{hc, M, LSTM_H, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "fc gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
-    }
+  // K2: softmax(Q K^T / sqrt(dh)) V per (sequence, head)
+  if (int rc = launch_attn<T::DH>(c, pb.qkv, pb.att, N, pc.geom, c->cfg.num_heads, lane.st, c->drop_cfg(pc.block, pc.path, pb.train, pc.run.half),
+                                  reinterpret_cast<float2*>(pb.astats), reinterpret_cast<unsigned long long*>(pb.amask)))
+    return rc;
+  // K3: y1 = LN1(att W_o^T + b_o + x)                           (dptn.py:46-47)
+  const bool tape = pb.train && pb.zn1;   // + zn / rstd on the tape for the LayerNorm backward
+  ALoadDense al{pb.att, M, N, T::BM};
+  took = false;
+  if (tape && N == 128 && c->opt_fcln) {   // 16-token tiles, three workgroups per CU (fcln.hip)
+    FclnArgs fa{pb.att, w.out_w, w.out_b, w.ln1_w, w.ln1_b, pc.x_in, pb.y1, pb.zn1, pb.rs1, M, N, N, /*pre_res*/ true, /*act*/ 0};
+    if (int rc = try_fcln(c, lane, fa, CAT_OUTPROJ, "fcln (out-projection)", &took)) return rc;
+  }
+  if (took) return DPTNAV_OK;
+  if (tape) {
+    EpiBiasResLNSave<T::GROUP> ep{pb.y1, w.out_b, pc.x_in, w.ln1_w, w.ln1_b, M, N, T::BM, pb.zn1, pb.rs1};
+    return launch_gemm<N, 1, T::WR, T::WC>(c, lane, CAT_OUTPROJ, "out-proj gemm (tape)", w.out_w, pc.ntiles, 1, al, ep);
+  }
+  EpiBiasResLN<T::GROUP> ep{pb.y1, w.out_b, pc.x_in, w.ln1_w, w.ln1_b, M, N, T::BM};
+  return launch_gemm<N, 1, T::WR, T::WC>(c, lane, CAT_OUTPROJ, "out-proj gemm", w.out_w, pc.ntiles, 1, al, ep);
+}
+
+template <int N>
+int attention_stage(const PathCall& pc, const PathRoute& r) {
+  if (r.attn == ATTN_NONE) return DPTNAV_OK;
+  if (r.attn == ATTN_SEPARATE) return attention_separate<N>(pc);
+  dptnav_ctx* c = pc.c;
+  Lane& lane = pc.run.lane;
+  const PathWeights& w = pc.w;
+  ProfScope ps(c, CAT_ATTN, lane.st);
+  AttnFfnPrologue pro{};
+  if (r.prologue) {
+    const PathWeights& pw = c->pw[pc.slot() - 1];
+    pro = AttnFfnPrologue{pc.pb.hc, pw.ffn_w, pw.ffn_b, pw.ln2_w, pw.ln2_b};
+  }
+  const AttnFfnPrologue* prop = r.prologue ? &pro : nullptr;
+  if (r.attn == ATTN_FUSED64) {
+    const int rc = attn_block64_launch(lane.st, pc.x_in, w.in_w, w.in_b, w.out_w, w.out_b, w.ln1_w, w.ln1_b, pc.pb.y1, pc.geom, prop);
+    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention block (N = 64): %s", hipGetErrorString((hipError_t)rc));
     return DPTNAV_OK;
   }
-  // K6: x_out = LN2(relu(h) W_f^T + b_f + y1)                    (dptn.py:50-51)
-  if (chain & CHAIN_SKIP_FFN) return DPTNAV_OK;   // done by the next path's attention block (its prologue)
-  {
-    EpiBiasResLN<GROUP> ep{x_out, w.ffn_b, y1, w.ln2_w, w.ln2_b, M, N, BM};
-    // (training keeps the raw h on the tape and applies ffn[0] = ReLU while loading)
-    if (w.ndir == 2 && split) {
-      ALoadCols al{hc, M, 2 * LSTM_H, 0, BM};
-      if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC, false, true>(c, lane, CAT_FFN, "ffn gemm (split)", w.ffn_w, ntiles, 1, al, ep)) return rc;
-    } else if (w.ndir == 2 && pb.train) {
-      ALoadColsReLU al{hc, M, 2 * LSTM_H, 0, BM};
-      bool done = false;
-      {
-        if (pb.zn2 && N == 128 && c->opt_fcln) {     // ReLU while loading, 16-token tiles, two workgroups per CU (fcln.hip)
-          FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, y1, x_out, pb.zn2, pb.rs2, M, 2 * LSTM_H, N, /*pre_res*/ true, /*act: ReLU*/ 1};
-          if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (ffn)", &done)) return rc;
-        }
-        if (!done && pb.zn2) {
-          EpiBiasResLNSave<GROUP> eps{x_out, w.ffn_b, y1, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-          if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
-          done = true;
-        }
-      }
-      if (!done)
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
-    } else if (w.ndir == 2) {
-      bool done = false;
-      if (c->opt_fcln) {       // (the paths whose FFN does not ride in the next attention block; hc = ReLU(h) already)
-        FclnArgs fa{hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, y1, x_out, nullptr, nullptr, M, 2 * LSTM_H, N, /*pre_res*/ true, /*act*/ 0};
-        if (int rc = try_fcln(c, lane, fa, CAT_FFN, "fcln (ffn)", &done)) return rc;
-      }
-      if (!done) {
-        ALoadCols al{hc, M, 2 * LSTM_H, 0, BM};
-        if (int rc = launch_gemm<2 * LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
-      }
-    } else if (pb.train && pb.zn2) {
-      ALoadColsReLU al{hc, M, LSTM_H, 0, BM};
-      EpiBiasResLNSave<GROUP> eps{x_out, w.ffn_b, y1, w.ln2_w, w.ln2_b, M, N, BM, pb.zn2, pb.rs2};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm (tape)", w.ffn_w, ntiles, 1, al, eps)) return rc;
-    } else if (pb.train) {
-      ALoadColsReLU al{hc, M, LSTM_H, 0, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
-    } else {
-      ALoadCols al{hc, M, LSTM_H, 0, BM};
-      if (int rc = launch_gemm<LSTM_H, 1, WR, WC>(c, lane, CAT_FFN, "ffn gemm", w.ffn_w, ntiles, 1, al, ep)) return rc;
+  float* wpack = nullptr;
+  if (!c->opt_split_bf16) {
+    if (int rc = run_pack(c, pc.run, PACK_ATTN, pc.slot(), &wpack)) return rc;
+    if (r.prologue) pro.wf = wpack - ATTN_PACK_FLOATS + ATTN_PACK_IN + ATTN_PACK_OUT;   // previous path's ffn.1 segment
+  }
+  unsigned* seq_queue = nullptr;      // persistent form: one sequence-ticket counter of the pass (zeroed with the GEMM engine's, begin_run)
+  if (r.persist) {
+    seq_queue = lane.tk.take(1);
+    if (!seq_queue) return c->fail(DPTNAV_ERR_INVALID, "attention block: ticket counters exhausted");
+  }
+  const int rc = r.attn == ATTN_FUSED128_V2
+                     ? attn_block2_launch(lane.st, pc.x_in, w.in_b, w.out_b, w.ln1_w, w.ln1_b, pc.pb.y1, pc.geom, prop, wpack, seq_queue, r.persist_grid)
+                     : attn_block_launch(lane.st, pc.x_in, w.in_w, w.in_b, w.out_w, w.out_b, w.ln1_w, w.ln1_b, pc.pb.y1, pc.geom, c->opt_split_bf16,
+                                         prop, wpack);
+  if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "attention block: %s", hipGetErrorString((hipError_t)rc));
+  return DPTNAV_OK;
+}
+
+// K4: LSTM pre-activations for every (direction, sequence tile, position), in accumulator-fragment order
+template <int N>
+int lstm_pre_stage(const PathCall& pc, const PathRoute& r) {
+  if (!r.k4) return DPTNAV_OK;
+  dptnav_ctx* c = pc.c;
+  const PathWeights& w = pc.w;
+  // fp32 form: W_ih from its fragment-order copy (made for all paths at the start of the pass, or here for this path);
+  // ldw = 0 marks the copy.  The split form (bf16 hi/lo operands, fp32 accumulation; opt-in) reads the nn.LSTM tensors.
+  const float *wih0 = w.w_ih[0], *wih1 = w.w_ih[1];
+  int ldw_ih = N;
+  if (c->opt_pack_wih && !r.split) {
+    float* pk = nullptr;
+    if (int rc = run_pack(c, pc.run, PACK_WIH, pc.slot(), &pk)) return rc;
+    wih0 = pk;
+    wih1 = pk + 4 * LSTM_H * N;
+    ldw_ih = 0;
+  }
+  const ALoadSeqTile al{pc.lstm_in(), N, pc.geom};
+  const int64_t nt4 = (int64_t)pc.geom.nst * pc.geom.len;
+  auto launch = [&](const auto& ep) {
+    return r.split ? launch_gemm<N, 4, 1, 4, false, true>(c, pc.run.lane, CAT_LSTM_PRE, "lstm-pre gemm (split)", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih)
+                   : launch_gemm<N, 4, 1, 4>(c, pc.run.lane, CAT_LSTM_PRE, "lstm-pre gemm", wih0, nt4, w.ndir, al, ep, wih1, ldw_ih);
+  };
+  if (r.use16) return launch(EpiLstmPre16{pc.pb.pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, pc.geom, r.nst16});
+  return launch(EpiLstmPre{pc.pb.pre, {w.b_ih[0], w.b_ih[1]}, {w.b_hh[0], w.b_hh[1]}, pc.geom});
+}
+
+// K5: recurrence, both directions concurrently.  DPTN inference stores ReLU(h) (ffn = ReLU -> Linear, dptn.py:31); training
+// keeps raw h for the tape, DPRNN feeds fc directly.
+template <int N>
+int recurrence_stage(const PathCall& pc, const PathRoute& r) {
+  dptnav_ctx* c = pc.c;
+  Run& run = pc.run;
+  hipStream_t st = run.lane.st;
+  const PathWeights& w = pc.w;
+  const PathBufs& pb = pc.pb;
+  const SeqGeom& geom = pc.geom;
+  const bool dptn = pc.dptn();
+  const int ldh = w.ndir * LSTM_H, M = (int)pc.M;
+  float *pre = pb.pre, *hc = pb.hc;
+  // diagnostic stamps land behind the dump rows of hc (see make_plan); room: nst16 <= 2 nst
+  unsigned long long* stamps = reinterpret_cast<unsigned long long*>(run.ws + run.pl.stamps);
+  // the packed copies two of the kernels read: made on the stream, in front of the launch
+  float* xpack = nullptr;
+  if (r.lstm == LSTM_16X && c->opt_lstm_prologue)
+    if (int rc = run_pack(c, run, PACK_X16, pc.slot(), &xpack)) return rc;
+  const float *whh0 = w.w_hh[0], *whh1 = w.w_hh[1];
+  if (r.lstm == LSTM_4 && c->opt_pack_whh && 2 * (int)c->pw.size() <= LSTM4_PACK_MAX) {   // (the pack is one launch)
+    float* pk = nullptr;
+    if (int rc = run_pack(c, run, PACK_WHH4, pc.slot(), &pk)) return rc;
+    whh0 = pk;
+    whh1 = pk + 4 * LSTM_H * LSTM_H;
+  }
+  // lstm_stamps: diagnostic builds; lstm_diag > 0 are timing-only ablations (wrong results), see lstm16.hip
+  const int variant16 = pb.train ? L16_VARIANT_TRAIN : (c->opt_lstm_stamps ? 1 + c->opt_lstm_diag : 0);
+  static const char* const names[] = {"lstm16x", "lstm16s", "lstm4", "lstm16", "lstm32s", "lstm"};   // by LstmKernel
+  ProfScope ps(c, CAT_LSTM, st);
+  int rc = 0;   // hipError_t of the launch
+  switch (r.lstm) {
+    case LSTM_16X: rc = lstm16x_launch(N, dptn, r.nst16, w.ndir, st, pc.lstm_in(), N, w.w_ih, w.b_ih, w.b_hh, w.w_hh, hc, ldh, pc.M, geom, c->opt_lstm_sched, xpack); break;
+    case LSTM_16S: rc = lstm16s_launch(dptn, r.nst16, w.ndir, st, pre, whh0, whh1, hc, ldh, M, geom); break;
+    case LSTM_4: rc = lstm4_launch(dptn, r.nst4, r.nst16, w.ndir, st, pre, whh0, whh1, hc, ldh, M, geom, whh0 != w.w_hh[0]); break;
+    case LSTM_16: rc = lstm16_launch(variant16, dptn && !pb.train, r.nst16, w.ndir, st, pre, whh0, whh1, hc, ldh, M, geom, stamps, pb.gates, pb.cst); break;
+    case LSTM_32S: rc = lstm32s_launch(dptn, geom.nst, w.ndir, st, pre, whh0, whh1, hc, ldh, M, geom); break;
+    case LSTM_32: rc = lstm32_launch(c->opt_lstm_stamps && !pb.train, pb.train, dptn && !pb.train, geom.nst, w.ndir, st, pre, whh0, whh1, hc, ldh, M, geom, stamps, pb.gates, pb.cst); break;
+  }
+  if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "%s: %s", names[r.lstm], hipGetErrorString((hipError_t)rc));
+  return DPTNAV_OK;
+}
+
+// K6 on the GEMM engine.  RES_FIRST: the residual goes in before the LayerNorm (DPTN) or after it (DPRNN).  TAPE says that the
+// loader has the tape instantiation (the training loaders, never SPLIT); `tape` that this pass wants zn / rstd for the
+// LayerNorm backward.
+template <int N, int KIN, bool RES_FIRST, bool SPLIT, bool TAPE, class AL>
+int ffn_gemm(const PathCall& pc, const AL& al, bool tape) {
+  using T = PathTile<N>;
+  using Epi = std::conditional_t<RES_FIRST, EpiBiasResLN<T::GROUP>, EpiBiasLNRes<T::GROUP>>;
+  using EpiSave = std::conditional_t<RES_FIRST, EpiBiasResLNSave<T::GROUP>, EpiBiasLNResSave<T::GROUP>>;
+  static_assert(!(SPLIT && TAPE), "no split-precision GEMM with the tape epilogue");
+  const PathWeights& w = pc.w;
+  const float* res = RES_FIRST ? pc.pb.y1 : pc.x_in;
+  if constexpr (TAPE) {
+    if (tape) {
+      EpiSave eps{pc.x_out, w.ffn_b, res, w.ln2_w, w.ln2_b, pc.M, N, T::BM, pc.pb.zn2, pc.pb.rs2};
+      return launch_gemm<KIN, 1, T::WR, T::WC>(pc.c, pc.run.lane, CAT_FFN, RES_FIRST ? "ffn gemm (tape)" : "fc gemm (tape)", w.ffn_w, pc.ntiles, 1, al, eps);
     }
   }
-  return DPTNAV_OK;
+  Epi ep{pc.x_out, w.ffn_b, res, w.ln2_w, w.ln2_b, pc.M, N, T::BM};
+  const char* what = SPLIT ? (RES_FIRST ? "ffn gemm (split)" : "fc gemm (split)") : (RES_FIRST ? "ffn gemm" : "fc gemm");
+  return launch_gemm<KIN, 1, T::WR, T::WC, false, SPLIT>(pc.c, pc.run.lane, CAT_FFN, what, w.ffn_w, pc.ntiles, 1, al, ep);
+}
+
+// K6 (DPTN):  x_out = LN2(relu(h) W_f^T + b_f + y1)            (dptn.py:50-51)
+// K6 (DPRNN): x_out = LayerNorm(h W_fc^T + b_fc) + x_in         (dprnn.py:41-45, 83-87)
+// With both directions: the split GEMM under split_bf16; else fcln.hip first where it does the shape (16-token tiles, several
+// workgroups per CU), the GEMM engine behind it.  With one direction: the GEMM engine only, never split.
+template <int N, int NDIR>
+int ffn_stage_dirs(const PathCall& pc, const PathRoute& r) {
+  constexpr int KIN = NDIR * LSTM_H, BM = PathTile<N>::BM;
+  dptnav_ctx* c = pc.c;
+  const PathWeights& w = pc.w;
+  const PathBufs& pb = pc.pb;
+  const bool dptn = pc.dptn();
+  const bool tape = pb.train && pb.zn2;   // + zn / rstd on the tape for the LayerNorm backward
+  if constexpr (NDIR == 2) {
+    if (r.split)
+      return dptn ? ffn_gemm<N, KIN, true, true, false>(pc, ALoadCols{pb.hc, pc.M, KIN, 0, BM}, false)
+                  : ffn_gemm<N, KIN, false, true, false>(pc, ALoadDense{pb.hc, pc.M, KIN, BM}, false);
+    // DPTN: inference at either width (the paths whose FFN does not ride in the next attention block; hc = ReLU(h) already),
+    // training with the tape at N = 128 (ReLU while loading).  DPRNN: N = 64 without the tape; fcln = 2: 3 tiles ahead, two workgroups per CU.
+    const bool fcln = c->opt_fcln && (dptn ? (!pb.train || (pb.zn2 && N == 128)) : (!tape && N == 64));
+    if (fcln) {
+      bool took = false;
+      FclnArgs fa{pb.hc, w.ffn_w, w.ffn_b, w.ln2_w, w.ln2_b, dptn ? pb.y1 : pc.x_in, pc.x_out, tape ? pb.zn2 : nullptr, tape ? pb.rs2 : nullptr,
+                  pc.M, KIN, N, /*pre_res*/ dptn, /*act: ReLU*/ dptn && pb.train ? 1 : 0, !dptn && c->opt_fcln == 2 ? 3 : 2};
+      if (int rc = try_fcln(c, pc.run.lane, fa, CAT_FFN, dptn ? "fcln (ffn)" : "fcln (fc)", &took)) return rc;
+      if (took) return DPTNAV_OK;
+    }
+  }
+  if (!dptn) return ffn_gemm<N, KIN, false, false, true>(pc, ALoadDense{pb.hc, pc.M, KIN, BM}, tape);
+  // (training keeps the raw h on the tape and applies ffn[0] = ReLU while loading)
+  if (pb.train) return ffn_gemm<N, KIN, true, false, true>(pc, ALoadColsReLU{pb.hc, pc.M, KIN, 0, BM}, tape);
+  return ffn_gemm<N, KIN, true, false, false>(pc, ALoadCols{pb.hc, pc.M, KIN, 0, BM}, false);
+}
+template <int N>
+int ffn_stage(const PathCall& pc, const PathRoute& r) {
+  if (r.skip_ffn) return DPTNAV_OK;   // done by the next path's attention block (its prologue)
+  return pc.w.ndir == 2 ? ffn_stage_dirs<N, 2>(pc, r) : ffn_stage_dirs<N, 1>(pc, r);
+}
+
+// ---- one path: route, then the stages ---------------------------------------------------------------
+template <int N>
+int run_path(dptnav_ctx* c, Run& run, int block, int path, const float* x_in, float* x_out, int B, int S,
+             const PathBufs* bufs = nullptr, int chain = 0) {
+  const PathBufs pb = bufs ? *bufs : inference_bufs(run);
+  PathRoute r;
+  if (int rc = route_path<N>(c, run, block, path, B, S, pb.train, chain, &r)) return rc;
+  const int64_t M = (int64_t)B * S * c->cfg.chunk_size;
+  const PathCall pc{c, run, c->pw[2 * block + path], pb, make_geom(path, B, S, c->cfg.chunk_size), block, path,
+                    M, (M + PathTile<N>::BM - 1) / PathTile<N>::BM, x_in, x_out};
+  hipStream_t st = run.lane.st;
+  if (int rc = attention_stage<N>(pc, r)) return rc;
+  if (int rc = lstm_pre_stage<N>(pc, r)) return rc;
+  if (run.lstm_wait && hipStreamWaitEvent(st, run.lstm_wait, 0) != hipSuccess)
+    return c->fail(DPTNAV_ERR_HIP, "lstm stagger wait");
+  if (int rc = recurrence_stage<N>(pc, r)) return rc;
+  if (run.lstm_record && hipEventRecord(run.lstm_record, st) != hipSuccess)
+    return c->fail(DPTNAV_ERR_HIP, "lstm stagger record");
+  return ffn_stage<N>(pc, r);
 }
 
 template <int N>
@@ -1605,16 +1644,16 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
         EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, 2 * LSTM_H, 32, 2 * LSTM_H};
         float* slab = br.ws + br.pl.slab;
         int rgrid = 0;
-        bool t = false;
+        bool took = false;
         if (c->opt_dgrad_r) {
           const DgradRArgs a{DZ, wpk + BWD_PACK_FFNW, hc, DHb, M, 2 * LSTM_H, /*relu_gate*/ true, nullptr, slab,
                              slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, BWD_SLAB_WGS};
-          if (int rc = try_dgrad_r(c, lane, CAT_FFN, "d h + d ffn weight", a, &rgrid, &t)) return rc;
+          if (int rc = try_dgrad_r(c, lane, CAT_FFN, "d h + d ffn weight", a, &rgrid, &took)) return rc;
         }
         // (grid known only after the occupancy query inside: the column-sum rows go behind BWD_SLAB_WGS partial tiles)
         WgradRider<2 * LSTM_H, ALoadColsReLU, true> rd{ALoadColsReLU{hc, M, 2 * LSTM_H, 0, 32}, slab,
                                                        slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, M};
-        if (!t)
+        if (!took)
           if (int rc = launch_gemm<N, 2, 1, 4, true, false>(c, lane, CAT_FFN, "d h + d ffn weight", w.ffn_w, ntiles, 1, al, ep, nullptr,
                                                             2 * LSTM_H, &rgrid, rd))
             return rc;
@@ -1716,12 +1755,12 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   // 6. d y1 = dz2 (residual) + dG_f W_ih_f + dG_b W_ih_b
   for (int d = 0; d < nd; ++d) {
     if constexpr (N == 128) {
-      bool t = false;
+      bool took = false;
       if (c->opt_dgrad_t) {
         const DgradTArgs a{DG + d * 512, nd * 512, wpk + BWD_PACK_WIH + (size_t)d * 512 * 128, d == 0 ? DZ : DY1, DY1, M, 512};
-        if (int rc = try_dgrad_t(c, lane, CAT_LSTM_PRE, "d y1", a, &t)) return rc;
+        if (int rc = try_dgrad_t(c, lane, CAT_LSTM_PRE, "d y1", a, &took)) return rc;
       }
-      if (t) continue;
+      if (took) continue;
       ALoadCols al{DG, M, nd * 512, d * 512, 32};
       EpiAddMaskStoreT<true, false> ep{DY1, d == 0 ? DZ : DY1, nullptr, M, N, 32, N};
       if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, "d y1", w.w_ih[d], ntiles, 1, al, ep, nullptr, N))
@@ -1761,14 +1800,14 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
       EpiAddMaskStoreT<false, false> ep{DATT, nullptr, nullptr, M, N, 32, N};
       float* slab = br.ws + br.pl.slab;
       int rgrid = 0;
-      bool t = false;
+      bool took = false;
       if (c->opt_dgrad_r) {
         const DgradRArgs a{DZ, wpk + BWD_PACK_OUTW, att, DATT, M, N, /*relu_gate*/ false, nullptr, slab, slab + (size_t)BWD_SLAB_WGS * N * N,
                            BWD_SLAB_WGS};
-        if (int rc = try_dgrad_r(c, lane, CAT_OUTPROJ, "d att + d out weight", a, &rgrid, &t)) return rc;
+        if (int rc = try_dgrad_r(c, lane, CAT_OUTPROJ, "d att + d out weight", a, &rgrid, &took)) return rc;
       }
       WgradRider<N, ALoadDense, true> rd{ALoadDense{att, M, N, 32}, slab, slab + (size_t)BWD_SLAB_WGS * N * N, M};
-      if (!t)
+      if (!took)
         if (int rc = launch_gemm<N, 1, 1, 4, true, false>(c, lane, CAT_OUTPROJ, "d att + d out weight", w.out_w, ntiles, 1, al, ep,
                                                           nullptr, N, &rgrid, rd))
           return rc;
@@ -1852,14 +1891,14 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
     }
   }
   {
-    bool t = false;
+    bool took = false;
     if constexpr (N == 128) {      // d x = dz + d qkv W_in (K = 384) by dgrad_t.hip
       if (c->opt_dgrad_t) {
         const DgradTArgs a{DQKV, 3 * N, wpk + BWD_PACK_INW, DZ, d_in, M, 384};
-        if (int rc = try_dgrad_t(c, lane, CAT_QKV, "d x", a, &t)) return rc;
+        if (int rc = try_dgrad_t(c, lane, CAT_QKV, "d x", a, &took)) return rc;
       }
     }
-    if (!t) {
+    if (!took) {
       ALoadDense al{DQKV, M, 3 * N, BMn};
       EpiAddMaskStoreT<true, false> ep{d_in, DZ, nullptr, M, N, BMn, N};
       if (int rc = launch_gemm<3 * N, 1, WRn, WCn, true>(c, lane, CAT_QKV, "d x", w.in_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;

@@ -656,6 +656,35 @@ def test_unidirectional_inter_path_backward_matches_autograd(dev, arch, features
         assert O.agreement_db(got, gref.numpy()) > 70, (leaf, O.agreement_db(got, gref.numpy()))
 
 
+@pytest.mark.parametrize("arch,features,bidir", [("dprnn", 64, True), ("dprnn", 64, False), ("dptn", 128, False)],
+                         ids=["dprnn64", "dprnn64_unidir", "dptn128_unidir"])
+def test_training_forward_without_the_layernorm_tape_matches_inference(dev, arch, features, bidir):
+    """Option ln_tape = 0: the training forward of a block half writes no zn / rstd, so its K6 takes the launches without the
+    tape epilogue -- for a bidirectional DPRNN half with 64 features that is fcln.hip, as in inference; with one direction the
+    GEMM engine over 128 hidden columns (DPTN: ReLU while loading the raw h of the tape).  Same bound as the tape forwards
+    above: the training forward agrees with the inference one to fp32 rounding.  DPRNN blocks have no LayerNorm recompute:
+    their backward says that it needs the tape."""
+    from speech_separation_amd.engine import DptnEngine, params_to_device
+    from speech_separation_amd.spec import DPRNN_AUDIO
+    base = DPTN_AV if arch == "dptn" else DPRNN_AUDIO
+    cfg = DPTNConfig(**{**base.to_dict(), "num_blocks": 1, "dropout": 0.0, "num_features": features, "hidden_video": features,
+                        "audio_only": True, "bidir": bidir, "chunk_size": 50, "step_size": 25})
+    eng = DptnEngine(cfg, dev)
+    eng.bind(params_to_device(synthetic_state_dict(cfg, seed=4), dev))
+    eng.bind_grads()
+    eng.set_option("ln_tape", 0)
+    B, S, K, N, path = 2, 9, cfg.chunk_size, cfg.num_features, 1
+    xt = torch.from_numpy(np.random.default_rng(7).standard_normal((B, S, K, N)).astype(np.float32)).to(dev)
+    y, tape = eng.train_path_forward(0, path, xt)
+    y_inf = eng.stage_path(0, path, xt)
+    torch.cuda.synchronize()
+    assert torch.isfinite(y).all()
+    assert O.agreement_db(y.cpu().numpy(), y_inf.cpu().numpy()) > 120
+    if arch == "dprnn":
+        with pytest.raises(RuntimeError, match="needs option ln_tape = 1"):
+            eng.train_path_backward(0, path, xt, torch.ones_like(xt), tape)
+
+
 def test_unidirectional_whole_model_trains(dev):
     """A bidir = False DPTN-AV model through the drop-in module: loss.backward() fills every parameter's gradient (finite,
     non-zero) and three fused optimizer steps lower the loss."""
