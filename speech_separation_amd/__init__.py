@@ -6,7 +6,8 @@ __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "D
            "DeepConvTasNetEngine", "TrainableDeepConvTasNet", "DeepConvTasNetTrainEngine", "TrainableDeepAVConvTasNet", "DeepAVConvTasNetTrainEngine", "FusedAdamW", "clip_grad_norm_", "SiSNRWavLoss", "MAEWavLoss",
            "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "ShuffleNetLipreadingEngine", "ShuffleNetLipreading", "init_lipreader", "VideoSSModel", "make_embeddings",
            "STFT", "LogMelSpectrogram", "add_spectrogram_keys", "MSESpecLoss", "L1SpecLoss",
-           "VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude"]
+           "VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude",
+           "voicefilter_analysis", "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
@@ -31,7 +32,8 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
     if name in ("STFT", "LogMelSpectrogram", "add_spectrogram_keys"):
         from . import spectral
         return getattr(spectral, name)
-    if name in ("VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude"):
+    if name in ("VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude", "voicefilter_analysis",
+                "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys"):
         from . import voicefilter
         return getattr(voicefilter, name)
     raise AttributeError(name)

@@ -84,6 +84,7 @@ LIPFE_ABI_VERSION = 1
 SPECFE_ABI_VERSION = 1
 VFILT_ABI_VERSION = 1
 LIPSN_ABI_VERSION = 1
+VFWAVE_ABI_VERSION = 1
 
 
 def _infer_symbols(prefix, create_extra=(), workspace_extra=(), forward_in=(), more=None):
@@ -205,6 +206,14 @@ SPECFE_SYMBOLS = {
     "specfe_logmel": (_i, [_vp, _fp, _i, _i64, _fp, _vp]),
 }
 
+#: every symbol include/vfwave.h declares (VoiceFilter's waveform ends: analysis to magnitude + phasor, synthesis back; on a specfe handle)
+VFWAVE_SYMBOLS = {
+    "vfwave_abi_version": (_i, []),
+    "vfwave_strerror": (C.c_char_p, [_i]),
+    "vfwave_analysis": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp]),
+    "vfwave_synthesis": (_i, [_vp, _fp, _fp, _i, _i, _i64, _i64, _fp, _vp]),
+}
+
 #: every symbol include/vfilt.h declares (VoiceFilter separator: magnitude spectrogram + lip embeddings -> two masked spectrograms)
 VFILT_SYMBOLS = {
     "vfilt_abi_version": (_i, []),
@@ -261,7 +270,7 @@ def load() -> C.CDLL:
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
                               + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())
                               + list(SPECFE_SYMBOLS.items()) + list(VFILT_SYMBOLS.items())
-                              + list(LIPSN_SYMBOLS.items())):
+                              + list(LIPSN_SYMBOLS.items()) + list(VFWAVE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -279,7 +288,8 @@ def load() -> C.CDLL:
                             (lib.lipfe_abi_version, LIPFE_ABI_VERSION, "lipfe"),
                             (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe"),
                             (lib.vfilt_abi_version, VFILT_ABI_VERSION, "vfilt"),
-                            (lib.lipsn_abi_version, LIPSN_ABI_VERSION, "lipsn")):
+                            (lib.lipsn_abi_version, LIPSN_ABI_VERSION, "lipsn"),
+                            (lib.vfwave_abi_version, VFWAVE_ABI_VERSION, "vfwave")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -1,20 +1,26 @@
-// specfe.hip -- the spectral front end on the device (include/specfe.h): STFT, inverse STFT, their adjoints, log-mel.
+// specfe.hip -- the spectral front end on the device (include/specfe.h): STFT, inverse STFT, their adjoints, log-mel; and
+// VoiceFilter's two waveform ends on the same transform (include/vfwave.h).
 //
 //   STFT.stft            src/encoders/stft.py:25-38                  (torch.stft, then stack / transpose / contiguous)
 //   torch.istft          src/model/rtfsnet.py:843-849                (AudioDecoder)
 //   get_spectrogram      src/datasets/base_dataset.py:115-123,165    (torchaudio MelSpectrogram, clamp, log; on loader threads)
 //
-// Two kernels, one launch per call, no scratch:
+// Three kernels, one launch per call, no scratch:
 //   dft     analysis: frames x twiddles as a GEMM on v_mfma_f32_32x32x2_f32 (exact fp32).  Workgroup = 32 frames of one
 //           item.  The A tile is built in LDS 128 samples at a time straight from the signal: framing, reflect indexing and
 //           the window happen in that load, no padded signal and no frame matrix ever exist in HBM.  Wave v takes the 32-bin
 //           column tiles v, v + 4, v + 8 of the cos and the -sin table: re and im of a (frame, bin) land in the same lane
-//           and register.  Three modes share the loop:
+//           and register.  Four modes share the loop:
 //             STFT        A = w[t] xp[m H + t]; the epilogue writes [B][2][M][F] directly
 //             LOGMEL      same A; the epilogue squares into an LDS power tile, multiplies with the sparse mel filterbank,
 //                         clamps, takes the log and writes [B][n_mels][M]
 //             ISTFT_BWD   A = w[t] gy[m H + t - N / 2] / env; the epilogue scales by c_k / N and zeroes Im of bins 0, N / 2
-//           (the adjoint of the synthesis IS an analysis of the enveloped gradient)
+//                         (the adjoint of the synthesis IS an analysis of the enveloped gradient)
+//             VF          same A, but the MFMA operands change places: the table fragment is the A operand and the frames the
+//                         B operand, so the accumulators hold the TRANSPOSED tile, a lane owns one frame and its registers
+//                         run over the bins.  The epilogue turns (Re, Im) into VoiceFilter's normalised dB magnitude and the
+//                         unit phasor and stores both as [B][F][W] straight from the registers: the 32 lanes of a half wave
+//                         write 32 consecutive frames of one bin, no pass through LDS
 //   gather  synthesis: one thread per output sample walks the frames that overlap it in ascending order and sums the
 //           N-term inverse DFT of each from one period of cos / sin in LDS.  Two modes:
 //             ISTFT       y[j] = z[N / 2 + j] / (N env[N / 2 + j])
@@ -22,6 +28,9 @@
 //                         order (the adjoint of the analysis IS a synthesis without the envelope)
 //           Plain VALU: at 2 frames x 256 terms per sample the synthesis of a [16][32000] batch is 0.26 GFLOP and the kernel
 //           needs no intermediate frame matrix.
+//   synth   vfwave_synthesis: the ISTFT gather on X = 10^(5 clamp(p, 0, 1) - 4) (phasor[0] + i phasor[1]).  A workgroup of
+//           256 output samples stages the complex rows of the frames its samples overlap in LDS, VF_FRAMES at a time,
+//           denormalising every (frame, bin) ONCE while it does; the threads then gather from LDS, frames ascending.
 // env is summed in double from the fp32 window.  No atomics anywhere.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -30,6 +39,7 @@
 #include <vector>
 
 #include "../../include/specfe.h"
+#include "../../include/vfwave.h"
 
 namespace {
 
@@ -45,7 +55,10 @@ constexpr int SF_MAX_MELS = 256;
 constexpr float SF_CLAMP = 1e-5f;
 constexpr float SF_LOG_CLAMP = -11.512925464970229f;       // log(1e-5) rounded once: what a clamped band gets, whatever logf's last bits are
 
-enum { MODE_STFT = 0, MODE_LOGMEL = 1, MODE_ISTFT_BWD = 2 };
+constexpr int VF_FRAMES = 16;            // frames of the denormalised spectrum in LDS at a time (vfwave_synthesis)
+constexpr float VF_FLOOR = 1e-5f;        // get_magnitude's clamp of |S|
+
+enum { MODE_STFT = 0, MODE_LOGMEL = 1, MODE_ISTFT_BWD = 2, MODE_VF = 3 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -65,6 +78,7 @@ struct DftArgs {
   int N, H, F, Fp, n_mels;
   const float *win, *cosT, *sinT, *fb;
   const int* rng;
+  float* out2;                           // MODE_VF: the phasor [B][2][F][M] (out is spec [B][F][M])
 };
 
 // env[n] = sum of w[n - m H]^2 over the frames 0 <= m < M that contain n, ascending m, in double
@@ -147,15 +161,40 @@ __global__ __launch_bounds__(256) void specfe_dft_kernel(DftArgs a) {
 #pragma unroll
         for (int c = 0; c < SF_TILES; ++c) {
           if (wave + 4 * c < nb) {
-            re[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, cv[u][c], re[c], 0, 0, 0);
-            im[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, sv[u][c], im[c], 0, 0, 0);
+            if (MODE == MODE_VF) {                             // D^T = table^T frames^T: the same products, bins down the registers
+              re[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[u][c], x0, re[c], 0, 0, 0);
+              im[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[u][c], x0, im[c], 0, 0, 0);
+            } else {
+              re[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, cv[u][c], re[c], 0, 0, 0);
+              im[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, sv[u][c], im[c], 0, 0, 0);
+            }
           }
         }
       }
     }
   }
   // D register i of lane l: row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31
-  if (MODE != MODE_LOGMEL) {
+  if (MODE == MODE_VF) {                                       // rows are bins, columns frames: lane l owns frame m0 + (l & 31)
+    const int64_t m = m0 + frag_row;
+    float* spec = a.out + b * F * M;
+    float* ph = a.out2 + b * 2 * F * M;
+#pragma unroll
+    for (int c = 0; c < SF_TILES; ++c) {
+      const int ct = wave + 4 * c;
+      if (ct >= nb) continue;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int k = ct * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+        if (k >= F || m >= M) continue;
+        const float p = re[c][i], q = im[c][i];
+        const float mag = sqrtf(fmaf(p, p, q * q));
+        const float db = (20.f * log10f(fmaxf(mag, VF_FLOOR)) - 20.f) / 100.f;
+        spec[k * M + m] = mag >= 10.f ? 1.f : fminf(fmaxf(db, -1.f), 0.f) + 1.f;   // |S| >= 10 is 1 whatever log10f's last bit is
+        ph[k * M + m] = mag > 0.f ? p / mag : 1.f;                                  // angle(0) = 0
+        ph[(F + k) * M + m] = mag > 0.f ? q / mag : 0.f;
+      }
+    }
+  } else if (MODE != MODE_LOGMEL) {
     float* out = a.out + b * 2 * M * F;
 #pragma unroll
     for (int c = 0; c < SF_TILES; ++c) {
@@ -260,6 +299,68 @@ __global__ __launch_bounds__(256) void specfe_gather_kernel(const float* __restr
   out[b * L + j] = v;
 }
 
+// pred [S][B][F][M], phasor [B][2][F][M] -> y [S][B][L]: specfe_gather_kernel<true> on the denormalised, rotated spectrum.
+// blockIdx.x = (source s, item b, chunk of 256 samples).  The frames m_lo .. m_hi that the chunk's samples overlap are staged
+// VF_FRAMES at a time as rows xr / xi [frame][F]; a thread adds its own frames of every group in ascending order, so the
+// order of its sum does not depend on the grouping.
+__global__ __launch_bounds__(256) void vfwave_synth_kernel(const float* __restrict__ pred, const float* __restrict__ phasor, int B,
+                                                           int64_t M, int64_t L, unsigned nchunk, int N, int H, int F,
+                                                           const float* __restrict__ win, const float* __restrict__ cos1,
+                                                           const float* __restrict__ sin1, float* __restrict__ out) {
+  __shared__ float w[SF_MAX_N], cs[SF_MAX_N], sn[SF_MAX_N];
+  __shared__ float xr[VF_FRAMES * (SF_MAX_N / 2 + 1)], xi[VF_FRAMES * (SF_MAX_N / 2 + 1)];
+  for (int t = threadIdx.x; t < N; t += 256) {
+    w[t] = win[t];
+    cs[t] = cos1[t];
+    sn[t] = sin1[t];
+  }
+  __syncthreads();
+  const int64_t sb = blockIdx.x / nchunk, b = sb % B;
+  const int64_t j0 = (int64_t)(blockIdx.x % nchunk) * 256, j = j0 + threadIdx.x;
+  const bool active = j < L;
+  const int64_t n_first = j0 + N / 2, n_last = (j0 + 255 < L ? j0 + 255 : L - 1) + N / 2, n = j + N / 2;
+  const int64_t m_lo = n_first >= N ? (n_first - N) / H + 1 : 0;
+  const int64_t m_hi = n_last / H < M - 1 ? n_last / H : M - 1;
+  const int64_t lo = n >= N ? (n - N) / H + 1 : 0, hi = n / H < M - 1 ? n / H : M - 1;
+  const float* ps = pred + sb * F * M;
+  const float* p0 = phasor + b * 2 * F * M;
+  const float* p1 = p0 + (int64_t)F * M;
+  float s = 0.f;
+  for (int64_t ma = m_lo; ma <= m_hi; ma += VF_FRAMES) {
+    const int nf = m_hi - ma + 1 < VF_FRAMES ? (int)(m_hi - ma + 1) : VF_FRAMES;
+    if (ma != m_lo) __syncthreads();                           // every thread is done with the last group
+    for (int id = threadIdx.x; id < nf * F; id += 256) {       // frames fastest: odd row stride F, no bank conflict
+      const int k = id / nf, g = id - k * nf;
+      const int64_t at = k * M + ma + g;
+      const float mag = exp10f(fmaf(5.f, fminf(fmaxf(ps[at], 0.f), 1.f), -4.f));
+      xr[g * F + k] = mag * p0[at];
+      xi[g * F + k] = mag * p1[at];
+    }
+    __syncthreads();
+    if (active) {
+      const int64_t a = lo > ma ? lo : ma, e = hi < ma + nf - 1 ? hi : ma + nf - 1;
+      for (int64_t m = a; m <= e; ++m) {
+        const int t = (int)(n - m * H);
+        const float* re = xr + (int)(m - ma) * F;              // gather_at<2>'s term of one frame, its operands in LDS
+        const float* im = xi + (int)(m - ma) * F;
+        const float edge = (t & 1) ? re[0] - re[N / 2] : re[0] + re[N / 2];
+        float acc = 0.f;
+        int idx = 0;                                           // k t mod N
+        for (int k = 1; k < N / 2; ++k) {                      // im[0] and im[N / 2] are never read
+          idx += t;
+          if (idx >= N) idx -= N;
+          acc = fmaf(re[k], cs[idx], acc);
+          acc = fmaf(-im[k], sn[idx], acc);
+        }
+        s = fmaf(w[t], fmaf(2.f, acc, edge), s);
+      }
+    }
+  }
+  if (!active) return;
+  const double e = env_at(w, n, N, H, M);
+  out[sb * L + j] = e > 0 ? (float)((double)s / ((double)N * e)) : 0.f;
+}
+
 // cos and sin of 2 pi idx / N, exact on the axes
 void twiddle(int idx, int N, double* c, double* s) {
   const double pi = 3.14159265358979323846;
@@ -349,11 +450,11 @@ int create(int n_fft, int hop, int sample_rate, int n_mels, bool mel, void** han
 }
 
 template <int MODE>
-int launch_dft(const Handle* h, const float* src, int B, int64_t T, int64_t M, float* out, void* stream) {
+int launch_dft(const Handle* h, const float* src, int B, int64_t T, int64_t M, float* out, void* stream, float* out2 = nullptr) {
   const int64_t ntile = (M + SF_ROWS - 1) / SF_ROWS;
   if (ntile * B >= ((int64_t)1 << 31)) return SPECFE_ERR_INVALID;
   DftArgs a;
-  a.src = src; a.out = out; a.T = T; a.M = M; a.ntile = (unsigned)ntile;
+  a.src = src; a.out = out; a.out2 = out2; a.T = T; a.M = M; a.ntile = (unsigned)ntile;
   a.N = h->N; a.H = h->H; a.F = h->F; a.Fp = h->Fp; a.n_mels = h->n_mels;
   a.win = h->win; a.cosT = h->cosT; a.sinT = h->sinT; a.fb = h->fb; a.rng = h->rng;
   hipLaunchKernelGGL(specfe_dft_kernel<MODE>, dim3((unsigned)(ntile * B)), dim3(256), 0, (hipStream_t)stream, a);
@@ -436,6 +537,37 @@ int specfe_istft_backward(void* handle, const float* gy, int B, int64_t M, int64
   const int64_t L = inverse_length(h, B, M, length);
   if (!gy || !gX || L < 1) return SPECFE_ERR_INVALID;
   return launch_dft<MODE_ISTFT_BWD>(h, gy, B, L, M, gX, stream);
+}
+
+int vfwave_abi_version(void) { return VFWAVE_ABI_VERSION; }
+
+const char* vfwave_strerror(int code) {
+  switch (code) {
+    case VFWAVE_OK: return "ok";
+    case VFWAVE_ERR_INVALID:
+      return "vfwave: bad argument (null pointer or handle, a signal no longer than n_fft / 2, n_src not in [1, 4], or a size out "
+             "of range)";
+    case VFWAVE_ERR_HIP: return "vfwave: the launch failed (no HIP device? libdptnav has no CPU path)";
+    default: return "vfwave: unknown error code";
+  }
+}
+
+int vfwave_analysis(void* handle, const float* x, int B, int64_t T, float* spec, float* phasor, void* stream) {
+  const Handle* h = (const Handle*)handle;
+  if (!h || !x || !spec || !phasor || !size_ok(B, T) || T <= h->N / 2) return VFWAVE_ERR_INVALID;
+  return launch_dft<MODE_VF>(h, x, B, T, 1 + T / h->H, spec, stream, phasor);
+}
+
+int vfwave_synthesis(void* handle, const float* pred, const float* phasor, int n_src, int B, int64_t W, int64_t length, float* y,
+                     void* stream) {
+  const Handle* h = (const Handle*)handle;
+  const int64_t L = inverse_length(h, B, W, length);
+  if (!pred || !phasor || !y || L < 1 || n_src < 1 || n_src > VFWAVE_MAX_SRC) return VFWAVE_ERR_INVALID;
+  const int64_t nchunk = (L + 255) / 256;
+  if (nchunk * B * n_src >= ((int64_t)1 << 31)) return VFWAVE_ERR_INVALID;
+  hipLaunchKernelGGL(vfwave_synth_kernel, dim3((unsigned)(nchunk * B * n_src)), dim3(256), 0, (hipStream_t)stream, pred, phasor, B, W, L,
+                     (unsigned)nchunk, h->N, h->H, h->F, h->win, h->cos1, h->sin1, y);
+  return hipGetLastError() == hipSuccess ? VFWAVE_OK : VFWAVE_ERR_HIP;
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ import torch
 TENSOR_KEYS = ["mix_spectrogram", "complex_spectrogram", "s1_spectrogram", "s2_spectrogram", "s1_video", "s2_video",
                "s1_embedding", "s2_embedding", "mix", "s1", "s2"]
 LIST_KEYS = ["audio_path"]
+VIDEO_KEYS = ["s1_video", "s2_video"]
 
 
 def load_object(path: str) -> torch.Tensor:
@@ -38,6 +39,13 @@ def load_object(path: str) -> torch.Tensor:
     else:
         raise ValueError(f"unsupported object file: {path}")
     return obj.unsqueeze(0)
+
+
+def load_video(path: str) -> torch.Tensor:
+    """(1, Tv, H, W) float32: the ``data`` array of a mouth-crop .npz, as BaseDataset.load_video reads it
+    (base_dataset.py:151-153)."""
+    with np.load(path) as data:
+        return torch.from_numpy(np.asarray(data["data"], dtype=np.float32)).unsqueeze(0)
 
 
 def collate(items: Sequence[Mapping[str, object]]) -> Dict[str, object]:
@@ -107,7 +115,8 @@ def load_audio(path: str, target_sr: Optional[int] = None) -> torch.Tensor:
 
 def load_item(entry: Mapping[str, Optional[str]], target_sr: Optional[int] = None) -> Dict[str, object]:
     """One dataset element from its index entry, the parts of BaseDataset.__getitem__ (base_dataset.py:56-135) this path
-    consumes: mix / s1 / s2 waveforms, the two lip embeddings, audio_path.  Spectrogram keys are not produced (the
+    consumes: mix / s1 / s2 waveforms, the two lip embeddings, audio_path, and -- only for an entry that names them with
+    s1_video_path / s2_video_path -- the two mouth videos (load_video).  Spectrogram keys are not produced (the
     separator ignores them, dptn_wav.py:171): spectral.add_spectrogram_keys computes them for a whole batch on the device."""
     g = lambda k: entry.get(k)
     item: Dict[str, object] = {"mix": load_audio(entry["mix_wav_path"], target_sr), "s1": None, "s2": None, "s1_video": None,
@@ -117,6 +126,8 @@ def load_item(entry: Mapping[str, Optional[str]], target_sr: Optional[int] = Non
         item["s1"], item["s2"] = load_audio(entry["s1_wav_path"], target_sr), load_audio(entry["s2_wav_path"], target_sr)
     if g("s1_embedding_path") is not None:
         item["s1_embedding"], item["s2_embedding"] = load_object(entry["s1_embedding_path"]), load_object(entry["s2_embedding_path"])
+    if g("s1_video_path") is not None:
+        item["s1_video"], item["s2_video"] = load_video(entry["s1_video_path"]), load_video(entry["s2_video_path"])
     return item
 
 
@@ -165,7 +176,7 @@ class PinnedBatcher:
                 batch[key] = None
             elif key in LIST_KEYS:
                 batch[key] = [it[key] for it in items]
-            elif key in self.device_tensors:
+            elif key in self.device_tensors or key in VIDEO_KEYS:    # videos an entry opted into go where the model runs
                 staged[key] = self._stage(self._sets[i], key, [it[key] for it in items])
             else:
                 batch[key] = torch.cat([it[key] for it in items], dim=0)

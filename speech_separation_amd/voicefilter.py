@@ -1,6 +1,7 @@
 """VoiceFilter on libdptnav (include/vfilt.h): the mixture's magnitude spectrogram and one lip-embedding sequence per speaker
 -> one masked spectrogram per speaker.  Replaces the reference's VoiceFilter (src/model/voicefilter.py) in eval mode and
-its dataset's get_magnitude (src/datasets/base_dataset.py:167-180).  Inference only.
+its dataset's get_magnitude (src/datasets/base_dataset.py:167-180).  Inference only.  The two waveform ends
+(include/vfwave.h): voicefilter_analysis, voicefilter_waveforms, VoiceFilter.separate, VoiceFilterSeparator.
 """
 from __future__ import annotations
 
@@ -281,6 +282,187 @@ class VoiceFilter(nn.Module):
         B = int(s1_video.shape[0])
         emb = self._embed(torch.cat([s1_video, s2_video], dim=0).float())
         return self.forward_embeddings(mix_magnitude, emb[:B], emb[B:])
+
+    def _separate(self, mix, s1_embedding, s2_embedding, hop_length):
+        self._need_eval()
+        n_fft = 2 * (self.input_size - 1)
+        hop = n_fft // 4 if hop_length is None else int(hop_length)
+        if not isinstance(mix, torch.Tensor) or mix.dim() not in (2, 3) or (mix.dim() == 3 and mix.shape[1] != 1):
+            raise ValueError("mix: expected a (B, T) or (B, 1, T) tensor")
+        wav = mix.detach().reshape(mix.shape[0], mix.shape[-1])
+        spec, phasor = voicefilter_analysis(wav, n_fft, hop)
+        B, F, W = spec.shape
+        stack = torch.empty(2, B, F, W, dtype=torch.float32, device=spec.device)       # both masks' results, one synthesis launch
+        out = self.forward_embeddings(spec, s1_embedding, s2_embedding, out=(stack[0], stack[1]))
+        y = voicefilter_waveforms(stack, phasor, wav.shape[1], n_fft, hop)
+        out.update(s1_pred=y[0].view(mix.shape), s2_pred=y[1].view(mix.shape), mix_magnitude=spec)
+        return out
+
+    def separate_embeddings(self, mix, s1_embedding, s2_embedding, hop_length=None):
+        """forward_embeddings between the two waveform ends (include/vfwave.h): mix (B, T) or (B, 1, T) waveforms,
+        s1/s2_embedding (B, Tv, embed_size) -> {"s1_spec_pred", "s2_spec_pred" (B, F, W), "s1_pred", "s2_pred" (the shape of
+        mix), "mix_magnitude" (B, F, W)}.  n_fft is 2 (input_size - 1), hop_length defaults to n_fft / 4 (the reference's
+        400 / 100).  Three parts -- voicefilter_analysis, the separator, voicefilter_waveforms -- enqueued back to back on the
+        current stream: no host synchronisation and no torch operator between them.  The waveforms carry the convention's
+        two clamps (voicefilter_waveforms)."""
+        return self._separate(mix, s1_embedding, s2_embedding, hop_length)
+
+    def separate(self, mix, s1_video, s2_video, hop_length=None, **batch):
+        """separate_embeddings with the lip reader in front, as forward: s1/s2_video (B, Tv, H, W') raw mouth frames."""
+        self._need_eval()
+        if self.lipreader is None:
+            raise RuntimeError("VoiceFilter was built without a lip reader: call separate_embeddings(mix, s1_embedding, s2_embedding)")
+        if s1_video.dim() != 4 or s1_video.shape != s2_video.shape:
+            raise ValueError(f"s1_video / s2_video: expected two (B,Tv,H,W), got {tuple(s1_video.shape)} and {tuple(s2_video.shape)}")
+        B = int(s1_video.shape[0])
+        emb = self._embed(torch.cat([s1_video, s2_video], dim=0).float())
+        return self._separate(mix, emb[:B], emb[B:], hop_length)
+
+
+class VoiceFilterSeparator:
+    """``model(**batch)`` of evaluate / run_inference for a VoiceFilter: reads ``mix`` and either ``s1_embedding`` /
+    ``s2_embedding`` (precomputed; (B, Tv, E), or (B, E, Tv) as make_embeddings stores them and the loader delivers them) or
+    ``s1_video`` / ``s2_video``, and returns VoiceFilter.separate's dict, so that the waveform metrics and the prediction
+    writer find ``s1_pred`` / ``s2_pred``.  `n_fft` must be the model's 2 (input_size - 1)."""
+
+    def __init__(self, model: "VoiceFilter", n_fft: Optional[int] = None, hop_length: Optional[int] = None):
+        want = 2 * (model.input_size - 1)
+        if n_fft is not None and int(n_fft) != want:
+            raise ValueError(f"n_fft={n_fft} gives {int(n_fft) // 2 + 1} bins, the model takes {model.input_size} (n_fft={want})")
+        self.model, self.n_fft = model, want
+        self.hop_length = want // 4 if hop_length is None else int(hop_length)
+        _check_transform(self.n_fft, self.hop_length)
+
+    def __call__(self, mix, s1_embedding=None, s2_embedding=None, s1_video=None, s2_video=None, **batch):
+        if s1_embedding is not None and s2_embedding is not None:
+            E = self.model.embed_size
+            if s1_embedding.dim() == 3 and s1_embedding.shape[2] != E and s1_embedding.shape[1] == E:
+                s1_embedding, s2_embedding = s1_embedding.transpose(1, 2), s2_embedding.transpose(1, 2)
+            return self.model.separate_embeddings(mix, s1_embedding, s2_embedding, self.hop_length)
+        if s1_video is not None and s2_video is not None:
+            return self.model.separate(mix, s1_video, s2_video, self.hop_length)
+        raise ValueError("VoiceFilterSeparator: the batch has neither s1_embedding / s2_embedding nor s1_video / s2_video")
+
+
+def _check_transform(n_fft: int, hop: int):
+    from .spectral import _check_sizes as check
+    check(int(n_fft), int(hop))
+
+
+def _vfwave(name: str, dev: torch.device, what: str, *args):
+    from . import _lib
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(*args, torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise (ValueError if rc == 1 else RuntimeError)(f"{name}({what}): {lib.vfwave_strerror(rc).decode()}")
+
+
+def _fp32(t, who: str, ranks) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: expected float32, got {t.dtype}")
+    if t.dim() not in ranks:
+        raise ValueError(f"{who}: expected {' or '.join(str(r) for r in ranks)} dimensions, got {tuple(t.shape)}")
+
+
+def _on_gpu(t: torch.Tensor, who: str) -> torch.device:
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{who} computes only on an AMD GPU through libdptnav (got a {t.device} tensor); there is no "
+                           f"CPU/PyTorch fallback")
+    return t.device
+
+
+def voicefilter_analysis(audio: torch.Tensor, n_fft: int = 400, hop_length: int = 100):
+    """The reference's get_magnitude (src/datasets/base_dataset.py:167-180) in ONE launch (vfwave_analysis): audio (B, T) or
+    (T,), T > n_fft / 2 -> (spec, phasor), (B, F, W) and (B, 2, F, W) with F = n_fft // 2 + 1, W = 1 + T // hop_length (no B
+    for a 1-D input).  spec = clamp((20 log10(max(|S|, 1e-5)) - 20) / 100, -1, 0) + 1 in [0, 1], phasor = (Re S, Im S) / |S|,
+    (1, 0) where S = 0; the reference's phase is atan2(phasor[:, 1], phasor[:, 0]).  spec keeps |S| only inside
+    [1e-4, 10]: smaller bins read 0, larger ones 1 (a full-scale tone at n_fft = 400 reaches about 100).  That is the
+    reference's convention, and voicefilter_waveforms inverts exactly this range."""
+    _fp32(audio, "voicefilter_analysis: audio", (1, 2))
+    _check_transform(n_fft, hop_length)
+    one = audio.dim() == 1
+    x = audio.detach()[None] if one else audio.detach()
+    B, T = x.shape
+    if T <= n_fft // 2:
+        raise ValueError(f"voicefilter_analysis: needs more than n_fft / 2 = {n_fft // 2} samples, got {T}")
+    dev = _on_gpu(x, "voicefilter_analysis")
+    from .spectral import _handle
+    x = x.contiguous()
+    F, W = n_fft // 2 + 1, 1 + T // hop_length
+    with torch.cuda.device(dev):
+        spec = torch.empty(B, F, W, dtype=torch.float32, device=dev)
+        phasor = torch.empty(B, 2, F, W, dtype=torch.float32, device=dev)
+    if B:
+        _vfwave("vfwave_analysis", dev, f"B={B}, T={T}", _handle(dev, n_fft, hop_length), x.data_ptr(), B, T, spec.data_ptr(),
+                phasor.data_ptr())
+    return (spec[0], phasor[0]) if one else (spec, phasor)
+
+
+def voicefilter_waveforms(spec_preds, phasor: torch.Tensor, length: Optional[int] = None, n_fft: int = 400, hop_length: int = 100,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Predicted maps back to audio on the mixture's phase (vfwave_synthesis): spec_preds (n_src, B, F, W) -- or a sequence
+    of n_src (B, F, W) tensors --, phasor (B, 2, F, W) from voicefilter_analysis -> (n_src, B, length), `length` defaulting
+    to the natural (W - 1) hop_length.  y = istft(10^(5 clamp(p, 0, 1) - 4) (phasor[0] + i phasor[1])), this package's
+    STFT.istft: the inverse of voicefilter_analysis's scaling on [1e-4, 10], outside of which the analysis has already
+    clamped.  1 <= n_src <= 4.  One launch for a stack (a sequence that is a stack's slices counts as one); otherwise one
+    launch per source, each writing its slice of the result: no map is ever copied.  `out`: a contiguous
+    (n_src, B, length) result to fill."""
+    maps = [spec_preds] if isinstance(spec_preds, torch.Tensor) else list(spec_preds)
+    for t in maps:
+        _fp32(t, "voicefilter_waveforms: spec_preds", (4,) if isinstance(spec_preds, torch.Tensor) else (3,))
+    _fp32(phasor, "voicefilter_waveforms: phasor", (4,))
+    _check_transform(n_fft, hop_length)
+    n_src = maps[0].shape[0] if isinstance(spec_preds, torch.Tensor) else len(maps)
+    if not 1 <= n_src <= 4:
+        raise ValueError(f"voicefilter_waveforms: 1 to 4 sources per item, got {n_src}")
+    B, two, F, W = phasor.shape
+    if two != 2 or F != n_fft // 2 + 1 or W < 1:
+        raise ValueError(f"voicefilter_waveforms: phasor must be (B, 2, {n_fft // 2 + 1}, W), got {tuple(phasor.shape)}")
+    for t in maps:
+        if tuple(t.shape[-3:]) != (B, F, W):
+            raise ValueError(f"voicefilter_waveforms: every map must be ({B}, {F}, {W}) as the phasor, got {tuple(t.shape)}")
+    L = (W - 1) * hop_length if length is None else int(length)
+    if L < 1:
+        raise ValueError(f"voicefilter_waveforms: output length {L}; it must be at least 1")
+    dev = _on_gpu(phasor, "voicefilter_waveforms")
+    if any(t.device != phasor.device for t in maps) or any(not t.is_contiguous() for t in maps + [phasor]):
+        raise ValueError("voicefilter_waveforms: the maps and the phasor must be contiguous and on one device")
+    if out is None:
+        with torch.cuda.device(dev):
+            out = torch.empty(n_src, B, L, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (n_src, B, L) or out.dtype != torch.float32 or out.device != phasor.device or not out.is_contiguous():
+        raise ValueError(f"voicefilter_waveforms: out must be a contiguous float32 ({n_src}, {B}, {L}) tensor on {phasor.device}")
+    from .spectral import _handle
+    step = 4 * B * F * W
+    if all(t.data_ptr() == maps[0].data_ptr() + i * step for i, t in enumerate(maps)):
+        calls = [(maps[0].data_ptr(), n_src, out.data_ptr())]
+    else:
+        calls = [(t.data_ptr(), 1, out[i].data_ptr()) for i, t in enumerate(maps)]
+    if B:
+        for src, n, dst in calls:
+            _vfwave("vfwave_synthesis", dev, f"n_src={n}, B={B}, W={W}, length={L}", _handle(dev, n_fft, hop_length), src,
+                    phasor.data_ptr(), n, B, W, L, dst)
+    return out
+
+
+def add_magnitude_keys(batch: dict, n_fft: int = 400, hop_length: int = 100) -> dict:
+    """Fill VoiceFilter's spectrogram keys of a device batch in place, as the reference's dataset would per item on the host
+    with get_magnitude: ``mix_magnitude`` and ``mix_phase`` (= atan2 of the phasor) from ``mix``, ``s1_spec_true`` /
+    ``s2_spec_true`` from ``s1`` / ``s2``.  A key whose waveform is absent (None or missing) stays absent.  The
+    counterpart of spectral.add_spectrogram_keys.  Returns the batch."""
+    with torch.no_grad():
+        for src, key in (("mix", "mix_magnitude"), ("s1", "s1_spec_true"), ("s2", "s2_spec_true")):
+            wav = batch.get(src)
+            if wav is None:
+                continue
+            spec, phasor = voicefilter_analysis(wav.detach().reshape(wav.shape[0], wav.shape[-1]), n_fft, hop_length)
+            batch[key] = spec
+            if src == "mix":
+                batch["mix_phase"] = torch.atan2(phasor[:, 1], phasor[:, 0])
+    return batch
 
 
 def magnitude_from_stft(re: torch.Tensor, im: torch.Tensor):
