@@ -7,7 +7,8 @@ __all__ = ["DPTNConfig", "DPTN_AV", "DPTN_AUDIO", "DPTN_MASK", "DPRNN_AUDIO", "D
            "MSEWavLoss", "STOIMetric", "SISDRMetric", "LipreadingEngine", "Lipreading", "ShuffleNetLipreadingEngine", "ShuffleNetLipreading", "init_lipreader", "VideoSSModel", "make_embeddings",
            "STFT", "LogMelSpectrogram", "add_spectrogram_keys", "MSESpecLoss", "L1SpecLoss",
            "VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude",
-           "voicefilter_analysis", "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys"]
+           "voicefilter_analysis", "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys",
+           "TrainableVoiceFilter", "VoiceFilterTrainEngine"]
 
 
 def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py stays numpy-only)
@@ -33,7 +34,8 @@ def __getattr__(name):  # torch-dependent parts are imported lazily (spec.py sta
         from . import spectral
         return getattr(spectral, name)
     if name in ("VoiceFilter", "VoiceFilterEngine", "voicefilter_state_dict_spec", "voicefilter_magnitude", "voicefilter_analysis",
-                "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys"):
+                "voicefilter_waveforms", "VoiceFilterSeparator", "add_magnitude_keys", "TrainableVoiceFilter",
+                "VoiceFilterTrainEngine"):
         from . import voicefilter
         return getattr(voicefilter, name)
     raise AttributeError(name)

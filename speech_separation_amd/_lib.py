@@ -230,6 +230,31 @@ VFILT_SYMBOLS = {
     "vfilt_min_bytes_per_item": (C.c_double, [_vp, _i, _i]),
 }
 
+#: every symbol include/vfilt_train.h declares (VoiceFilter training step): _train_symbols' entries with shapes (B, W, Tv), the
+#: two embeddings behind the mixture and the dropout's (ppm, seed) in train_forward; costs are counted per item
+VFTRAIN_SYMBOLS = {
+    "vftrain_abi_version": (_i, []),
+    "vftrain_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "vftrain_destroy": (None, [_vp]),
+    "vftrain_last_error": (C.c_char_p, [_vp]),
+    "vftrain_num_weights": (_i, [_vp]),
+    "vftrain_weight_name": (C.c_char_p, [_vp, _i]),
+    "vftrain_weight_numel": (_i64, [_vp, _i]),
+    "vftrain_bind_weights": (_i, [_vp, C.POINTER(_fp), _i]),
+    "vftrain_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
+    "vftrain_flat_offset": (_i64, [_vp, _i]),
+    "vftrain_flat_numel": (_i64, [_vp]),
+    "vftrain_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vftrain_train_forward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, C.c_uint32, _fp, _fp, _vp, _sz, _vp]),
+    "vftrain_train_backward": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "vftrain_tape_offset": (_i64, [_vp, _i, _i, _i, _i, _i]),
+    "vftrain_clip_scratch_bytes": (_sz, [_vp]),
+    "vftrain_grad_clip": (_i, [_vp, _fp, _i64, C.c_float, _vp, _sz, _fp, _vp]),
+    "vftrain_adamw_step": (_i, [_vp, _fp, _fp, _fp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i, _vp]),
+    "vftrain_flops_per_item": (C.c_double, [_vp, _i, _i]),
+}
+VFTRAIN_ABI_VERSION = 1
+
 #: every symbol include/lipsn.h declares (ShuffleNet-v2 lip reader: mouth video -> 1024-wide embeddings)
 LIPSN_SYMBOLS = {
     "lipsn_abi_version": (_i, []),
@@ -270,7 +295,8 @@ def load() -> C.CDLL:
                               + list(DAVTRAIN_SYMBOLS.items()) + list(WAVLOSS_SYMBOLS.items())
                               + list(WAVMETRIC_SYMBOLS.items()) + list(LIPFE_SYMBOLS.items())
                               + list(SPECFE_SYMBOLS.items()) + list(VFILT_SYMBOLS.items())
-                              + list(LIPSN_SYMBOLS.items()) + list(VFWAVE_SYMBOLS.items())):
+                              + list(LIPSN_SYMBOLS.items()) + list(VFWAVE_SYMBOLS.items())
+                              + list(VFTRAIN_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -289,7 +315,8 @@ def load() -> C.CDLL:
                             (lib.specfe_abi_version, SPECFE_ABI_VERSION, "specfe"),
                             (lib.vfilt_abi_version, VFILT_ABI_VERSION, "vfilt"),
                             (lib.lipsn_abi_version, LIPSN_ABI_VERSION, "lipsn"),
-                            (lib.vfwave_abi_version, VFWAVE_ABI_VERSION, "vfwave")):
+                            (lib.vfwave_abi_version, VFWAVE_ABI_VERSION, "vfwave"),
+                            (lib.vftrain_abi_version, VFTRAIN_ABI_VERSION, "vftrain")):
         if fn() != want:
             raise RuntimeError(f"{label} ABI {fn()} != binding {want}: rebuild")
     _lib = lib

@@ -54,13 +54,16 @@ SOURCES = {"dptnav.hip": _GEMM_ENGINE_FLAGS, "lstm.hip": ["-mllvm", "-amdgpu-mfm
            # vfilt.hip: the VoiceFilter separator; its 64 -> 64 convs run on lipfe's implicit-GEMM kernel and its dense products
            # on a strided GEMM of the same tile shape, both with VALU epilogues on the accumulators
            "vfilt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+           # vfilt_train.hip: the VoiceFilter training step; the same two MFMA kernels as vfilt.hip and the weight gradient of the
+           # 64 -> 64 convs, all with one accumulator tile per wave
+           "vfilt_train.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
            # lipsn.hip: the ShuffleNet-v2 lip reader; one fused kernel per InvertedResidual block, its pointwise convs on fp32 MFMA
            # with BN / ReLU applied to the accumulators with plain VALU instructions, as lipfe.hip
            "lipsn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def _headers():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h", "specfe.h", "vfilt.h", "lipsn.h", "vfwave.h")]
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("dptnav.h", "ctasnet.h", "dctasnet.h", "ctasnet_train.h", "dctasnet_train.h", "davctasnet_train.h", "wavloss.h", "wavmetric.h", "lipfe.h", "specfe.h", "vfilt.h", "lipsn.h", "vfwave.h", "vfilt_train.h")]
 
 
 def source_digest() -> str:

@@ -1,17 +1,20 @@
 """VoiceFilter on libdptnav (include/vfilt.h): the mixture's magnitude spectrogram and one lip-embedding sequence per speaker
 -> one masked spectrogram per speaker.  Replaces the reference's VoiceFilter (src/model/voicefilter.py) in eval mode and
-its dataset's get_magnitude (src/datasets/base_dataset.py:167-180).  Inference only.  The two waveform ends
+its dataset's get_magnitude (src/datasets/base_dataset.py:167-180); TrainableVoiceFilter adds the training step
+(include/vfilt_train.h).  The two waveform ends
 (include/vfwave.h): voicefilter_analysis, voicefilter_waveforms, VoiceFilter.separate, VoiceFilterSeparator.
 """
 from __future__ import annotations
 
 import math
+import os
+import weakref
 from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from .engine import DptnEngine, _ConvTasNetEngineBase
+from .engine import ConvTasNetTrainEngine, DptnEngine, _ConvTasNetEngineBase
 
 EMBED_SIZES = (512, 1024)
 MAX_INPUT_SIZE = 257
@@ -317,6 +320,228 @@ class VoiceFilter(nn.Module):
         B = int(s1_video.shape[0])
         emb = self._embed(torch.cat([s1_video, s2_video], dim=0).float())
         return self._separate(mix, emb[:B], emb[B:], hop_length)
+
+
+class VoiceFilterTrainEngine(ConvTasNetTrainEngine):
+    """The VoiceFilter training step (include/vfilt_train.h), the counterpart of ConvTasNetTrainEngine: borrowed weights,
+    gradient buffers the library writes as views of ONE flat tensor (bind_grads), train_forward -> tape, train_backward, and
+    the clip / AdamW step over the flat layout.  Shapes are (B, W, Tv).  The 16 running-statistics slots keep their place in
+    the flat layout but are never written and never stepped (no_grad_keys)."""
+
+    TAPE_Z, TAPE_ACT, TAPE_LSTM_H, TAPE_FC1, TAPE_DROP, TAPE_GATES, TAPE_STATS, TAPE_CELL = range(8)
+
+    def __init__(self, input_size: int, embed_size: int = 1024, device: torch.device | str = "cuda:0", alloc=None):
+        _check_sizes(input_size, embed_size)
+        self.input_size, self.embed_size = int(input_size), int(embed_size)
+        full = voicefilter_state_dict_spec(input_size, embed_size)
+        self.no_grad_keys = frozenset(k for k, _, kind in full if kind == "buffer")
+        self._init_train("vftrain", "VoiceFilter training", [(k, s) for k, s, kind in full if kind != "count"], device, alloc,
+                         self.input_size, self.embed_size)
+
+    _input = VoiceFilterEngine._input
+
+    def flops_per_item(self, W: int, Tv: int) -> float:
+        return float(self.lib.vftrain_flops_per_item(self._h, W, Tv))
+
+    def _inputs(self, mix_magnitude, s1_embedding, s2_embedding):
+        if not isinstance(mix_magnitude, torch.Tensor) or mix_magnitude.dim() != 3:
+            raise ValueError("mix_magnitude: expected a (B, F, W) tensor")
+        if not isinstance(s1_embedding, torch.Tensor) or s1_embedding.dim() != 3:
+            raise ValueError("s1_embedding: expected a (B, Tv, E) tensor")
+        B, F, W = (int(d) for d in mix_magnitude.shape)
+        Tv = int(s1_embedding.shape[1])
+        if F != self.input_size:
+            raise ValueError(f"mix_magnitude: expected {self.input_size} frequency bins, got {F}")
+        return (self._input(mix_magnitude, "mix_magnitude", (B, F, W)), self._input(s1_embedding, "s1_embedding", (B, Tv, self.embed_size)),
+                self._input(s2_embedding, "s2_embedding", (B, Tv, self.embed_size)), B, F, W, Tv)
+
+    def train_forward(self, mix_magnitude, s1_embedding, s2_embedding, dropout_ppm: int = 350000, dropout_seed: int = 0):
+        """mix_magnitude (B, F, W), s1/s2_embedding (B, Tv, E) -> (s1_spec_pred, s2_spec_pred, tape): the reference's forward
+        in training mode; the tape lives in the engine's workspace until the next train_forward."""
+        mix, e1, e2, B, F, W, Tv = self._inputs(mix_magnitude, s1_embedding, s2_embedding)
+        self._need_bound("train_forward")
+        ws = self._workspace(B, W, Tv)
+        o1, o2 = self._empty(B, F, W), self._empty(B, F, W)
+        rc = self.lib.vftrain_train_forward(self._h, mix.data_ptr(), e1.data_ptr(), e2.data_ptr(), B, W, Tv, int(dropout_ppm),
+                                            int(dropout_seed) & 0xFFFFFFFF, o1.data_ptr(), o2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            self._stream())
+        if rc:
+            self._raise(rc, "vftrain_train_forward")
+        self._tape_id += 1
+        return o1, o2, (self._tape_id, B, W, ws.data_ptr(), Tv)
+
+    def tape_tensor(self, tape: tuple, which: int, index: int = 0) -> torch.Tensor:
+        """A view of what the forward of `tape` stored (vftrain_tape_offset; the shapes are in include/vfilt_train.h).  Valid
+        until the next train_forward."""
+        tid, B, W, wsp, Tv = tape
+        if tid != self._tape_id or self._ws is None or self._ws.data_ptr() != wsp:
+            raise RuntimeError("tape_tensor: the tape was overwritten by a later train_forward")
+        off = int(self.lib.vftrain_tape_offset(self._h, B, W, Tv, which, index))
+        if off < 0:
+            self._raise(1, "vftrain_tape_offset")
+        F, pos, rows = self.input_size, B * self.input_size * W, 2 * B * W
+        shape = {self.TAPE_Z: (B, W, F, 8) if index == 7 else (pos, 64), self.TAPE_ACT: (pos, 64), self.TAPE_LSTM_H: (rows, _HIDDEN),
+                 self.TAPE_FC1: (rows, _FC), self.TAPE_DROP: (2 * B, W), self.TAPE_GATES: (rows, 4 * _HIDDEN),
+                 self.TAPE_STATS: (8, 2, 64), self.TAPE_CELL: (rows, _HIDDEN)}[which]
+        return self._ws[off:off + 4 * math.prod(shape)].view(torch.float32).view(*shape)
+
+    def train_backward(self, mix_magnitude, s1_embedding, s2_embedding, d_out1, d_out2, tape):
+        """d loss / d predictions (B, F, W) -> the bound gradient buffers (overwritten), from the tape of train_forward."""
+        if self._grads is None:
+            raise RuntimeError("VoiceFilterTrainEngine.train_backward: gradients not bound (call bind_grads first)")
+        mix, e1, e2, B, F, W, Tv = self._inputs(mix_magnitude, s1_embedding, s2_embedding)
+        tid, tB, tW, tws, tTv = tape
+        if tid != self._tape_id or (tB, tW, tTv) != (B, W, Tv) or self._ws is None or self._ws.data_ptr() != tws:
+            raise RuntimeError("VoiceFilterTrainEngine.train_backward: the tape was overwritten by a later train_forward (one "
+                               "backward per forward, in order)")
+        d1 = self._input(d_out1, "d_out1", (B, F, W))
+        d2 = self._input(d_out2, "d_out2", (B, F, W))
+        ws = self._ws
+        rc = self.lib.vftrain_train_backward(self._h, mix.data_ptr(), e1.data_ptr(), e2.data_ptr(), B, W, Tv, d1.data_ptr(),
+                                             d2.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        if rc:
+            self._raise(rc, "vftrain_train_backward")
+
+
+class _VoiceFilterTrainFn(torch.autograd.Function):
+    """The model part of TrainableVoiceFilter's training step, as model._ConvTasNetTrainFn: forward records the tape
+    (vftrain_train_forward) and updates the running statistics, backward turns d loss / d predictions into every
+    parameter's gradient (vftrain_train_backward) and hands autograd views of one flat copy."""
+
+    @staticmethod
+    def forward(ctx, module, mix, e1, e2, *params):
+        eng = module._get_engine(mix.device)
+        if eng._grads is None:
+            eng.bind_grads()
+        ppm, seed = module._arm_dropout()
+        o1, o2, tape = eng.train_forward(mix, e1, e2, ppm, seed)
+        module._update_running(eng.tape_tensor(tape, eng.TAPE_STATS))
+        ctx.module, ctx.tape, ctx.inputs = module, tape, (mix, e1, e2)
+        return o1, o2
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        module = ctx.module
+        eng = module._engine
+        mix = ctx.inputs[0]
+        zeros = lambda g: torch.zeros_like(mix) if g is None else g.contiguous()
+        eng.train_backward(*ctx.inputs, zeros(d1), zeros(d2), ctx.tape)
+        ctx.tape = None
+        # the library's gradient buffers are reused by the next step: autograd gets its own flat copy, whose views become
+        # .grad (train.allreduce_gradients and the fused clip / AdamW find it again through `_flat_grad`)
+        flat = eng._grads_flat.clone()
+        module._flat_grad = flat
+        outs = []
+        for key, shape, kind in module._spec:
+            if kind == "param":
+                o = eng._grad_offsets[key]
+                outs.append(flat[o:o + math.prod(shape)].view(*shape))
+        return (None, None, None, None) + tuple(outs)
+
+
+class TrainableVoiceFilter(VoiceFilter):
+    """VoiceFilter with the training step on libdptnav (include/vfilt_train.h): same constructor, state_dict keys and order,
+    initialisation and parameter-count lines, and checkpoints load strictly either way.  In eval mode or under
+    torch.no_grad() the forward is VoiceFilter's inference engine (bitwise the same outputs).  In training mode with grad
+    enabled it is the reference's training-mode forward -- BatchNorm on the batch's statistics, Dropout2d(0.35) on whole
+    frames -- which records a tape, updates the eight running_mean / running_var buffers (momentum 0.1, from a device block,
+    no host synchronisation) and num_batches_tracked, and whose backward computes every parameter's gradient in HIP.  The
+    lip reader stays frozen and in eval mode; the embeddings get no gradient (one that requires grad is refused).
+    `_get_engine` is the training engine, so optim.clip_grad_norm_ / optim.FusedAdamW(weight_decay=0) / train.train_step take
+    their fused paths when the model has no lip reader attached (forward_embeddings, or model(**batch) with s1_embedding /
+    s2_embedding in the batch); with one, its frozen parameters send them to the stock paths.  torch.optim.Adam and
+    torch.nn.utils.clip_grad_norm_ work either way."""
+
+    DROPOUT = 0.35
+    MOMENTUM = 0.1
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._infer_engine: Optional[VoiceFilterEngine] = None
+        self._flat_grad: Optional[torch.Tensor] = None
+        for key, _, kind in self._spec:
+            if kind == "param":
+                self._tensor(key)._dptnav_owner = weakref.ref(self)      # lets optim.FusedAdamW / clip_grad_norm_ find the engine
+
+    def _bound(self, attr: str, make, device: torch.device):
+        if device.type != "cuda":
+            raise RuntimeError(f"VoiceFilter computes only on an AMD GPU through libdptnav (got a {device} tensor); there is no "
+                               f"CPU/PyTorch fallback")
+        eng = getattr(self, attr)
+        if eng is None or eng.device != device:
+            eng = make(self.input_size, self.embed_size, device)
+            setattr(self, attr, eng)
+        tensors = self._float_tensors()
+        for k, t in tensors.items():
+            if t.device != device:
+                raise RuntimeError(f"{k} is on {t.device} but the input is on {device}: call model.to(device)")
+        if not eng.bound_to(tensors):
+            eng.bind(tensors)
+        return eng
+
+    def _get_engine(self, device: torch.device) -> VoiceFilterTrainEngine:
+        return self._bound("_engine", VoiceFilterTrainEngine, device)
+
+    def _get_infer_engine(self, device: torch.device) -> VoiceFilterEngine:
+        return self._bound("_infer_engine", VoiceFilterEngine, device)
+
+    def _need_eval(self):
+        pass
+
+    def _separate(self, mix, s1_embedding, s2_embedding, hop_length):
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("TrainableVoiceFilter: separate / separate_embeddings reconstruct waveforms from the inference "
+                               "forward; call model.eval() or use torch.no_grad()")
+        return super()._separate(mix, s1_embedding, s2_embedding, hop_length)
+
+    def _arm_dropout(self):
+        """A fresh dropout seed per training forward, model._DPTNBase._arm_dropout's scheme: torch's initial seed, a step
+        counter and the data-parallel rank (ranks share torch's seed)."""
+        self._drop_step = getattr(self, "_drop_step", 0) + 1
+        rank = int(os.environ.get("RANK", "0"))
+        seed = (torch.initial_seed() * 2654435761 + self._drop_step * 40503 + rank * 0x632BE5AB) & 0x7FFFFFFF
+        return int(round(self.DROPOUT * 1e6)), seed
+
+    def _update_running(self, block: torch.Tensor):
+        """block: the tape's [8][2][64] batch means and unbiased variances, on the device"""
+        with torch.no_grad():
+            for l, (_, bi, cout, *_rest) in enumerate(_CNN):
+                node = getattr(self.cnn_layers, str(bi))
+                node.running_mean.mul_(1.0 - self.MOMENTUM).add_(block[l, 0, :cout], alpha=self.MOMENTUM)
+                node.running_var.mul_(1.0 - self.MOMENTUM).add_(block[l, 1, :cout], alpha=self.MOMENTUM)
+                node.num_batches_tracked.add_(1)
+
+    def _own_parameters(self):
+        return [self._tensor(key) for key, _, kind in self._spec if kind == "param"]
+
+    def forward_embeddings(self, mix_magnitude, s1_embedding, s2_embedding, out=None, ws=None):
+        """The separator alone: mix_magnitude (B, F, W), s1/s2_embedding (B, Tv, embed_size) -> {"s1_spec_pred", "s2_spec_pred"}.
+        Training mode with grad enabled: the training step (out / ws do not apply); otherwise VoiceFilter's inference."""
+        params = self._own_parameters()
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            for name, e in (("s1_embedding", s1_embedding), ("s2_embedding", s2_embedding)):
+                if isinstance(e, torch.Tensor) and e.requires_grad:
+                    raise NotImplementedError(f"TrainableVoiceFilter: no gradient is computed for {name} (it comes from a frozen "
+                                              f"lip-reader): pass it detached")
+            if out is not None or ws is not None:
+                raise ValueError("TrainableVoiceFilter: out / ws belong to the inference path")
+            s1, s2 = _VoiceFilterTrainFn.apply(self, mix_magnitude, s1_embedding, s2_embedding, *params)
+        else:
+            s1, s2 = self._get_infer_engine(mix_magnitude.device).forward(mix_magnitude, s1_embedding, s2_embedding, out=out, ws=ws)
+        return {"s1_spec_pred": s1, "s2_spec_pred": s2}
+
+    def forward(self, mix_magnitude, s1_video=None, s2_video=None, s1_embedding=None, s2_embedding=None, **batch):
+        """VoiceFilter.forward; a batch that carries precomputed s1_embedding / s2_embedding skips the lip reader.  They are
+        (B, Tv, embed_size), or (B, embed_size, Tv) as make_embeddings stores them and the loader delivers them (transposed
+        here, as VoiceFilterSeparator does)."""
+        if s1_embedding is not None and s2_embedding is not None:
+            E = self.embed_size
+            if s1_embedding.dim() == 3 and s1_embedding.shape[2] != E and s1_embedding.shape[1] == E:
+                s1_embedding, s2_embedding = s1_embedding.transpose(1, 2), s2_embedding.transpose(1, 2)
+            return self.forward_embeddings(mix_magnitude, s1_embedding, s2_embedding)
+        if s1_video is None or s2_video is None:
+            raise ValueError("TrainableVoiceFilter: the batch has neither s1_embedding / s2_embedding nor s1_video / s2_video")
+        return super().forward(mix_magnitude, s1_video, s2_video)
 
 
 class VoiceFilterSeparator:
