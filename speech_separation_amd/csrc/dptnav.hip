@@ -35,12 +35,18 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct PathWeights {
-  const float *in_w, *in_b, *out_w, *out_b, *ln1_w, *ln1_b;
-  const float *w_ih[2], *w_hh[2], *b_ih[2], *b_hh[2];
-  const float *ffn_w, *ffn_b, *ln2_w, *ln2_b;
+// The parameters of one path: where they are in memory (PathWeights) and their slots in the weight table (PathSlots: the index
+// into dptnav_ctx::names / ptr / gptr and into a half's gradient scratch).  What a DPRNN block does not have is null / -1; the
+// reverse direction of a unidirectional path repeats the forward one.
+template <class T>
+struct PathParams {
+  T in_w, in_b, out_w, out_b, ln1_w, ln1_b;
+  T w_ih[2], w_hh[2], b_ih[2], b_hh[2];
+  T ffn_w, ffn_b, ln2_w, ln2_b;
   int ndir;
 };
+using PathWeights = PathParams<const float*>;
+using PathSlots = PathParams<int>;
 
 constexpr int QUEUE_SLOTS = 1024;
 
@@ -242,6 +248,7 @@ struct dptnav_ctx {
   int num_cus = 256;
   int device_id = 0;   // the HIP device that was current at dptnav_create
   std::vector<PathWeights> pw;   // [2*block + path], rebuilt by dptnav_bind_weights
+  std::vector<PathSlots> ps;     // ... and where each of them sits in the weight table
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -364,40 +371,33 @@ void build_names(dptnav_ctx* c) {
   c->ptr.assign(c->names.size(), nullptr);
 }
 
-PathWeights path_weights(const dptnav_ctx* c, int block, int path) {
+// Path (block, path)'s parameters by name: their slots, and from dptnav_ctx::ptr where they are
+void resolve_path(const dptnav_ctx* c, int block, int path, PathSlots* s, PathWeights* w) {
   const std::string pre =
       "dprnn.model." + std::to_string(block) + (path == 0 ? ".intra_chunk_block." : ".inter_chunk_block.");
-  PathWeights p{};
-  p.ndir = (path == 0 || c->cfg.bidir) ? 2 : 1;
+  auto put = [&](const std::string& leaf, int* slot, const float** ptr) {   // (a name the model does not have: -1, null)
+    *slot = c->slot(pre + leaf);
+    *ptr = *slot < 0 ? nullptr : c->ptr[(size_t)*slot];
+  };
+  s->ndir = w->ndir = (path == 0 || c->cfg.bidir) ? 2 : 1;
   const bool dptn = c->cfg.arch == 0;
-  if (dptn) {
-    p.in_w = c->w(pre + "mha.in_proj_weight");
-    p.in_b = c->w(pre + "mha.in_proj_bias");
-    p.out_w = c->w(pre + "mha.out_proj.weight");
-    p.out_b = c->w(pre + "mha.out_proj.bias");
-    p.ln1_w = c->w(pre + "ln1.weight");
-    p.ln1_b = c->w(pre + "ln1.bias");
+  put("mha.in_proj_weight", &s->in_w, &w->in_w);
+  put("mha.in_proj_bias", &s->in_b, &w->in_b);
+  put("mha.out_proj.weight", &s->out_w, &w->out_w);
+  put("mha.out_proj.bias", &s->out_b, &w->out_b);
+  put("ln1.weight", &s->ln1_w, &w->ln1_w);
+  put("ln1.bias", &s->ln1_b, &w->ln1_b);
+  for (int d = 0; d < 2; ++d) {
+    const std::string sfx = d == 1 && s->ndir == 2 ? "_reverse" : "";
+    put("rnn.weight_ih_l0" + sfx, &s->w_ih[d], &w->w_ih[d]);
+    put("rnn.weight_hh_l0" + sfx, &s->w_hh[d], &w->w_hh[d]);
+    put("rnn.bias_ih_l0" + sfx, &s->b_ih[d], &w->b_ih[d]);
+    put("rnn.bias_hh_l0" + sfx, &s->b_hh[d], &w->b_hh[d]);
   }
-  p.w_ih[0] = c->w(pre + "rnn.weight_ih_l0");
-  p.w_hh[0] = c->w(pre + "rnn.weight_hh_l0");
-  p.b_ih[0] = c->w(pre + "rnn.bias_ih_l0");
-  p.b_hh[0] = c->w(pre + "rnn.bias_hh_l0");
-  if (p.ndir == 2) {
-    p.w_ih[1] = c->w(pre + "rnn.weight_ih_l0_reverse");
-    p.w_hh[1] = c->w(pre + "rnn.weight_hh_l0_reverse");
-    p.b_ih[1] = c->w(pre + "rnn.bias_ih_l0_reverse");
-    p.b_hh[1] = c->w(pre + "rnn.bias_hh_l0_reverse");
-  } else {
-    p.w_ih[1] = p.w_ih[0];
-    p.w_hh[1] = p.w_hh[0];
-    p.b_ih[1] = p.b_ih[0];
-    p.b_hh[1] = p.b_hh[0];
-  }
-  p.ffn_w = c->w(pre + (dptn ? "ffn.1.weight" : "fc.weight"));
-  p.ffn_b = c->w(pre + (dptn ? "ffn.1.bias" : "fc.bias"));
-  p.ln2_w = c->w(pre + (dptn ? "ln2.weight" : "norm1d.weight"));
-  p.ln2_b = c->w(pre + (dptn ? "ln2.bias" : "norm1d.bias"));
-  return p;
+  put(dptn ? "ffn.1.weight" : "fc.weight", &s->ffn_w, &w->ffn_w);
+  put(dptn ? "ffn.1.bias" : "fc.bias", &s->ffn_b, &w->ffn_b);
+  put(dptn ? "ln2.weight" : "norm1d.weight", &s->ln2_w, &w->ln2_w);
+  put(dptn ? "ln2.bias" : "norm1d.bias", &s->ln2_b, &w->ln2_b);
 }
 
 int make_plan(dptnav_ctx* c, int B, int64_t T, int Tv, Plan* p) {
@@ -1325,6 +1325,20 @@ int begin_bwd_run(dptnav_ctx* c, BwdRun* br, float* ws, const BwdPlan& bp, hipSt
   return DPTNAV_OK;
 }
 
+// sums of the NN x KK partial tiles (fragment order) a launch left in `slab` -> grad (overwrite); bias_grad (optional): the
+// column-sum rows colslab[nslabs][NN] of the same launch, summed by extra workgroups of this one
+template <int NN, int KK>
+int reduce_slabs(dptnav_ctx* c, hipStream_t st, const char* what, const float* slab, int nslabs, const float* colslab, float* grad,
+                 float* bias_grad) {
+  constexpr int64_t count = (int64_t)NN * KK;
+  FragOuts outs{};
+  outs.out[0] = grad;
+  hipLaunchKernelGGL((slab_reduce_frag_kernel<NN / 128, KK / 32>), dim3((unsigned)(count / 128) + (bias_grad ? (NN + 31) / 32 : 0)),
+                     dim3(256), 0, st, slab, nslabs, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
+  LAUNCH_CHECK(c, what);
+  return DPTNAV_OK;
+}
+
 // dW[NN][KK] = sum_tokens Y^T X  ->  grad (overwrite);  bias_grad (optional): column sums of Y, fused into the same pass
 template <int NN, int KK, class YL, class XL>
 int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, const YL& yl, const XL& xl, float* grad,
@@ -1333,8 +1347,9 @@ int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, co
   const int grid = cap_grid(ntiles, br.pl.slab_wgs);
   float* slab = br.ws + br.pl.slab;
   float* colslab = slab + (size_t)grid * NN * KK;   // behind the weight slabs (BWD_SLAB_WGS x 512 x 128 floats in all)
-  if (bias_grad) {
-    auto kern = wgrad_kernel<NN, KK, YL, XL, true>;
+  auto launch = [&](auto with_bias) -> int {        // the kernel with the column sums and the one without
+    constexpr bool BIAS = decltype(with_bias)::value;
+    auto kern = wgrad_kernel<NN, KK, YL, XL, BIAS>;
     static PerDeviceOnce ready;
     if (!ready.done(c->device_id)) {
       if (int rc = set_lds(c, kern, lds, what)) return rc;
@@ -1342,27 +1357,13 @@ int launch_wgrad(dptnav_ctx* c, BwdRun& br, const char* what, int64_t ntiles, co
     }
     unsigned* const queue = br.lane.tk.take(1);
     if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, colslab);
-  } else {
-    auto kern = wgrad_kernel<NN, KK, YL, XL, false>;
-    static PerDeviceOnce ready;
-    if (!ready.done(c->device_id)) {
-      if (int rc = set_lds(c, kern, lds, what)) return rc;
-      ready.set(c->device_id);
-    }
-    unsigned* const queue = br.lane.tk.take(1);
-    if (!queue) return c->fail(DPTNAV_ERR_INVALID, "%s: ticket counters exhausted", what);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab, (float*)nullptr);
-  }
-  LAUNCH_CHECK(c, what);
-  constexpr int64_t count = (int64_t)NN * KK;
-  FragOuts outs{};
-  outs.out[0] = grad;
-  // the bias gradient's column sums are reduced by extra workgroups of the same launch
-  hipLaunchKernelGGL((slab_reduce_frag_kernel<NN / 128, KK / 32>), dim3((unsigned)(count / 128) + (bias_grad ? (NN + 31) / 32 : 0)),
-                     dim3(256), 0, br.lane.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
-  LAUNCH_CHECK(c, what);
-  return DPTNAV_OK;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, br.lane.st, (int)ntiles, c->opt_deterministic ? nullptr : queue, yl, xl, slab,
+                       BIAS ? colslab : (float*)nullptr);
+    LAUNCH_CHECK(c, what);
+    return DPTNAV_OK;
+  };
+  if (int rc = bias_grad ? launch(std::true_type{}) : launch(std::false_type{})) return rc;
+  return reduce_slabs<NN, KK>(c, br.lane.st, what, slab, grid, colslab, grad, bias_grad);
 }
 
 // the same for the shapes wgrad_kernel is not built for (NN not a multiple of 128): wgrad_generic_kernel, row-major partial
@@ -1383,20 +1384,6 @@ int launch_wgrad_generic(dptnav_ctx* c, BwdRun& br, const char* what, int64_t nt
   LAUNCH_CHECK(c, what);
   constexpr int64_t count = (int64_t)NN * KK;
   hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, br.lane.st, slab, grid, count, grad, 0);
-  LAUNCH_CHECK(c, what);
-  return DPTNAV_OK;
-}
-
-// sums of the partial tiles / column sums a WgradRider launch (launch_gemm) left in the slab region
-template <int NN, int KK>
-int reduce_rider(dptnav_ctx* c, BwdRun& br, const char* what, int grid, int col_after, float* grad, float* bias_grad) {
-  constexpr int64_t count = (int64_t)NN * KK;
-  float* slab = br.ws + br.pl.slab;
-  float* colslab = slab + (size_t)col_after * count;   // where the launch put its column-sum rows
-  FragOuts outs{};
-  outs.out[0] = grad;
-  hipLaunchKernelGGL((slab_reduce_frag_kernel<NN / 128, KK / 32>), dim3((unsigned)(count / 128) + (bias_grad ? (NN + 31) / 32 : 0)),
-                     dim3(256), 0, br.lane.st, slab, grid, count, outs, (int64_t)0, 1, colslab, bias_grad ? NN : 0, bias_grad);
   LAUNCH_CHECK(c, what);
   return DPTNAV_OK;
 }
@@ -1451,243 +1438,247 @@ int launch_colsum(dptnav_ctx* c, BwdRun& br, const char* what, const float* Y, i
   return DPTNAV_OK;
 }
 
-// One DPRNN block half backward (IntraChunkRNN / InterChunkRNN, dprnn.py:24-47,65-89):
-//   forward   h = biLSTM(x);  v = h W_fc^T + b_fc;  out = LayerNorm(v) + x
-//   backward  dz = LayerNorm'(d_out)  [tape: zn, rstd];  dW_fc = dz^T h, db_fc = colsum dz;  dh = dz W_fc;  BPTT -> dP;
-//             dW_ih = dP^T x, dW_hh = dP^T h_{t-1}, db = colsum dP;  d_in = d_out (residual) + dP_f W_ih_f + dP_b W_ih_b
-// The kernels are the DPTN chain's (ln_backward_kernel, BPTT, weight gradients, data-gradient GEMMs); no attention half.
-template <int N>
-int run_path_backward_dprnn(dptnav_ctx* c, BwdRun& br, int block, int path, const float* x_in, const float* d_out, float* d_in,
-                            int B, int S, float* tape, const PathTape& tp) {
-  constexpr int WRn = N == 128 ? 1 : 2, WCn = N == 128 ? 4 : 2, BMn = 32 * WRn;
-  const dptnav_config& g = c->cfg;
-  const PathWeights& w = c->pw[2 * block + path];
-  const std::string pre = "dprnn.model." + std::to_string(block) + (path == 0 ? ".intra_chunk_block." : ".inter_chunk_block.");
-  auto G = [&](const char* leaf) { return br.gptr[c->slot(pre + leaf)]; };
-  const int nd = w.ndir;                 // 2, or 1 for the inter-chunk path of a bidir = False model (dprnn.py:56-63)
-  if (!tp.zn2) return c->fail(DPTNAV_ERR_INVALID, "training step of DPRNN blocks needs option ln_tape = 1");
-  const int K = g.chunk_size;
-  const int64_t M = (int64_t)B * S * K;
-  const SeqGeom geom = make_geom(path, B, S, K);
-  Lane& lane = br.lane;
-  hipStream_t st = lane.st;
-  float *hc = tape + tp.hc, *gates = tape + tp.gates, *cst = tape + tp.cst;
-  float *DZ = br.ws + br.pl.dz, *DHb = br.ws + br.pl.dh, *DG = br.ws + br.pl.dg, *LNP = br.ws + br.pl.lnp;
-  const int64_t ntiles = (M + 31) / 32, ntiles_n = (M + BMn - 1) / BMn;
-  // 1. LayerNorm backward from the tape
-  {
-    const int64_t npass = (M + (256 / (N / 4)) - 1) / (256 / (N / 4));
-    const int lgrid = (int)std::min<int64_t>(std::min<int64_t>(BWD_LNP_WGS, 4 * (int64_t)c->num_cus), (npass + 3) / 4);
-    ProfScope ps(c, CAT_FFN, st);
-    hipLaunchKernelGGL(ln_backward_kernel<N>, dim3(lgrid), dim3(256), 0, st, d_out, tape + tp.zn2, tape + tp.rs2, w.ln2_w, DZ, LNP, M);
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, lgrid, (int64_t)2 * N, G("norm1d.weight"),
-                       G("norm1d.bias"), N);
-    LAUNCH_CHECK(c, "norm1d backward");
-  }
-  // 2. fc gradients, d h = dz W_fc
-  if (nd == 1) {
-    {
-      ALoadCols yl{DZ, M, N, 0, 32};
-      ALoadCols xl{hc, M, LSTM_H, 0, 32};
-      if constexpr (N == 128) {
-        if (int rc = launch_wgrad<N, LSTM_H>(c, br, "d fc weight + bias", ntiles, yl, xl, G("fc.weight"), G("fc.bias"))) return rc;
-      } else {
-        if (int rc = launch_wgrad_generic<N, LSTM_H>(c, br, "d fc weight", ntiles, yl, xl, G("fc.weight"))) return rc;
-        if (int rc = launch_colsum<N>(c, br, "d fc bias", DZ, M, N, 0, G("fc.bias"))) return rc;
-      }
-    }
-    {
-      ALoadDense al{DZ, M, N, 32};
-      EpiAddMaskStoreT<false, false> ep{DHb, nullptr, nullptr, M, LSTM_H, 32, LSTM_H};
-      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
-    }
+// The launch names of one Linear's backward
+struct LinearNames {
+  const char *both, *weight, *bias;   // dW with db / dW alone / db alone
+  const char *dgrad, *ride;           // the data gradient, alone / with dW and db riding
+};
+// The gradients of one Linear, Y = X W^T + b with W [NN][KK], from dY [M][NN] (dense) and the loader of X:  dW = dY^T X and
+// db = column sums of dY (optional).  wgrad_kernel forms both in one pass where it is built for the shape (NN a multiple of
+// 128); elsewhere the generic kernel and a column-sum pass of its own.
+template <int NN, int KK, class XL>
+int weight_grads(dptnav_ctx* c, BwdRun& br, const LinearNames& nm, const float* dY, int64_t M, const XL& xl, float* dW, float* db) {
+  const ALoadCols yl{dY, M, NN, 0, 32};
+  const int64_t ntiles = (M + 31) / 32;
+  if constexpr (NN % 128 == 0) {
+    return launch_wgrad<NN, KK>(c, br, db ? nm.both : nm.weight, ntiles, yl, xl, dW, db);
   } else {
-    {
-      ALoadCols yl{DZ, M, N, 0, 32};
-      ALoadCols xl{hc, M, 2 * LSTM_H, 0, 32};
-      if constexpr (N == 128) {
-        if (int rc = launch_wgrad<N, 2 * LSTM_H>(c, br, "d fc weight + bias", ntiles, yl, xl, G("fc.weight"), G("fc.bias"))) return rc;
-      } else {
-        if (int rc = launch_wgrad_generic<N, 2 * LSTM_H>(c, br, "d fc weight", ntiles, yl, xl, G("fc.weight"))) return rc;
-        if (int rc = launch_colsum<N>(c, br, "d fc bias", DZ, M, N, 0, G("fc.bias"))) return rc;
-      }
-    }
-    {
-      ALoadDense al{DZ, M, N, 32};
-      EpiAddMaskStoreT<false, false> ep{DHb, nullptr, nullptr, M, 2 * LSTM_H, 32, 2 * LSTM_H};
-      if (int rc = launch_gemm<N, 2, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H)) return rc;
-    }
+    if (int rc = launch_wgrad_generic<NN, KK>(c, br, nm.weight, ntiles, yl, xl, dW)) return rc;
+    return db ? launch_colsum<NN>(c, br, nm.bias, dY, M, NN, 0, db) : DPTNAV_OK;
   }
-  // 3. LSTM backward through time (tile height as in the forward that wrote the tape)
-  const bool use16 = lstm_use16(c, geom, nd, M);
-  const int ntl = use16 ? (geom.nseq + 15) / 16 : geom.nst;
-  if (br.lstm_wait && hipStreamWaitEvent(st, br.lstm_wait, 0) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "bptt stagger wait");
-  {
-    ProfScope ps(c, CAT_LSTM, st);
-    const int rc = use16 ? lstm_bptt16_launch(ntl, nd, st, gates, cst, w.w_hh[0], w.w_hh[1], DHb, nd * LSTM_H, DG, nd * 512, (int)M, geom, LNP)
-                         : lstm_bptt_launch(geom.nst, nd, st, gates, cst, w.w_hh[0], w.w_hh[1], DHb, nd * LSTM_H, DG, nd * 512, (int)M, geom,
-                                            LNP);
-    if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm bptt: %s", hipGetErrorString((hipError_t)rc));
-  }
-  if (br.lstm_record && hipEventRecord(br.lstm_record, st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "bptt stagger record");
-  // 4. LSTM parameter gradients (the LSTM's input is the block input x)
-  for (int d = 0; d < nd; ++d) {
-    const char* sfx = d ? "_reverse" : "";
-    const std::string wih = std::string("rnn.weight_ih_l0") + sfx, whh = std::string("rnn.weight_hh_l0") + sfx,
-                      bih = std::string("rnn.bias_ih_l0") + sfx, bhh = std::string("rnn.bias_hh_l0") + sfx;
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3(512 / 32), dim3(256), 0, st, LNP + (size_t)d * ntl * 512, ntl, (int64_t)512,
-                       G(bih.c_str()), G(bhh.c_str()), -1);
-    LAUNCH_CHECK(c, "d lstm bias");
-    const ALoadDense xl{x_in, M, N, 32};
-    const ALoadSeqShift hl = make_seq_shift(hc, M, nd * LSTM_H, d * LSTM_H, 32, d ? -1 : 1, geom);
-    for (int half = 0; half < 2; ++half) {
-      const ALoadCols yl{DG, M, nd * 512, d * 512 + half * 256, 32};
-      if (int rc = launch_wgrad<256, N>(c, br, "d w_ih", ntiles, yl, xl, G(wih.c_str()) + half * 256 * N)) return rc;
-      if (int rc = launch_wgrad<256, LSTM_H>(c, br, "d w_hh", ntiles, yl, hl, G(whh.c_str()) + half * 256 * LSTM_H)) return rc;
-    }
-  }
-  // 5. d_in = d_out (residual) + dP_f W_ih_f + dP_b W_ih_b
-  for (int d = 0; d < nd; ++d) {
-    if constexpr (N == 128) {
-      ALoadCols al{DG, M, nd * 512, d * 512, 32};
-      EpiAddMaskStoreT<true, false> ep{d_in, d == 0 ? d_out : d_in, nullptr, M, N, 32, N};
-      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, "d x", w.w_ih[d], ntiles, 1, al, ep, nullptr, N)) return rc;
-    } else {
-      for (int half = 0; half < 2; ++half) {
-        ALoadCols al{DG, M, nd * 512, d * 512 + half * 256, BMn};
-        EpiAddMaskStoreT<true, false> ep{d_in, d == 0 && half == 0 ? d_out : d_in, nullptr, M, N, BMn, N};
-        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, lane, CAT_LSTM_PRE, "d x", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1, al,
-                                                         ep, nullptr, N))
-          return rc;
-      }
-    }
-  }
+}
+
+// ---- the route of one path's backward: every policy line and every refusal, ahead of the first launch ----------------
+// Forward of a block half (dptn.py:36-52; DPRNN, dprnn.py:24-47,65-89, has no attention half and no ReLU):
+//   qkv = x W_in^T + b_in;  att = attention(qkv);  y1 = LN1(att W_o^T + b_o + x);  h = LSTM(y1);  out = LN2(relu(h) W_f^T + b_f + y1)
+//   DPRNN:  h = LSTM(x);  out = LayerNorm(h W_fc^T + b_fc) + x
+// Backward, the stages below in order:  dz = LN2'(d_out);  dW_f, db_f, dh = dz W_f (ReLU gate);  BPTT -> dP;  LSTM gradients;
+//   d y1 = dz + dP W_ih  (DPRNN: d_in = d_out + dP W_ih, the end);  dz = LN1'(d y1);  dW_o, db_o, d att = dz W_o;
+//   attention backward -> d qkv;  dW_in, db_in;  d_in = dz + d qkv W_in.
+//
+// Invariants of route + stages against the one function they replace: for every arm the sequence of launches, their grids,
+// arguments, streams and events is the same, and so is the order of the inject_failure ticks (launch_gemm, try_dedicated)
+// and of the ticket takes; the launch names are the same; so is the set of kernel instantiations (the `if constexpr` guards
+// of the stages keep a helper from instantiating a gemm_ws_kernel / wgrad_kernel / wgrad2_kernel form no arm launches).
+// One exception: the tape LayerNorm backward of an N = 64 DPTN path takes its grid from the kernel's own rows per pass
+// (ln_backward_grid), as DPRNN always did -- fewer workgroups below ~65 k tokens, the ln1 / ln2 gradients' fp32 partial
+// sums regrouped.
+enum LinearForm {
+  LINEAR_ALONE,      // weight_grads, then the data-gradient GEMM
+  LINEAR_RIDER,      // ONE launch: the data-gradient GEMM stages the dz tile anyway and forms dW / db on the side (WgradRider, gemm_ws.h)
+  LINEAR_RIDER_R     // ... dgrad_r.hip tried first
+};
+enum LstmWgradForm {
+  LSTM_WGRAD_SEPARATE,   // W_ih and W_hh gradients as launches of their own, per direction and half of the gate rows
+  LSTM_WGRAD_PAIRED,     // both in ONE pass over dP, the four (direction, half) slices in one launch (wgrad2_kernel)
+  LSTM_WGRAD_SIDE        // ... on the half's side stream (BwdRun::side)
+};
+struct BwdRoute {
+  bool dptn;                 // the block has an attention half
+  int nd;                    // LSTM directions: 2, or 1 for the inter-chunk path of a bidir = False model (dptn.py:60, dprnn.py:56-63)
+  bool use16;                // BPTT tile height, as in the forward that wrote the tape (lstm_use16)
+  int ntl;                   // BPTT workgroups per direction = partial bias rows
+  bool pack;                 // the path's PACK_BWD slot is needed
+  bool ln2_tape, ln1_tape;   // LayerNorm backward from the tape's zn / rstd (option ln_tape), or by a recompute GEMM
+  LinearForm ffn, outp;
+  LstmWgradForm lstm_wgrad;
+  bool dgrad_t;              // dgrad_t.hip tried first for d y1 and d x
+  bool attn_long;            // attention backward: the streaming pair (attn_long_train.h), or attention_bwd_kernel<DH, nkb>
+  int nkb;                   // 32-key blocks of a sequence
+};
+
+template <int N>
+int route_path_backward(dptnav_ctx* c, const BwdRun& br, int block, int path, int B, int S, const PathTape& tp, BwdRoute* r) {
+  const SeqGeom geom = make_geom(path, B, S, c->cfg.chunk_size);
+  const int64_t M = (int64_t)B * S * c->cfg.chunk_size;
+  r->dptn = c->cfg.arch == 0;
+  r->nd = c->pw[2 * block + path].ndir;
+  r->ln2_tape = tp.zn2 != 0;
+  r->ln1_tape = tp.zn1 != 0;
+  if (!r->dptn && !r->ln2_tape) return c->fail(DPTNAV_ERR_INVALID, "training step of DPRNN blocks needs option ln_tape = 1");
+  if (r->dptn && N != 128 && !(r->ln2_tape && r->ln1_tape))   // the recompute GEMMs are built for 128 features
+    return c->fail(DPTNAV_ERR_INVALID, "training with num_features = %d needs option ln_tape = 1", N);
+  r->use16 = lstm_use16(c, geom, r->nd, M);
+  r->ntl = r->use16 ? (geom.nseq + 15) / 16 : geom.nst;
+  // N = 128 (BASELINE config 4): the tuned kernels (weight-gradient riders, wgrad2, dgrad_t / dgrad_r on the weight copies of
+  // PACK_BWD);  N = 64 (DPTNWavEncDec) and DPRNN: the same chain with stand-alone weight-gradient launches and the GEMM engine
+  const bool tuned = r->dptn && N == 128;
+  r->pack = tuned;
+  const LinearForm rider = c->opt_dgrad_r ? LINEAR_RIDER_R : LINEAR_RIDER;
+  r->ffn = tuned && c->opt_wgrad_ride && r->nd == 2 ? rider : LINEAR_ALONE;   // one direction: W_f is [N][128]; the plain schedule
+  r->outp = tuned && c->opt_wgrad_ride ? rider : LINEAR_ALONE;
+  // wgrad2 pairs two X operands of equal width (N == LSTM_H), four slices (two directions).  On the side stream where the
+  // half has one: nothing needs dW before the step ends (BwdRun::side)
+  const bool paired = r->dptn && c->opt_wgrad2 && N == LSTM_H && r->nd == 2;
+  r->lstm_wgrad = !paired ? LSTM_WGRAD_SEPARATE : br.side.st != nullptr ? LSTM_WGRAD_SIDE : LSTM_WGRAD_PAIRED;
+  r->dgrad_t = tuned && c->opt_dgrad_t;
+  r->nkb = (geom.len + 31) / 32;
+  r->attn_long = c->opt_train_long_seq == 2 || (c->opt_train_long_seq == 1 && r->nkb > 8);   // tiles of fixed size, any length
+  if (r->dptn && !r->attn_long && r->nkb > 8) return c->fail(DPTNAV_ERR_INVALID, "attention bwd: sequence length %d > 256", geom.len);
   return DPTNAV_OK;
 }
 
+// ---- the stages of one path's backward ----------------------------------------------------------------------------------
+// What every stage reads; run_path_backward builds it once.
+struct BwdCall {
+  dptnav_ctx* c;
+  BwdRun& br;
+  const PathWeights& w;
+  const PathSlots& s;      // gradient destinations: G(s.x)
+  SeqGeom geom;
+  int block, path;
+  int64_t M, ntiles, ntiles_n;   // tokens; GEMM-engine tiles of 32 and of PathTile::BM tokens
+  const float *x_in, *d_out;
+  float* d_in;
+  const float *qkv, *att, *y1, *hc, *gates, *cst, *astats, *amask, *zn1, *rs1, *zn2, *rs2;   // the tape
+  float *DZ, *DH, *DY1, *DATT, *DQKV, *LNP;   // the backward workspace (dP: chosen by lstm_backward)
+  const float* wpk;                           // the path's PACK_BWD slot (BwdRoute::pack)
+  float* G(int slot) const { return br.gptr[slot]; }
+  const float* packed(size_t at) const { return wpk ? wpk + at : nullptr; }
+};
+
+// workgroups of ln_backward_kernel<N>: four passes of 256 / (N / 4) rows each per trip of its loop
 template <int N>
-int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const float* x_in, const float* d_out,
-                      float* d_in, int B, int S, float* tape, const PathTape& tp) {
-  constexpr int GROUP = N / 4, DH = N / 4;
-  // N = 128 (BASELINE config 4): the tuned kernels (weight-gradient riders, wgrad2, fragment-order partial tiles);  N = 64
-  // (DPTNWavEncDec): the same chain with the generic weight-gradient kernel where a tuned shape does not exist and
-  // 64-row x 64-column tiles for the data-gradient GEMMs whose output is N wide
-  constexpr int WRn = N == 128 ? 1 : 2, WCn = N == 128 ? 4 : 2, BMn = 32 * WRn;
-  if (c->cfg.arch == 1) return run_path_backward_dprnn<N>(c, br, block, path, x_in, d_out, d_in, B, S, tape, tp);
-  const dptnav_config& g = c->cfg;
-  const PathWeights& w = c->pw[2 * block + path];
-  const std::string pre = "dprnn.model." + std::to_string(block) + (path == 0 ? ".intra_chunk_block." : ".inter_chunk_block.");
-  auto G = [&](const char* leaf) { return br.gptr[c->slot(pre + leaf)]; };
-  const int nd = w.ndir;                 // 2, or 1 for the inter-chunk path of a bidir = False model (dptn.py:60)
-  const int K = g.chunk_size;
-  const int64_t M = (int64_t)B * S * K;
-  const SeqGeom geom = make_geom(path, B, S, K);
+int ln_backward_grid(const dptnav_ctx* c, int64_t M) {
+  constexpr int rows = 256 / (N / 4);
+  const int64_t npass = (M + rows - 1) / rows;
+  return (int)std::min<int64_t>(std::min<int64_t>(BWD_LNP_WGS, 4 * (int64_t)c->num_cus), (npass + 3) / 4);
+}
+// DZ = LayerNorm'(dout) from the tape's zn / rstd; the LayerNorm's own gradients
+template <int N>
+int ln_backward_tape(const BwdCall& bc, const char* what, const float* dout, const float* zn, const float* rs, const float* gamma,
+                     float* d_gamma, float* d_beta) {
+  hipStream_t st = bc.br.lane.st;
+  const int grid = ln_backward_grid<N>(bc.c, bc.M);
+  ProfScope ps(bc.c, CAT_FFN, st);
+  hipLaunchKernelGGL(ln_backward_kernel<N>, dim3(grid), dim3(256), 0, st, dout, zn, rs, gamma, bc.DZ, bc.LNP, bc.M);
+  hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, bc.LNP, grid, (int64_t)2 * N, d_gamma, d_beta, N);
+  LAUNCH_CHECK(bc.c, what);
+  return DPTNAV_OK;
+}
+// ... by recomputing z = A W^T + bias + res in a GEMM whose epilogue applies the derivative (128 features)
+template <int KIN, class AL>
+int ln_backward_recompute(const BwdCall& bc, int cat, const char* what, const char* what_grads, const AL& al, const float* W,
+                          const float* bias, const float* res, const float* gamma, const float* dout, float* d_gamma, float* d_beta) {
+  constexpr int N = 128;
+  int grid = 0;
+  EpiLNBackward<N / 4, 0> ep{bc.DZ, bias, res, gamma, dout, bc.LNP, bc.M, N, 32};
+  if (int rc = launch_gemm<KIN, 1, 1, 4>(bc.c, bc.br.lane, cat, what, W, bc.ntiles, 1, al, ep, nullptr, KIN, &grid)) return rc;
+  hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, bc.br.lane.st, bc.LNP, grid, (int64_t)2 * N, d_gamma,
+                     d_beta, N);
+  LAUNCH_CHECK(bc.c, what_grads);
+  return DPTNAV_OK;
+}
+// d_out through LayerNorm 2 (DPRNN: norm1d), d y1 through LayerNorm 1
+template <int N>
+int ln2_backward(const BwdCall& bc, const BwdRoute& r) {
+  const PathWeights& w = bc.w;
+  float *dg = bc.G(bc.s.ln2_w), *db = bc.G(bc.s.ln2_b);
+  if (r.ln2_tape) return ln_backward_tape<N>(bc, r.dptn ? "ln2 backward" : "norm1d backward", bc.d_out, bc.zn2, bc.rs2, w.ln2_w, dg, db);
+  if constexpr (N == 128)
+    return ln_backward_recompute<2 * LSTM_H>(bc, CAT_FFN, "ffn recompute + ln2 bwd", "ln2 grads", ALoadColsReLU{bc.hc, bc.M, 2 * LSTM_H, 0, 32},
+                                             w.ffn_w, w.ffn_b, bc.y1, w.ln2_w, bc.d_out, dg, db);
+  return DPTNAV_OK;   // (refused by the route)
+}
+template <int N>
+int ln1_backward(const BwdCall& bc, const BwdRoute& r) {
+  const PathWeights& w = bc.w;
+  float *dg = bc.G(bc.s.ln1_w), *db = bc.G(bc.s.ln1_b);
+  if (r.ln1_tape) return ln_backward_tape<N>(bc, "ln1 backward", bc.DY1, bc.zn1, bc.rs1, w.ln1_w, dg, db);
+  if constexpr (N == 128)
+    return ln_backward_recompute<N>(bc, CAT_OUTPROJ, "out-proj recompute + ln1 bwd", "ln1 grads", ALoadDense{bc.att, bc.M, N, 32}, w.out_w,
+                                    w.out_b, bc.x_in, w.ln1_w, bc.DY1, dg, db);
+  return DPTNAV_OK;
+}
+
+// One Linear of KOUT inputs and N outputs backward, from dz = bc.DZ:  dW = dz^T X, db = column sums of dz, out = dz W, gated by
+// X > 0 where a ReLU stood in front of the Linear (GATE; xl then loads relu(X)).  WR x WC: the GEMM-engine tile of the
+// stand-alone data gradient.  RIDE: the rider forms exist for this shape (BwdRoute says whether they are taken).
+template <int N, int KOUT, int WR, int WC, bool GATE, bool RIDE, class XL>
+int linear_backward(const BwdCall& bc, LinearForm form, int cat, const LinearNames& nm, const XL& xl, const float* X, const float* W,
+                    const float* Wpacked, float* out, float* dW, float* db) {
+  dptnav_ctx* c = bc.c;
+  BwdRun& br = bc.br;
+  const int64_t M = bc.M;
+  if constexpr (RIDE) {
+    static_assert(N == 128 && WR == 1 && WC == 4, "rider shapes");
+    if (form != LINEAR_ALONE) {
+      const ALoadDense al{bc.DZ, M, N, 32};
+      const EpiAddMaskStoreT<false, GATE> ep{out, nullptr, GATE ? X : nullptr, M, KOUT, 32, KOUT};
+      // (the grid is known only after the occupancy query inside: the column-sum rows go behind BWD_SLAB_WGS partial tiles)
+      float *slab = br.ws + br.pl.slab, *colslab = slab + (size_t)BWD_SLAB_WGS * N * KOUT;
+      int grid = 0;
+      bool took = false;
+      if (form == LINEAR_RIDER_R) {
+        const DgradRArgs a{bc.DZ, Wpacked, X, out, M, KOUT, /*relu_gate*/ GATE, nullptr, slab, colslab, BWD_SLAB_WGS};
+        if (int rc = try_dgrad_r(c, br.lane, cat, nm.ride, a, &grid, &took)) return rc;
+      }
+      if (!took) {
+        const WgradRider<KOUT, XL, true> rd{xl, slab, colslab, M};
+        if (int rc = launch_gemm<N, KOUT / 128, 1, 4, true, false>(c, br.lane, cat, nm.ride, W, bc.ntiles, 1, al, ep, nullptr, KOUT, &grid, rd))
+          return rc;
+      }
+      return reduce_slabs<N, KOUT>(c, br.lane.st, nm.both, slab, grid, colslab, dW, db);
+    }
+  }
+  constexpr int BM = 32 * WR;
+  if (int rc = weight_grads<N, KOUT>(c, br, nm, bc.DZ, M, xl, dW, db)) return rc;
+  const ALoadDense al{bc.DZ, M, N, BM};
+  const EpiAddMaskStoreT<false, GATE> ep{out, nullptr, GATE ? X : nullptr, M, KOUT, BM, KOUT};
+  return launch_gemm<N, KOUT / (32 * WC), WR, WC, true>(c, br.lane, cat, nm.dgrad, W, (M + BM - 1) / BM, 1, al, ep, nullptr, KOUT);
+}
+// ffn (DPTN: ReLU in front, the rider forms with both directions at 128 features) / fc (DPRNN):  dW, db, d h -> bc.DH
+template <int N, int NDIR>
+int ffn_backward_dirs(const BwdCall& bc, const BwdRoute& r) {
+  constexpr int KOUT = NDIR * LSTM_H;
+  static constexpr LinearNames ffn{"d ffn weight + bias", "d ffn weight", "d ffn bias", "d h", "d h + d ffn weight"};
+  static constexpr LinearNames fc{"d fc weight + bias", "d fc weight", "d fc bias", "d h", nullptr};
+  float *dW = bc.G(bc.s.ffn_w), *db = bc.G(bc.s.ffn_b);
+  if (!r.dptn)
+    return linear_backward<N, KOUT, 1, 4, false, false>(bc, LINEAR_ALONE, CAT_FFN, fc, ALoadCols{bc.hc, bc.M, KOUT, 0, 32}, bc.hc, bc.w.ffn_w,
+                                                        nullptr, bc.DH, dW, db);
+  return linear_backward<N, KOUT, 1, 4, true, N == 128 && NDIR == 2>(bc, r.ffn, CAT_FFN, ffn, ALoadColsReLU{bc.hc, bc.M, KOUT, 0, 32}, bc.hc,
+                                                                     bc.w.ffn_w, bc.packed(BWD_PACK_FFNW), bc.DH, dW, db);
+}
+template <int N>
+int ffn_backward(const BwdCall& bc, const BwdRoute& r) {
+  return r.nd == 2 ? ffn_backward_dirs<N, 2>(bc, r) : ffn_backward_dirs<N, 1>(bc, r);
+}
+// out-projection:  dW_o, db_o, d att -> bc.DATT
+template <int N>
+int out_proj_backward(const BwdCall& bc, const BwdRoute& r) {
+  using T = PathTile<N>;
+  static constexpr LinearNames nm{"d out weight + bias", "d out weight", "d out bias", "d att", "d att + d out weight"};
+  return linear_backward<N, N, T::WR, T::WC, false, N == 128>(bc, r.outp, CAT_OUTPROJ, nm, ALoadDense{bc.att, bc.M, N, 32}, bc.att, bc.w.out_w,
+                                                              bc.packed(BWD_PACK_OUTW), bc.DATT, bc.G(bc.s.out_w), bc.G(bc.s.out_b));
+}
+
+// LSTM backward, both architectures:  BPTT from d h (bc.DH) -> dP;  bias and weight gradients (x: the LSTM's input);
+// out = addend + dP_f W_ih_f + dP_b W_ih_b  (`what`: that launch's name)
+template <int N>
+int lstm_backward(const BwdCall& bc, const BwdRoute& r, const float* x, const float* addend, float* out, const char* what) {
+  using T = PathTile<N>;
+  dptnav_ctx* c = bc.c;
+  BwdRun& br = bc.br;
   Lane& lane = br.lane;
   hipStream_t st = lane.st;
-  float *qkv = tape + tp.qkv, *att = tape + tp.att, *y1 = tape + tp.y1, *hc = tape + tp.hc, *gates = tape + tp.gates,
-        *cst = tape + tp.cst;
-  float *DZ = br.ws + br.pl.dz, *DHb = br.ws + br.pl.dh, *DG = br.ws + br.pl.dg, *DY1 = br.ws + br.pl.dy1,
-        *DATT = br.ws + br.pl.datt, *DQKV = br.ws + br.pl.dqkv, *LNP = br.ws + br.pl.lnp;
-  const int64_t ntiles = (M + 31) / 32, ntiles_n = (M + BMn - 1) / BMn;
-  float* wpk = nullptr;   // this path's PACK_BWD slot
-  if (int rc = pack_for(c, st, PACK_BWD, br.all_paths, br.ws + br.pl.wiht, 2 * block + path, &wpk)) return rc;
-  int grid = 0;
-
-  // 1. push d_out through LayerNorm 2: from the tape's zn / rstd (option ln_tape), or by recomputing
-  //    z2 = relu(h) W_f^T + b_f + y1 in a GEMM whose epilogue applies the derivative
-  auto ln_from_tape = [&](const float* dout, const float* zn, const float* rs, const float* gamma, const char* gw, const char* gb) {
-    const int64_t npass = (M + 7) / 8;
-    const int lgrid = (int)std::min<int64_t>(std::min<int64_t>(BWD_LNP_WGS, 4 * (int64_t)c->num_cus), (npass + 3) / 4);
-    ProfScope ps(c, CAT_FFN, st);
-    hipLaunchKernelGGL(ln_backward_kernel<N>, dim3(lgrid), dim3(256), 0, st, dout, zn, rs, gamma, DZ, LNP, M);
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, lgrid, (int64_t)2 * N, G(gw), G(gb), N);
-    return hipGetLastError() == hipSuccess;
-  };
-  if (tp.zn2) {
-    if (!ln_from_tape(d_out, tape + tp.zn2, tape + tp.rs2, w.ln2_w, "ln2.weight", "ln2.bias")) return c->fail(DPTNAV_ERR_HIP, "ln2 backward");
-  } else if constexpr (N != 128) {
-    return c->fail(DPTNAV_ERR_INVALID, "training with num_features = %d needs option ln_tape = 1", N);
-  } else {
-    ALoadColsReLU al{hc, M, 2 * LSTM_H, 0, 32};
-    EpiLNBackward<GROUP, 0> ep{DZ, w.ffn_b, y1, w.ln2_w, d_out, LNP, M, N, 32};
-    if (int rc = launch_gemm<2 * LSTM_H, 1, 1, 4>(c, lane, CAT_FFN, "ffn recompute + ln2 bwd", w.ffn_w, ntiles, 1, al, ep,
-                                                 nullptr, 2 * LSTM_H, &grid))
-      return rc;
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)2 * N, G("ln2.weight"),
-                       G("ln2.bias"), N);
-    LAUNCH_CHECK(c, "ln2 grads");
-  }
-  // 2 + 3. ffn parameter gradients and d h = (dz2 W_f) masked by the ReLU.  Option wgrad_ride (default): ONE launch -- the
-  //        data-gradient GEMM stages the dz2 tile anyway and forms dW_f / db_f on the side (WgradRider, gemm_ws.h)
-  if (nd == 1) {   // one direction: W_f is [N][128]; the plain schedule (no rider)
-    {
-      ALoadCols yl{DZ, M, N, 0, 32};
-      ALoadColsReLU xl{hc, M, LSTM_H, 0, 32};
-      if constexpr (N == 128) {
-        if (int rc = launch_wgrad<N, LSTM_H>(c, br, "d ffn weight + bias", ntiles, yl, xl, G("ffn.1.weight"), G("ffn.1.bias"))) return rc;
-      } else {
-        if (int rc = launch_wgrad_generic<N, LSTM_H>(c, br, "d ffn weight", ntiles, yl, xl, G("ffn.1.weight"))) return rc;
-        if (int rc = launch_colsum<N>(c, br, "d ffn bias", DZ, M, N, 0, G("ffn.1.bias"))) return rc;
-      }
-    }
-    {
-      ALoadDense al{DZ, M, N, 32};
-      EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, LSTM_H, 32, LSTM_H};
-      if (int rc = launch_gemm<N, 1, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, LSTM_H)) return rc;
-    }
-  } else {
-    bool rode = false;
-    if constexpr (N == 128) {
-      if (c->opt_wgrad_ride) {
-        rode = true;
-        ALoadDense al{DZ, M, N, 32};
-        EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, 2 * LSTM_H, 32, 2 * LSTM_H};
-        float* slab = br.ws + br.pl.slab;
-        int rgrid = 0;
-        bool took = false;
-        if (c->opt_dgrad_r) {
-          const DgradRArgs a{DZ, wpk + BWD_PACK_FFNW, hc, DHb, M, 2 * LSTM_H, /*relu_gate*/ true, nullptr, slab,
-                             slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, BWD_SLAB_WGS};
-          if (int rc = try_dgrad_r(c, lane, CAT_FFN, "d h + d ffn weight", a, &rgrid, &took)) return rc;
-        }
-        // (grid known only after the occupancy query inside: the column-sum rows go behind BWD_SLAB_WGS partial tiles)
-        WgradRider<2 * LSTM_H, ALoadColsReLU, true> rd{ALoadColsReLU{hc, M, 2 * LSTM_H, 0, 32}, slab,
-                                                       slab + (size_t)BWD_SLAB_WGS * N * 2 * LSTM_H, M};
-        if (!took)
-          if (int rc = launch_gemm<N, 2, 1, 4, true, false>(c, lane, CAT_FFN, "d h + d ffn weight", w.ffn_w, ntiles, 1, al, ep, nullptr,
-                                                            2 * LSTM_H, &rgrid, rd))
-            return rc;
-        if (int rc = reduce_rider<N, 2 * LSTM_H>(c, br, "d ffn weight + bias", rgrid, BWD_SLAB_WGS, G("ffn.1.weight"), G("ffn.1.bias")))
-          return rc;
-      }
-    }
-    if (!rode) {
-      {
-        ALoadCols yl{DZ, M, N, 0, 32};
-        ALoadColsReLU xl{hc, M, 2 * LSTM_H, 0, 32};
-        if constexpr (N == 128) {
-          if (int rc = launch_wgrad<N, 2 * LSTM_H>(c, br, "d ffn weight + bias", ntiles, yl, xl, G("ffn.1.weight"), G("ffn.1.bias")))
-            return rc;
-        } else {
-          if (int rc = launch_wgrad_generic<N, 2 * LSTM_H>(c, br, "d ffn weight", ntiles, yl, xl, G("ffn.1.weight"))) return rc;
-          if (int rc = launch_colsum<N>(c, br, "d ffn bias", DZ, M, N, 0, G("ffn.1.bias"))) return rc;
-        }
-      }
-      {
-        ALoadDense al{DZ, M, N, 32};
-        EpiAddMaskStoreT<false, true> ep{DHb, nullptr, hc, M, 2 * LSTM_H, 32, 2 * LSTM_H};
-        if (int rc = launch_gemm<N, 2, 1, 4, true>(c, lane, CAT_FFN, "d h", w.ffn_w, ntiles, 1, al, ep, nullptr, 2 * LSTM_H))
-          return rc;
-      }
-    }
-  }
-  // 4. LSTM backward through time (tile height as in the forward that wrote the tape)
-  const bool use16 = lstm_use16(c, geom, nd, M);
-  const int ntl = use16 ? (geom.nseq + 15) / 16 : geom.nst;   // workgroups per direction = partial bias rows
+  const PathWeights& w = bc.w;
+  const SeqGeom& geom = bc.geom;
+  const int64_t M = bc.M, ntiles = bc.ntiles;
+  const int nd = r.nd;
   if (br.lstm_wait && hipStreamWaitEvent(st, br.lstm_wait, 0) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "bptt stagger wait");
-  const bool wg2 = c->opt_wgrad2 && N == LSTM_H && nd == 2;   // wgrad2 pairs two X operands of equal width, four slices
-  const bool side = br.side.st != nullptr && wg2;
-  if (side) {   // this path's dP goes to the buffer the weight gradients of two paths ago have (or will have) read
+  float* DG = br.ws + br.pl.dg;
+  if (r.lstm_wgrad == LSTM_WGRAD_SIDE) {   // this path's dP goes to the buffer the weight gradients of two paths ago have (or will have) read
     if (br.dg_sel) DG = br.ws + (br.dg_sel == 1 ? br.pl.dg2 : br.pl.dg3);
     if (br.wg_pending[br.dg_sel] && hipStreamWaitEvent(st, br.ev_wg[br.dg_sel], 0) != hipSuccess)
       return c->fail(DPTNAV_ERR_HIP, "side stream wait");
@@ -1701,210 +1692,184 @@ int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const floa
   }
   {
     ProfScope ps(c, CAT_LSTM, st);
-    const int rc = use16 ? lstm_bptt16_launch(ntl, nd, st, gates, cst, w.w_hh[0], w.w_hh[1], DHb, nd * LSTM_H, DG, nd * 512, (int)M,
-                                              geom, LNP)
-                         : lstm_bptt_launch(geom.nst, nd, st, gates, cst, w.w_hh[0], w.w_hh[1], DHb, nd * LSTM_H, DG, nd * 512, (int)M,
-                                            geom, LNP);
+    const int rc = r.use16 ? lstm_bptt16_launch(r.ntl, nd, st, bc.gates, bc.cst, w.w_hh[0], w.w_hh[1], bc.DH, nd * LSTM_H, DG, nd * 512, (int)M,
+                                                geom, bc.LNP)
+                           : lstm_bptt_launch(geom.nst, nd, st, bc.gates, bc.cst, w.w_hh[0], w.w_hh[1], bc.DH, nd * LSTM_H, DG, nd * 512, (int)M,
+                                              geom, bc.LNP);
     if (rc != 0) return c->fail(DPTNAV_ERR_HIP, "lstm bptt: %s", hipGetErrorString((hipError_t)rc));
   }
   if (br.lstm_record && hipEventRecord(br.lstm_record, st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "bptt stagger record");
-  // 5. LSTM parameter gradients
+  // LSTM parameter gradients
   Wgrad2Args<ALoadCols, ALoadDense, ALoadSeqShift, 4> wa{};
   float *gA[4], *gB[4];
   for (int d = 0; d < nd; ++d) {
-    const char* sfx = d ? "_reverse" : "";
-    const std::string wih = std::string("rnn.weight_ih_l0") + sfx, whh = std::string("rnn.weight_hh_l0") + sfx,
-                      bih = std::string("rnn.bias_ih_l0") + sfx, bhh = std::string("rnn.bias_hh_l0") + sfx;
     // bias gradients: per-workgroup partial rows written by the BPTT kernel
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3(512 / 32), dim3(256), 0, st, LNP + (size_t)d * ntl * 512, ntl,
-                       (int64_t)512, G(bih.c_str()), G(bhh.c_str()), -1);
+    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3(512 / 32), dim3(256), 0, st, bc.LNP + (size_t)d * r.ntl * 512, r.ntl, (int64_t)512,
+                       bc.G(bc.s.b_ih[d]), bc.G(bc.s.b_hh[d]), -1);
     LAUNCH_CHECK(c, "d lstm bias");
-    const ALoadDense xl{y1, M, N, 32};
-    const ALoadSeqShift hl = make_seq_shift(hc, M, nd * LSTM_H, d * LSTM_H, 32, d ? -1 : 1, geom);
+    const ALoadDense xl{x, M, N, 32};
+    const ALoadSeqShift hl = make_seq_shift(bc.hc, M, nd * LSTM_H, d * LSTM_H, 32, d ? -1 : 1, geom);
     for (int half = 0; half < 2; ++half) {   // 512 gate rows as 2 x 256: 16 accumulator tiles per wave would spill
       const ALoadCols yl{DG, M, nd * 512, d * 512 + half * 256, 32};
-      if (wg2) {   // W_ih and W_hh gradients in ONE pass over dP; the four (direction, half) slices in one launch
-        if constexpr (N == LSTM_H) {
-          const int s4 = 2 * d + half;
-          wa.yl[s4] = yl;
-          wa.xa[s4] = xl;
-          wa.xb[s4] = hl;
-          gA[s4] = G(wih.c_str()) + half * 256 * N;
-          gB[s4] = G(whh.c_str()) + half * 256 * LSTM_H;
-        }
+      float *d_wih = bc.G(bc.s.w_ih[d]) + half * 256 * N, *d_whh = bc.G(bc.s.w_hh[d]) + half * 256 * LSTM_H;
+      if (r.lstm_wgrad == LSTM_WGRAD_SEPARATE) {
+        if (int rc = launch_wgrad<256, N>(c, br, "d w_ih", ntiles, yl, xl, d_wih)) return rc;
+        if (int rc = launch_wgrad<256, LSTM_H>(c, br, "d w_hh", ntiles, yl, hl, d_whh)) return rc;
       } else {
-        if (int rc = launch_wgrad<256, N>(c, br, "d w_ih", ntiles, yl, xl, G(wih.c_str()) + half * 256 * N)) return rc;
-        if (int rc = launch_wgrad<256, LSTM_H>(c, br, "d w_hh", ntiles, yl, hl, G(whh.c_str()) + half * 256 * LSTM_H)) return rc;
+        const int s4 = 2 * d + half;
+        wa.yl[s4] = yl;
+        wa.xa[s4] = xl;
+        wa.xb[s4] = hl;
+        gA[s4] = d_wih;
+        gB[s4] = d_whh;
       }
     }
   }
   if constexpr (N == LSTM_H) {
-    if (wg2) {
-      if (side) {
-        if (hipEventRecord(br.ev_bptt, st) != hipSuccess || hipStreamWaitEvent(br.side.st, br.ev_bptt, 0) != hipSuccess)
-          return c->fail(DPTNAV_ERR_HIP, "side stream fork");
-        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, br.side, br.ws + br.pl.slab2)) return rc;
-        if (hipEventRecord(br.ev_wg[br.dg_sel], br.side.st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "side stream record");
-        br.wg_pending[br.dg_sel] = true;
-        br.dg_sel = (br.dg_sel + 1) % 3;
-      } else {
-        if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, lane, br.ws + br.pl.slab)) return rc;
-      }
+    if (r.lstm_wgrad == LSTM_WGRAD_SIDE) {
+      if (hipEventRecord(br.ev_bptt, st) != hipSuccess || hipStreamWaitEvent(br.side.st, br.ev_bptt, 0) != hipSuccess)
+        return c->fail(DPTNAV_ERR_HIP, "side stream fork");
+      if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, br.side, br.ws + br.pl.slab2)) return rc;
+      if (hipEventRecord(br.ev_wg[br.dg_sel], br.side.st) != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "side stream record");
+      br.wg_pending[br.dg_sel] = true;
+      br.dg_sel = (br.dg_sel + 1) % 3;
+    } else if (r.lstm_wgrad == LSTM_WGRAD_PAIRED) {
+      if (int rc = launch_wgrad2<256, N, 4>(c, br, "d w_ih + d w_hh", ntiles, wa, gA, gB, lane, br.ws + br.pl.slab)) return rc;
     }
   }
-  // 6. d y1 = dz2 (residual) + dG_f W_ih_f + dG_b W_ih_b
+  // out = addend + dP_f W_ih_f + dP_b W_ih_b
   for (int d = 0; d < nd; ++d) {
     if constexpr (N == 128) {
       bool took = false;
-      if (c->opt_dgrad_t) {
-        const DgradTArgs a{DG + d * 512, nd * 512, wpk + BWD_PACK_WIH + (size_t)d * 512 * 128, d == 0 ? DZ : DY1, DY1, M, 512};
-        if (int rc = try_dgrad_t(c, lane, CAT_LSTM_PRE, "d y1", a, &took)) return rc;
+      if (r.dgrad_t) {
+        const DgradTArgs a{DG + d * 512, nd * 512, bc.packed(BWD_PACK_WIH + (size_t)d * 512 * 128), d == 0 ? addend : out, out, M, 512};
+        if (int rc = try_dgrad_t(c, lane, CAT_LSTM_PRE, what, a, &took)) return rc;
       }
       if (took) continue;
       ALoadCols al{DG, M, nd * 512, d * 512, 32};
-      EpiAddMaskStoreT<true, false> ep{DY1, d == 0 ? DZ : DY1, nullptr, M, N, 32, N};
-      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, "d y1", w.w_ih[d], ntiles, 1, al, ep, nullptr, N))
-        return rc;
+      EpiAddMaskStoreT<true, false> ep{out, d == 0 ? addend : out, nullptr, M, N, 32, N};
+      if (int rc = launch_gemm<512, 1, 1, 4, true>(c, lane, CAT_LSTM_PRE, what, w.w_ih[d], ntiles, 1, al, ep, nullptr, N)) return rc;
     } else {
       // 64-row tiles: a 64 x 512 A tile (double buffered) does not fit the LDS, so the gate columns go in two halves
       for (int half = 0; half < 2; ++half) {
-        ALoadCols al{DG, M, nd * 512, d * 512 + half * 256, BMn};
-        EpiAddMaskStoreT<true, false> ep{DY1, d == 0 && half == 0 ? DZ : DY1, nullptr, M, N, BMn, N};
-        if (int rc = launch_gemm<256, 1, WRn, WCn, true>(c, lane, CAT_LSTM_PRE, "d y1", w.w_ih[d] + (size_t)half * 256 * N, ntiles_n, 1,
-                                                         al, ep, nullptr, N))
+        ALoadCols al{DG, M, nd * 512, d * 512 + half * 256, T::BM};
+        EpiAddMaskStoreT<true, false> ep{out, d == 0 && half == 0 ? addend : out, nullptr, M, N, T::BM, N};
+        if (int rc = launch_gemm<256, 1, T::WR, T::WC, true>(c, lane, CAT_LSTM_PRE, what, w.w_ih[d] + (size_t)half * 256 * N, bc.ntiles_n, 1,
+                                                             al, ep, nullptr, N))
           return rc;
       }
-    }
-  }
-  // 7. push d y1 through LayerNorm 1 (tape, or recompute z1 = att W_o^T + b_o + x)
-  if (tp.zn1) {
-    if (!ln_from_tape(DY1, tape + tp.zn1, tape + tp.rs1, w.ln1_w, "ln1.weight", "ln1.bias")) return c->fail(DPTNAV_ERR_HIP, "ln1 backward");
-  } else if constexpr (N != 128) {
-    return c->fail(DPTNAV_ERR_INVALID, "training with num_features = %d needs option ln_tape = 1", N);
-  } else {
-    ALoadDense al{att, M, N, 32};
-    EpiLNBackward<GROUP, 0> ep{DZ, w.out_b, x_in, w.ln1_w, DY1, LNP, M, N, 32};
-    if (int rc = launch_gemm<N, 1, 1, 4>(c, lane, CAT_OUTPROJ, "out-proj recompute + ln1 bwd", w.out_w, ntiles, 1, al, ep,
-                                        nullptr, N, &grid))
-      return rc;
-    hipLaunchKernelGGL(slab_reduce_to2_kernel, dim3((2 * N + 31) / 32), dim3(256), 0, st, LNP, grid, (int64_t)2 * N, G("ln1.weight"),
-                       G("ln1.bias"), N);
-    LAUNCH_CHECK(c, "ln1 grads");
-  }
-  // 8. out-projection gradients and d att (one launch with option wgrad_ride, as in 2 + 3)
-  bool rode8 = false;
-  if constexpr (N == 128) {
-    if (c->opt_wgrad_ride) {
-      rode8 = true;
-      ALoadDense al{DZ, M, N, 32};
-      EpiAddMaskStoreT<false, false> ep{DATT, nullptr, nullptr, M, N, 32, N};
-      float* slab = br.ws + br.pl.slab;
-      int rgrid = 0;
-      bool took = false;
-      if (c->opt_dgrad_r) {
-        const DgradRArgs a{DZ, wpk + BWD_PACK_OUTW, att, DATT, M, N, /*relu_gate*/ false, nullptr, slab, slab + (size_t)BWD_SLAB_WGS * N * N,
-                           BWD_SLAB_WGS};
-        if (int rc = try_dgrad_r(c, lane, CAT_OUTPROJ, "d att + d out weight", a, &rgrid, &took)) return rc;
-      }
-      WgradRider<N, ALoadDense, true> rd{ALoadDense{att, M, N, 32}, slab, slab + (size_t)BWD_SLAB_WGS * N * N, M};
-      if (!took)
-        if (int rc = launch_gemm<N, 1, 1, 4, true, false>(c, lane, CAT_OUTPROJ, "d att + d out weight", w.out_w, ntiles, 1, al, ep,
-                                                          nullptr, N, &rgrid, rd))
-          return rc;
-      if (int rc = reduce_rider<N, N>(c, br, "d out weight + bias", rgrid, BWD_SLAB_WGS, G("mha.out_proj.weight"), G("mha.out_proj.bias")))
-        return rc;
-    }
-  }
-  if (!rode8) {
-    {
-      ALoadCols yl{DZ, M, N, 0, 32};
-      ALoadDense xl{att, M, N, 32};
-      if constexpr (N == 128) {
-        if (int rc = launch_wgrad<N, N>(c, br, "d out weight + bias", ntiles, yl, xl, G("mha.out_proj.weight"),
-                                        G("mha.out_proj.bias")))
-          return rc;
-      } else {
-        if (int rc = launch_wgrad_generic<N, N>(c, br, "d out weight", ntiles, yl, xl, G("mha.out_proj.weight"))) return rc;
-        if (int rc = launch_colsum<N>(c, br, "d out bias", DZ, M, N, 0, G("mha.out_proj.bias"))) return rc;
-      }
-    }
-    {
-      ALoadDense al{DZ, M, N, BMn};
-      EpiAddMaskStoreT<false, false> ep{DATT, nullptr, nullptr, M, N, BMn, N};
-      if (int rc = launch_gemm<N, 1, WRn, WCn, true>(c, lane, CAT_OUTPROJ, "d att", w.out_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
-    }
-  }
-  // 9. attention backward
-  {
-    const int nkb = (geom.len + 31) / 32;
-    const float scale = 1.0f / sqrtf((float)DH);
-    float* stats = DATT == nullptr ? nullptr : br.ws + br.pl.dy1;   // dy1 is dead by now: reuse it for [token][head][4]
-    auto launch = [&](auto kern0, auto kern1, int threads) -> int {
-      const size_t lds = AttnBwdShape<DH>::lds_bytes(nkb);
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return c->fail(DPTNAV_ERR_HIP, "attention bwd lds: %s", hipGetErrorString(e));
-      ProfScope ps(c, CAT_ATTN, st);
-      const DropCfg drop = c->drop_cfg(block, path, true, br.half);
-      const unsigned long long* amask = reinterpret_cast<const unsigned long long*>(tape + tp.amask);
-      hipLaunchKernelGGL(kern0, dim3(geom.nseq, g.num_heads), dim3(threads), lds, st, qkv, att, DATT, DQKV, stats, g.num_heads, N,
-                         geom, scale, drop, reinterpret_cast<const float2*>(tape + tp.astats), amask);
-      hipLaunchKernelGGL(kern1, dim3(geom.nseq, g.num_heads), dim3(threads), lds, st, qkv, att, DATT, DQKV, stats, g.num_heads, N,
-                         geom, scale, drop, (const float2*)nullptr, amask);
-      return DPTNAV_OK;
-    };
-    int rc = DPTNAV_OK;
-    if (c->opt_train_long_seq == 2 || (c->opt_train_long_seq == 1 && nkb > 8)) {   // tiles of fixed size, any length (attn_long_train.h)
-      ProfScope ps(c, CAT_ATTN, st);
-      const DropCfg drop = c->drop_cfg(block, path, true, br.half);
-      const dim3 grid(geom.nseq, g.num_heads, (nkb + 3) / 4);
-      hipLaunchKernelGGL(attention_long_bwd_a_kernel<DH>, grid, dim3(256), 0, st, qkv, att, DATT, DQKV, stats, g.num_heads, N, geom, scale,
-                         drop, reinterpret_cast<const float2*>(tape + tp.astats));
-      hipLaunchKernelGGL(attention_long_bwd_b_kernel<DH>, grid, dim3(256), 0, st, qkv, DATT, DQKV, stats, g.num_heads, N, geom, scale, drop);
-    } else
-    switch (nkb) {
-      case 1: rc = launch(attention_bwd_kernel<DH, 1, 0>, attention_bwd_kernel<DH, 1, 1>, 64); break;
-      case 2: rc = launch(attention_bwd_kernel<DH, 2, 0>, attention_bwd_kernel<DH, 2, 1>, 128); break;
-      case 3: rc = launch(attention_bwd_kernel<DH, 3, 0>, attention_bwd_kernel<DH, 3, 1>, 192); break;
-      case 4: rc = launch(attention_bwd_kernel<DH, 4, 0>, attention_bwd_kernel<DH, 4, 1>, 256); break;
-      case 5: rc = launch(attention_bwd_kernel<DH, 5, 0>, attention_bwd_kernel<DH, 5, 1>, 320); break;
-      case 6: rc = launch(attention_bwd_kernel<DH, 6, 0>, attention_bwd_kernel<DH, 6, 1>, 384); break;
-      case 7: rc = launch(attention_bwd_kernel<DH, 7, 0>, attention_bwd_kernel<DH, 7, 1>, 448); break;
-      case 8: rc = launch(attention_bwd_kernel<DH, 8, 0>, attention_bwd_kernel<DH, 8, 1>, 512); break;
-      default: return c->fail(DPTNAV_ERR_INVALID, "attention bwd: sequence length %d > 256", geom.len);
-    }
-    if (rc) return rc;
-    LAUNCH_CHECK(c, "attention bwd");
-  }
-  // 10. in-projection gradients and d x = dz1 (residual) + dqkv W_in
-  {
-    ALoadCols yl{DQKV, M, 3 * N, 0, 32};
-    ALoadDense xl{x_in, M, N, 32};
-    if constexpr (N == 128) {
-      if (int rc = launch_wgrad<3 * N, N>(c, br, "d in weight + bias", ntiles, yl, xl, G("mha.in_proj_weight"),
-                                          G("mha.in_proj_bias")))
-        return rc;
-    } else {
-      if (int rc = launch_wgrad_generic<3 * N, N>(c, br, "d in weight", ntiles, yl, xl, G("mha.in_proj_weight"))) return rc;
-      if (int rc = launch_colsum<3 * N>(c, br, "d in bias", DQKV, M, 3 * N, 0, G("mha.in_proj_bias"))) return rc;
-    }
-  }
-  {
-    bool took = false;
-    if constexpr (N == 128) {      // d x = dz + d qkv W_in (K = 384) by dgrad_t.hip
-      if (c->opt_dgrad_t) {
-        const DgradTArgs a{DQKV, 3 * N, wpk + BWD_PACK_INW, DZ, d_in, M, 384};
-        if (int rc = try_dgrad_t(c, lane, CAT_QKV, "d x", a, &took)) return rc;
-      }
-    }
-    if (!took) {
-      ALoadDense al{DQKV, M, 3 * N, BMn};
-      EpiAddMaskStoreT<true, false> ep{d_in, DZ, nullptr, M, N, BMn, N};
-      if (int rc = launch_gemm<3 * N, 1, WRn, WCn, true>(c, lane, CAT_QKV, "d x", w.in_w, ntiles_n, 1, al, ep, nullptr, N)) return rc;
     }
   }
   return DPTNAV_OK;
+}
+
+// attention backward: d att (bc.DATT) -> d qkv (bc.DQKV), two launches
+template <int DH, int NKB>
+int launch_attn_bwd(const BwdCall& bc, float* stats) {
+  dptnav_ctx* c = bc.c;
+  hipStream_t st = bc.br.lane.st;
+  const int heads = c->cfg.num_heads, N = 4 * DH;
+  auto kern0 = attention_bwd_kernel<DH, NKB, 0>;
+  auto kern1 = attention_bwd_kernel<DH, NKB, 1>;
+  const size_t lds = AttnBwdShape<DH>::lds_bytes(NKB);
+  static PerDeviceOnce ready;   // per instantiation and device
+  if (!ready.done(c->device_id)) {
+    if (int rc = set_lds(c, kern0, lds, "attention bwd")) return rc;
+    if (int rc = set_lds(c, kern1, lds, "attention bwd")) return rc;
+    ready.set(c->device_id);
+  }
+  ProfScope ps(c, CAT_ATTN, st);
+  const DropCfg drop = c->drop_cfg(bc.block, bc.path, true, bc.br.half);
+  const float scale = 1.0f / sqrtf((float)DH);
+  const unsigned long long* amask = reinterpret_cast<const unsigned long long*>(bc.amask);
+  hipLaunchKernelGGL(kern0, dim3(bc.geom.nseq, heads), dim3(64 * NKB), lds, st, bc.qkv, bc.att, bc.DATT, bc.DQKV, stats, heads, N, bc.geom, scale,
+                     drop, reinterpret_cast<const float2*>(bc.astats), amask);
+  hipLaunchKernelGGL(kern1, dim3(bc.geom.nseq, heads), dim3(64 * NKB), lds, st, bc.qkv, bc.att, bc.DATT, bc.DQKV, stats, heads, N, bc.geom, scale,
+                     drop, (const float2*)nullptr, amask);
+  return DPTNAV_OK;
+}
+template <int N>
+int attention_backward(const BwdCall& bc, const BwdRoute& r) {
+  constexpr int DH = PathTile<N>::DH;
+  dptnav_ctx* c = bc.c;
+  hipStream_t st = bc.br.lane.st;
+  float* stats = bc.DY1;   // dy1 is dead by now: reuse it for [token][head][4]
+  int rc = DPTNAV_OK;
+  if (r.attn_long) {
+    const int heads = c->cfg.num_heads;
+    const float scale = 1.0f / sqrtf((float)DH);
+    ProfScope ps(c, CAT_ATTN, st);
+    const DropCfg drop = c->drop_cfg(bc.block, bc.path, true, bc.br.half);
+    const dim3 grid(bc.geom.nseq, heads, (r.nkb + 3) / 4);
+    hipLaunchKernelGGL(attention_long_bwd_a_kernel<DH>, grid, dim3(256), 0, st, bc.qkv, bc.att, bc.DATT, bc.DQKV, stats, heads, N, bc.geom, scale,
+                       drop, reinterpret_cast<const float2*>(bc.astats));
+    hipLaunchKernelGGL(attention_long_bwd_b_kernel<DH>, grid, dim3(256), 0, st, bc.qkv, bc.DATT, bc.DQKV, stats, heads, N, bc.geom, scale, drop);
+  } else {
+    switch (r.nkb) {
+      case 1: rc = launch_attn_bwd<DH, 1>(bc, stats); break;
+      case 2: rc = launch_attn_bwd<DH, 2>(bc, stats); break;
+      case 3: rc = launch_attn_bwd<DH, 3>(bc, stats); break;
+      case 4: rc = launch_attn_bwd<DH, 4>(bc, stats); break;
+      case 5: rc = launch_attn_bwd<DH, 5>(bc, stats); break;
+      case 6: rc = launch_attn_bwd<DH, 6>(bc, stats); break;
+      case 7: rc = launch_attn_bwd<DH, 7>(bc, stats); break;
+      default: rc = launch_attn_bwd<DH, 8>(bc, stats); break;   // (beyond 8 blocks: refused by the route)
+    }
+  }
+  if (rc) return rc;
+  LAUNCH_CHECK(c, "attention bwd");
+  return DPTNAV_OK;
+}
+
+// in-projection:  dW_in, db_in;  d_in = dz1 (residual) + d qkv W_in
+template <int N>
+int in_proj_backward(const BwdCall& bc, const BwdRoute& r) {
+  using T = PathTile<N>;
+  dptnav_ctx* c = bc.c;
+  Lane& lane = bc.br.lane;
+  const int64_t M = bc.M;
+  static constexpr LinearNames nm{"d in weight + bias", "d in weight", "d in bias", "d x", nullptr};
+  if (int rc = weight_grads<3 * N, N>(c, bc.br, nm, bc.DQKV, M, ALoadDense{bc.x_in, M, N, 32}, bc.G(bc.s.in_w), bc.G(bc.s.in_b))) return rc;
+  if constexpr (N == 128) {      // K = 384 by dgrad_t.hip
+    if (r.dgrad_t) {
+      bool took = false;
+      const DgradTArgs a{bc.DQKV, 3 * N, bc.packed(BWD_PACK_INW), bc.DZ, bc.d_in, M, 384};
+      if (int rc = try_dgrad_t(c, lane, CAT_QKV, nm.dgrad, a, &took)) return rc;
+      if (took) return DPTNAV_OK;
+    }
+  }
+  ALoadDense al{bc.DQKV, M, 3 * N, T::BM};
+  EpiAddMaskStoreT<true, false> ep{bc.d_in, bc.DZ, nullptr, M, N, T::BM, N};
+  return launch_gemm<3 * N, 1, T::WR, T::WC, true>(c, lane, CAT_QKV, nm.dgrad, bc.w.in_w, bc.ntiles_n, 1, al, ep, nullptr, N);
+}
+
+// ---- one path backward: route, then the stages ------------------------------------------------------------------------------
+template <int N>
+int run_path_backward(dptnav_ctx* c, BwdRun& br, int block, int path, const float* x_in, const float* d_out,
+                      float* d_in, int B, int S, float* tape, const PathTape& tp) {
+  BwdRoute r;
+  if (int rc = route_path_backward<N>(c, br, block, path, B, S, tp, &r)) return rc;
+  const int64_t M = (int64_t)B * S * c->cfg.chunk_size;
+  float* ws = br.ws;
+  const BwdPlan& pl = br.pl;
+  BwdCall bc{c, br, c->pw[2 * block + path], c->ps[2 * block + path], make_geom(path, B, S, c->cfg.chunk_size), block, path,
+             M, (M + 31) / 32, (M + PathTile<N>::BM - 1) / PathTile<N>::BM, x_in, d_out, d_in,
+             tape + tp.qkv, tape + tp.att, tape + tp.y1, tape + tp.hc, tape + tp.gates, tape + tp.cst, tape + tp.astats, tape + tp.amask,
+             tape + tp.zn1, tape + tp.rs1, tape + tp.zn2, tape + tp.rs2,
+             ws + pl.dz, ws + pl.dh, ws + pl.dy1, ws + pl.datt, ws + pl.dqkv, ws + pl.lnp, nullptr};
+  if (r.pack) {
+    float* wpk = nullptr;
+    if (int rc = pack_for(c, br.lane.st, PACK_BWD, br.all_paths, ws + pl.wiht, 2 * block + path, &wpk)) return rc;
+    bc.wpk = wpk;
+  }
+  if (int rc = ln2_backward<N>(bc, r)) return rc;
+  if (int rc = ffn_backward<N>(bc, r)) return rc;
+  if (!r.dptn) return lstm_backward<N>(bc, r, x_in, d_out, d_in, "d x");
+  if (int rc = lstm_backward<N>(bc, r, bc.y1, bc.DZ, bc.DY1, "d y1")) return rc;
+  if (int rc = ln1_backward<N>(bc, r)) return rc;
+  if (int rc = out_proj_backward<N>(bc, r)) return rc;
+  if (int rc = attention_backward<N>(bc, r)) return rc;
+  return in_proj_backward<N>(bc, r);
 }
 
 // =================================================================================================
@@ -2000,15 +1965,9 @@ int run_tail_backward(dptnav_ctx* c, BwdRun& br, const float* x, const float* E,
   // post-processing conv gradients; d u = d q W_post
   if (int rc = launch_colsum<N>(c, br, "d postproc bias", DQ, rows, N, 0, G("dprnn.postprocessing.0.bias"))) return rc;
   {
-    ALoadCols yl{DQ, rows, N, 0, 32};
+    static constexpr LinearNames nm{"d postproc weight", "d postproc weight", nullptr, nullptr, nullptr};   // (the bias: above)
     ALoadOla xl{Z, N, B, (int)L, S, K, P, left, ola, 32};
-    if constexpr (N == 128) {
-      if (int rc = launch_wgrad<N, N>(c, br, "d postproc weight", (rows + 31) / 32, yl, xl, G("dprnn.postprocessing.0.weight")))
-        return rc;
-    } else {
-      if (int rc = launch_wgrad_generic<N, N>(c, br, "d postproc weight", (rows + 31) / 32, yl, xl, G("dprnn.postprocessing.0.weight")))
-        return rc;
-    }
+    if (int rc = weight_grads<N, N>(c, br, nm, DQ, rows, xl, G("dprnn.postprocessing.0.weight"), nullptr)) return rc;
   }
   {
     ALoadDense al{DQ, rows, N, BMn};
@@ -2109,21 +2068,6 @@ int begin_run(dptnav_ctx* c, Run* run, float* ws, const Plan& pl, hipStream_t st
   return DPTNAV_OK;
 }
 
-// Join the caller's stream to BOTH internal streams (always, also after a failed enqueue: kernels already queued there
-// must be ordered before whatever the caller does next) and return the body's error, or the join's if the body was fine.
-int join_after(dptnav_ctx* c, hipStream_t st, bool forked, int rc_body, int nstreams = 2) {
-  if (!forked) return rc_body;
-  const std::string body_err = c->err;
-  bool ok = true;
-  for (int s = 0; s < nstreams; ++s)
-    ok &= hipEventRecord(c->ev_join[s], c->streams[s]) == hipSuccess && hipStreamWaitEvent(st, c->ev_join[s], 0) == hipSuccess;
-  if (rc_body) {
-    c->err = body_err;
-    return rc_body;
-  }
-  return ok ? DPTNAV_OK : c->fail(DPTNAV_ERR_HIP, "join event");
-}
-
 }  // namespace
 
 // =================================================================================================
@@ -2205,9 +2149,10 @@ int dptnav_bind_weights(dptnav_handle h, const float* const* dev_ptrs, int n) {
       return h->fail(DPTNAV_ERR_WEIGHTS, "%s is not 16-byte aligned", h->names[i].c_str());
   }
   h->ptr.assign(dev_ptrs, dev_ptrs + n);
-  h->pw.clear();
+  h->pw.resize((size_t)2 * h->cfg.num_blocks);
+  h->ps.resize(h->pw.size());
   for (int b = 0; b < h->cfg.num_blocks; ++b)
-    for (int p = 0; p < 2; ++p) h->pw.push_back(path_weights(h, b, p));
+    for (int p = 0; p < 2; ++p) resolve_path(h, b, p, &h->ps[2 * b + p], &h->pw[2 * b + p]);
   h->bound = true;
   return DPTNAV_OK;
 }
@@ -2217,6 +2162,21 @@ int64_t dptnav_frames(dptnav_handle h, int64_t T) {
 }
 int64_t dptnav_chunks(dptnav_handle h, int64_t T) {
   return h ? (dptnav_frames(h, T) - h->cfg.chunk_size) / h->cfg.step_size + 1 : -1;
+}
+
+// Join the caller's stream to BOTH internal streams (always, also after a failed enqueue: kernels already queued there
+// must be ordered before whatever the caller does next) and return the body's error, or the join's if the body was fine.
+static int join_after(dptnav_ctx* c, hipStream_t st, bool forked, int rc_body, int nstreams = 2) {
+  if (!forked) return rc_body;
+  const std::string body_err = c->err;
+  bool ok = true;
+  for (int s = 0; s < nstreams; ++s)
+    ok &= hipEventRecord(c->ev_join[s], c->streams[s]) == hipSuccess && hipStreamWaitEvent(st, c->ev_join[s], 0) == hipSuccess;
+  if (rc_body) {
+    c->err = body_err;
+    return rc_body;
+  }
+  return ok ? DPTNAV_OK : c->fail(DPTNAV_ERR_HIP, "join event");
 }
 
 // How dptnav_forward cuts a batch: sub-batches small enough that every recurrence launch fits the 16-sequence-tile kernel
