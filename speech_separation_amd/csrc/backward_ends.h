@@ -148,11 +148,14 @@ struct EpiPReLUBwd {
 // head backward, step 1: one thread group per frame (b, l):
 //   dE = DQ[spk 0] + DQ[spk 1] (decoder skip) + chunking backward (dX0 of the <= 2 chunks holding the frame)
 //   video gate: fused = enc + tanh(gate) * LN(interp(vid))  ->  d tanh(gate), d LN params (partials), d interp(vid)
+//   d tanh(gate) = sum dE * (zn * gamma + beta) is accumulated here in both of its terms, from dE itself: rebuilding the beta
+//   term from d beta_v = tanh(gate) * sum dE needs a division by tanh(gate), which loses the term at gate == 0.
 // ------------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void head_bwd_frames_kernel(const float* __restrict__ DQ, const float* __restrict__ dX0,
                                                                const float* __restrict__ vid, const float* __restrict__ gate,
-                                                               const float* __restrict__ ln_w, float* __restrict__ DE,
+                                                               const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                               float* __restrict__ DE,
                                                                float* __restrict__ DVI, float* __restrict__ partials,
                                                                int B, int L, int Tv, int S, int K, int P) {
   constexpr int GROUP = N / 4, FPB = 256 / GROUP;
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(256) void head_bwd_frames_kernel(const float* __res
   if (!ok) de = make_float4(0.f, 0.f, 0.f, 0.f);
   if (ok) *reinterpret_cast<float4*>(DE + ((int64_t)b * L + l) * N + 4 * c4) = de;
   float4 sgam = make_float4(0.f, 0.f, 0.f, 0.f), sbet = sgam;
-  float sgate = 0.f;
+  float sgate = 0.f, sgate_b = 0.f;
   if (vid != nullptr) {
     const float scale = (float)Tv / (float)L;
     float src = ((float)lc + 0.5f) * scale - 0.5f;
@@ -197,13 +200,13 @@ __global__ __launch_bounds__(256) void head_bwd_frames_kernel(const float* __res
     const float rstd = rsqrtf(group_sum<GROUP>(q) * (1.0f / N) + 1e-5f);
     const float tg = tanhf(*gate);
     const float4 ga = *reinterpret_cast<const float4*>(ln_w + 4 * c4);
+    const float4 be = *reinterpret_cast<const float4*>(ln_b + 4 * c4);
     const float dv[4] = {de.x, de.y, de.z, de.w}, gam[4] = {ga.x, ga.y, ga.z, ga.w};
     float zn[4], g[4];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       zn[i] = u[i] * rstd;
-      // d tanh(gate) needs the LN output itself: zn*gamma + beta; beta's part is added on the host side reduce
       g[i] = tg * dv[i] * gam[i];
       s1 += g[i];
       s2 += g[i] * zn[i];
@@ -213,16 +216,16 @@ __global__ __launch_bounds__(256) void head_bwd_frames_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = rstd * (g[i] - m1 - zn[i] * m2);
     if (ok) *reinterpret_cast<float4*>(DVI + ((int64_t)b * L + l) * N + 4 * c4) = make_float4(o[0], o[1], o[2], o[3]);
-    // per-thread partials: d gamma_v = tg*dE*zn, d beta_v = tg*dE, d tanh(gate) = sum dE*(zn*gamma + beta) -- the beta
-    // term equals <d beta_v, beta>/tg and is formed from the reduced d beta_v on the host side kernel
+    // per-thread partials: d gamma_v = tg*dE*zn, d beta_v = tg*dE, d tanh(gate) = sum dE*zn*gamma + sum dE*beta
     sgam = make_float4(tg * dv[0] * zn[0], tg * dv[1] * zn[1], tg * dv[2] * zn[2], tg * dv[3] * zn[3]);
     sbet = make_float4(tg * dv[0], tg * dv[1], tg * dv[2], tg * dv[3]);
     sgate = dv[0] * zn[0] * gam[0] + dv[1] * zn[1] * gam[1] + dv[2] * zn[2] * gam[2] + dv[3] * zn[3] * gam[3];
+    sgate_b = dv[0] * be.x + dv[1] * be.y + dv[2] * be.z + dv[3] * be.w;
   }
-  // block partials: [blk][0:N) d gamma_v | [N:2N) d beta_v | [2N] d tanh(gate) without the beta term
+  // block partials: [blk][0:N) d gamma_v | [N:2N) d beta_v | [2N] d tanh(gate), gamma term | [2N+1] its beta term
   red[0][threadIdx.x] = sgam;
   red[1][threadIdx.x] = sbet;
-  red[2][threadIdx.x] = make_float4(sgate, 0.f, 0.f, 0.f);
+  red[2][threadIdx.x] = make_float4(sgate, sgate_b, 0.f, 0.f);
   __syncthreads();
   float* p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (2 * N + 4);
   if (threadIdx.x < GROUP) {
@@ -235,33 +238,26 @@ __global__ __launch_bounds__(256) void head_bwd_frames_kernel(const float* __res
     *reinterpret_cast<float4*>(p + N + 4 * threadIdx.x) = c;
   }
   if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int k = 0; k < 256; ++k) s += red[2][k].x;
+    float s = 0.f, sb = 0.f;
+    for (int k = 0; k < 256; ++k) { s += red[2][k].x; sb += red[2][k].y; }
     p[2 * N] = s;
-    p[2 * N + 1] = p[2 * N + 2] = p[2 * N + 3] = 0.f;
+    p[2 * N + 1] = sb;
+    p[2 * N + 2] = p[2 * N + 3] = 0.f;
   }
 }
 
-// finish the gate gradient: d gate = (1 - tanh(gate)^2) * (S_gate + <d beta_v, beta_v> / tanh(gate)), where the
-// reduced vector holds [d gamma_v | d beta_v | S_gate]
+// finish the gate gradient: d gate = (1 - tanh(gate)^2) * (S_gamma + S_beta), where the reduced vector holds
+// [d gamma_v | d beta_v | S_gamma | S_beta]
 __global__ void gate_grad_finish_kernel(const float* __restrict__ reduced, const float* __restrict__ gate,
-                                        const float* __restrict__ ln_b, float* __restrict__ g_gate,
-                                        float* __restrict__ g_lnw, float* __restrict__ g_lnb, int N) {
-  __shared__ float red[256];
-  const float tg = tanhf(*gate);
-  float s = 0.f;
+                                        float* __restrict__ g_gate, float* __restrict__ g_lnw, float* __restrict__ g_lnb,
+                                        int N) {
   for (int i = threadIdx.x; i < N; i += blockDim.x) {
     g_lnw[i] = reduced[i];
     g_lnb[i] = reduced[N + i];
-    // d beta_v = tg * sum dE  ->  sum dE * beta = d beta_v * beta / tg
-    s += (tg != 0.f ? reduced[N + i] / tg : 0.f) * ln_b[i];
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
   if (threadIdx.x == 0) {
-    float t = reduced[2 * N];
-    for (int k = 0; k < (int)blockDim.x; ++k) t += red[k];
-    *g_gate = t * (1.f - tg * tg);
+    const float tg = tanhf(*gate);
+    *g_gate = (reduced[2 * N] + reduced[2 * N + 1]) * (1.f - tg * tg);
   }
 }
 

@@ -2012,13 +2012,14 @@ int run_head_backward(dptnav_ctx* c, BwdRun& br, const float* mix, const float* 
   const bool av = !g.audio_only;
   const unsigned gx = (unsigned)((L + FPB - 1) / FPB);
   hipLaunchKernelGGL(head_bwd_frames_kernel<N>, dim3(gx, B), dim3(256), 0, st, DQ, dX0, av ? vid : nullptr,
-                     av ? c->w("gate") : nullptr, av ? c->w("video_ln.weight") : nullptr, DE, DVI, slab, B, (int)L, Tv, S,
+                     av ? c->w("gate") : nullptr, av ? c->w("video_ln.weight") : nullptr, av ? c->w("video_ln.bias") : nullptr,
+                     DE, DVI, slab, B, (int)L, Tv, S,
                      g.chunk_size, g.step_size);
   LAUNCH_CHECK(c, "head backward frames");
   if (av) {
     const int64_t cnt = 2 * N + 4;
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((cnt + 31) / 32)), dim3(256), 0, st, slab, (int)(gx * B), cnt, red, 0);
-    hipLaunchKernelGGL(gate_grad_finish_kernel, dim3(1), dim3(128), 0, st, red, c->w("gate"), c->w("video_ln.bias"), G("gate"),
+    hipLaunchKernelGGL(gate_grad_finish_kernel, dim3(1), dim3(128), 0, st, red, c->w("gate"), G("gate"),
                        G("video_ln.weight"), G("video_ln.bias"), N);
     hipLaunchKernelGGL(interp_bwd_kernel, dim3(Tv, B), dim3(512), 0, st, DVI, DV, N, (int)L, Tv);
     {

@@ -60,6 +60,10 @@ VARIANTS = {
     "unidir64": (_cfg(DPTN_AUDIO, num_blocks=2, bidir=False), {}, 4, 8000, 1, 2),
     "split_bf16": (_cfg(DPTN_AV, num_blocks=2), {"split_bf16": 1}, 5, 8000, 13, 0),
     "ragged": (_cfg(DPTN_AV, num_blocks=1, chunk_size=50, step_size=25, kernel_size_enc=5), {}, 3, 3001, 5, 2),
+    # chunk 21 / step 5 (K > 2P and odd: the generic chunk loop of taps_fold_kernel instead of its two-row form), 8 encoder
+    # taps, 65 frames of which the last 4 belong to no chunk, 3 waveform samples that no frame covers: the geometry
+    # tests/path_ends_cases.py calls MEMSAFETY_GEOMETRY, whose values tests/test_gpu_path_ends.py checks
+    "path_ends": (_cfg(DPTN_AV, num_blocks=1, chunk_size=21, step_size=5, kernel_size_enc=8), {}, 3, 267, 13, 2),
     "full": (_cfg(DPTN_AV), {}, 16, 32000, 50, 16),
     # train-mode attention dropout (the default training configuration; every variant above runs the training step with
     # dropout off): the keep mask is a pure function of (seed, token, head, key), so every check holds unchanged
