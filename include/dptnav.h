@@ -155,6 +155,12 @@ int dptnav_workspace_tap(dptnav_handle h, int B, int64_t T, int Tv, const char* 
 int dptnav_bind_grads(dptnav_handle h, float* const* dev_ptrs, int n);
 size_t dptnav_train_path_tape_bytes(dptnav_handle h, int B, int S);
 size_t dptnav_train_bwd_workspace_bytes(dptnav_handle h, int B, int S);
+/* Introspection for tests: where (bytes from the tape's base) a tensor of the tape that dptnav_train_path_forward wrote
+ * lies, and its size in floats.  "qkv" (M,3N), "att" (M,N), "y1" (M,N) [post-LN1], "hc" (M + S*K, 2H) [raw LSTM output,
+ * h_fwd|h_bwd; the last S*K rows are padding], and under option ln_tape = 1 the LayerNorm rows "zn1" / "zn2" (M,N)
+ * [normalised, before gamma / beta] with "rs1" / "rs2" (M) [1/sigma].  A tensor the tape does not hold (the attention
+ * half's of a DPRNN model, zn* / rs* under ln_tape = 0) and an unknown name return non-zero with a message. */
+int dptnav_train_path_tape_tap(dptnav_handle h, int B, int S, const char* name, size_t* offset_bytes, size_t* numel);
 int dptnav_train_path_forward(dptnav_handle h, int block, int path, const float* x_in, float* x_out, int B, int S,
                               void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
 int dptnav_train_path_backward(dptnav_handle h, int block, int path, const float* x_in, const float* d_out, float* d_in,

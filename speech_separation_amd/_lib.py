@@ -48,6 +48,7 @@ SYMBOLS = {
     "dptnav_bind_grads": (_i, [_vp, C.POINTER(_fp), _i]),
     "dptnav_train_path_tape_bytes": (_sz, [_vp, _i, _i]),
     "dptnav_train_bwd_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "dptnav_train_path_tape_tap": (_i, [_vp, _i, _i, C.c_char_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "dptnav_train_path_forward": (_i, [_vp, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "dptnav_train_path_backward": (_i, [_vp, _i, _i, _fp, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "dptnav_train_tape_bytes": (_sz, [_vp, _i, _i64, _i]),

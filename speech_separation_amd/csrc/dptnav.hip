@@ -1585,9 +1585,14 @@ int ln2_backward(const BwdCall& bc, const BwdRoute& r) {
   const PathWeights& w = bc.w;
   float *dg = bc.G(bc.s.ln2_w), *db = bc.G(bc.s.ln2_b);
   if (r.ln2_tape) return ln_backward_tape<N>(bc, r.dptn ? "ln2 backward" : "norm1d backward", bc.d_out, bc.zn2, bc.rs2, w.ln2_w, dg, db);
-  if constexpr (N == 128)
+  if constexpr (N == 128) {
+    // (one LSTM direction -- the inter-chunk path of a bidir = False model: hc rows and ffn.1.weight are LSTM_H wide)
+    if (r.nd == 1)
+      return ln_backward_recompute<LSTM_H>(bc, CAT_FFN, "ffn recompute + ln2 bwd", "ln2 grads", ALoadColsReLU{bc.hc, bc.M, LSTM_H, 0, 32},
+                                           w.ffn_w, w.ffn_b, bc.y1, w.ln2_w, bc.d_out, dg, db);
     return ln_backward_recompute<2 * LSTM_H>(bc, CAT_FFN, "ffn recompute + ln2 bwd", "ln2 grads", ALoadColsReLU{bc.hc, bc.M, 2 * LSTM_H, 0, 32},
                                              w.ffn_w, w.ffn_b, bc.y1, w.ln2_w, bc.d_out, dg, db);
+  }
   return DPTNAV_OK;   // (refused by the route)
 }
 template <int N>
@@ -2519,6 +2524,32 @@ size_t dptnav_train_bwd_workspace_bytes(dptnav_handle h, int B, int S) {
   BwdPlan p;
   make_bwd_plan(h, B, S, &p);
   return p.total * sizeof(float);
+}
+// Where one tensor of a path's tape lies (read-only, for tests): the counterpart of dptnav_workspace_tap for the tape that
+// dptnav_train_path_forward writes.  A tensor the tape does not hold under the handle's configuration is an error.
+int dptnav_train_path_tape_tap(dptnav_handle h, int B, int S, const char* name, size_t* off, size_t* numel) {
+  if (!h) return DPTNAV_ERR_INVALID;
+  if (!name || !off || !numel || B < 1 || S < 1) return h->fail(DPTNAV_ERR_INVALID, "train_path_tape_tap: bad argument");
+  PathTape t;
+  make_path_tape(h, B, S, &t);
+  const dptnav_config& g = h->cfg;
+  const size_t M = (size_t)B * S * g.chunk_size, N = g.num_features;
+  const bool dptn = g.arch == 0, lnt = h->opt_ln_tape != 0;
+  const std::string n(name);
+  const bool attention = n == "qkv" || n == "att" || n == "y1" || n == "zn1" || n == "rs1";
+  const bool ln = n == "zn1" || n == "rs1" || n == "zn2" || n == "rs2";
+  if (!attention && !ln && n != "hc") return h->fail(DPTNAV_ERR_INVALID, "unknown tape tensor '%s'", name);
+  if (attention && !dptn) return h->fail(DPTNAV_ERR_INVALID, "tape tensor '%s': a DPRNN path has no attention half", name);
+  if (ln && !lnt) return h->fail(DPTNAV_ERR_INVALID, "tape tensor '%s': the tape holds no LayerNorm rows under ln_tape = 0", name);
+  if (n == "qkv") { *off = t.qkv * 4; *numel = M * 3 * N; }
+  else if (n == "att") { *off = t.att * 4; *numel = M * N; }
+  else if (n == "y1") { *off = t.y1 * 4; *numel = M * N; }
+  else if (n == "hc") { *off = t.hc * 4; *numel = (M + (size_t)S * g.chunk_size) * 2 * g.hidden_dim; }
+  else if (n == "zn1") { *off = t.zn1 * 4; *numel = M * N; }
+  else if (n == "rs1") { *off = t.rs1 * 4; *numel = M; }
+  else if (n == "zn2") { *off = t.zn2 * 4; *numel = M * N; }
+  else { *off = t.rs2 * 4; *numel = M; }
+  return DPTNAV_OK;
 }
 int dptnav_train_path_forward(dptnav_handle h, int block, int path, const float* x_in, float* x_out, int B, int S,
                               void* tape, size_t tape_bytes, void* ws, size_t ws_bytes, void* stream) {

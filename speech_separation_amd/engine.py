@@ -330,6 +330,17 @@ class DptnEngine:
             self._raise(rc, "dptnav_train_path_forward")
         return y, tape
 
+    def tape_tap(self, tape: torch.Tensor, name: str, B: int, S: int) -> torch.Tensor:
+        """Flat float32 view of tensor `name` (qkv, att, y1, hc, zn1, rs1, zn2, rs2) of a tape of train_path_forward(x[B][S]);
+        a tensor the tape does not hold under the engine's configuration and options raises (tests)."""
+        off, n = C.c_size_t(), C.c_size_t()
+        rc = self.lib.dptnav_train_path_tape_tap(self._h, B, S, name.encode(), C.byref(off), C.byref(n))
+        if rc:
+            self._raise(rc, "dptnav_train_path_tape_tap")
+        if off.value + 4 * n.value > tape.numel():
+            raise ValueError(f"tape_tap: the tape holds {tape.numel()} bytes, '{name}' ends at {off.value + 4 * n.value}")
+        return tape[off.value:off.value + 4 * n.value].view(torch.float32)
+
     def train_path_backward(self, block: int, path: int, x: torch.Tensor, dy: torch.Tensor, tape: torch.Tensor):
         B, S, K, N = x.shape
         dy = _check(dy, "dy", tuple(x.shape), self.device)
