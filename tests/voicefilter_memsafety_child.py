@@ -6,7 +6,8 @@ mode  poison       outputs and workspace start filled with 0xFF bytes
       guard_start  every buffer STARTS flush against an unmapped page
 
 vfilt_forward (74 bound tensors) runs through the C ABI at (input_size, W, Tv, B) = (17, 7, 1, 3) -- F below the reach of
-dilations 8 and 16, W below the 7-tap width, one video frame -- and (33, 50, 3, 1), under test first, then with plain
+dilations 8 and 16, W below the 7-tap width, one video frame --, (33, 50, 3, 1), (257, 7, 2, 1) -- the end of the range -- and (16, 8, 2, 8) -- exactly 1024 positions,
+16 sequences --, under test first, then with plain
 zero-filled buffers: every output element must have been written (no 0xFF pattern left) and the results must be
 bit-identical.
 
@@ -28,7 +29,7 @@ import torch  # noqa: E402
 from speech_separation_amd import _lib  # noqa: E402
 from tests import voicefilter_ref as R  # noqa: E402
 
-SHAPES = [(17, 7, 1, 3), (33, 50, 3, 1)]
+SHAPES = [(17, 7, 1, 3), (33, 50, 3, 1), (257, 7, 2, 1), (16, 8, 2, 8)]
 EMBED = 1024
 
 

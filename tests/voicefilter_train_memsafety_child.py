@@ -7,7 +7,8 @@ mode  poison       outputs, workspace and gradient buffers start filled with 0xF
       guard_start  every buffer STARTS flush against an unmapped page
 
 vftrain_train_forward + vftrain_train_backward (74 bound tensors, 74 gradient slots) run through the C ABI at
-(input_size, W, Tv, B) = (17, 7, 1, 3) and (33, 50, 3, 1), under test first, then with plain zero-filled buffers: every
+(input_size, W, Tv, B) = (17, 7, 1, 3), (33, 50, 3, 1), (257, 7, 2, 1) -- the end of the range: every VF_FMAX-sized array full --
+and (16, 8, 2, 8) -- exactly 1024 positions and 16 sequences, every chunk and group full --, under test first, then with plain zero-filled buffers: every
 output and every written gradient element must have been written (no 0xFF pattern left), the 16 running-statistics slots
 must keep their fill, and the results must be bit-identical.
 
@@ -29,7 +30,7 @@ import torch  # noqa: E402
 from speech_separation_amd import _lib  # noqa: E402
 from tests import voicefilter_ref as R  # noqa: E402
 
-SHAPES = [(17, 7, 1, 3), (33, 50, 3, 1)]
+SHAPES = [(17, 7, 1, 3), (33, 50, 3, 1), (257, 7, 2, 1), (16, 8, 2, 8)]
 EMBED = 1024
 PPM, SEED = 350000, 20240
 

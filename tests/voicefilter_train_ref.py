@@ -104,6 +104,22 @@ class Run:
         return out
 
 
+class _PlainGrad(torch.autograd.Function):
+    """Identity whose backward hands on a gradient in plain contiguous strides.  The map leaves the CNN through
+    permute(0, 3, 2, 1).contiguous(), whose backward returns strides (8 F W, 1, 8, 8 F) for a (B, 8, F, W) tensor; at W = 1 or
+    F = 1 those are exactly channels-last strides, and torch's CPU batch_norm backward then reads the gradient in one layout
+    and its input in the other: d beta is no longer the channel sum of the incoming gradient, and every CNN gradient behind
+    it is wrong, in fp32 and fp64 alike (tests/test_voicefilter_values_host.py shows it).  The values are untouched."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.clone(memory_format=torch.contiguous_format)
+
+
 def _relu(x, mask):
     return F_.relu(x) if mask is None else x * mask.to(x.dtype)
 
@@ -151,7 +167,7 @@ def forward(weights, mix, e1, e2, dtype=torch.float64, keep=None, relu_masks=Non
         run.Z.append(z)
         run.stats.append((z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=True)))
         p = f"cnn_layers.{bi}."
-        x = F_.batch_norm(z, None, None, w[p + "weight"], w[p + "bias"], True, MOMENTUM, BN_EPS)
+        x = _PlainGrad.apply(F_.batch_norm(z, None, None, w[p + "weight"], w[p + "bias"], True, MOMENTUM, BN_EPS))
         if l < 7:
             x = _relu(x, None if relu_masks is None else relu_masks["cnn"][l])
         run.act.append(x)
